@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- MFCC + modulation-spectrum frames/s on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path (MFCC, then the trajectory rFFT) over one batch of synthetic
 clips that is already resident in HBM.  Per-GPU workload = BASELINE.json configs[2]: 1024 clips x
@@ -9,7 +9,19 @@ clips that is already resident in HBM.  Per-GPU workload = BASELINE.json configs
 every rank processes its own 1024 clips (weak scaling; N = 8 is configs[4], 8192 clips) and ONE RCCL
 gather moves every rank's output slab to rank 0 inside the timed region.
 
-Prints one JSON line (rank 0) with `value` = whole-job frames/s, plus
+A plain run does only what the headline needs: set up the batch (rows 0, R/2 and R-1 carry three
+oracle clips unless --no-check, so that the inputs are those of a --full run), run the step untimed
+for --settle-ms (the GPU's clocks leave their idle state), run W warm-up steps, time K steps, write
+the last timed step's outputs when --dump-outputs DIR is given, and print one JSON line (rank 0)
+with `value` = whole-job frames/s and `ms_per_step` = wall milliseconds of one timed step.
+
+--dump-outputs DIR writes DIR/mfcc.npy (float32 [rows, n_mfcc, T]) and, for the workloads with the
+modulation spectrum, DIR/modspec.npy (float32 [rows, n_mfcc, n_mod/2+1, 2]: real, imaginary) of the
+last timed step on rank 0: every row of the batch when that fits DUMP_BYTES_MAX, otherwise a fixed
+sample of rows drawn with DUMP_ROW_SEED (the result line names them under `dump`).
+
+--full adds everything else, as sections of the same run (--no-cpu / --no-check / --no-extra drop
+single ones of them):
   roofline     -- the dominant kernel of the timed region (fused frame+window+rFFT+power+mel+log),
                   algorithmic bytes / average launch duration from HIP events on the launch stream;
   rfft_stage   -- the stage-isolated batched rFFT kernel (the "% HBM roofline (rFFT)" figure),
@@ -23,7 +35,10 @@ Prints one JSON line (rank 0) with `value` = whole-job frames/s, plus
                   gathered trajectories), each with the root's and the other ranks' compute / gather times;
   cpu_baseline -- the NumPy oracle (a port of the reference's librosa path) on the host cores,
                   bounded sample, rank 0 at N = 1 only.  It runs FIRST, before anything touches the
-                  GPU (its worker pool is forked from a process that has not initialised HIP).
+                  GPU (its worker pool is forked from a process that has not initialised HIP);
+  check, parity_ok -- the three oracle rows of every section's last timed step against the oracle
+                  (a failed check makes the run exit 3 after the line);
+  refdefault_call, next_rows -- see time_reference_call() and time_next_rows().
 """
 import argparse
 import json
@@ -183,7 +198,10 @@ def _check_one(args):
     return clip, m, (O.modspec(m) if with_mod else None)
 
 
-def oracle_check_vectors(jobs, seeds=(90001, 90002, 90003)):
+CHECK_SEEDS = (90001, 90002, 90003)
+
+
+def oracle_check_vectors(jobs, seeds=CHECK_SEEDS):
     """jobs: {name: (cfg kwargs, n_samples, with_modspec)} -> {name: [(clip, oracle MFCC, oracle spectrum or None) x 3]}.
     Three clips of the run's signal model per workload with their oracle answers, computed in forked workers BEFORE
     this process touches HIP -- the oracle as the checker of the timed output, never on its path.  The bench writes the
@@ -216,16 +234,38 @@ def compare_rows(np, out_mfcc, out_mod, rows, vec):
 EVENT_EVERY = 4      # dominant-kernel HIP events on every 4th timed step
 
 
-def time_steps(torch, plan, fn, steps, warmup, stages, sync=None):
+def settle(torch, fn, seconds, chunk=8):
+    """Untimed calls of fn, `chunk` at a time with a synchronize after each chunk (the host must not queue far more GPU work
+    than the wall-clock budget), until `seconds` have passed.  Returns the number of calls."""
+    calls = 0
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < seconds:
+        for _ in range(chunk):
+            fn()
+        torch.cuda.synchronize()
+        calls += chunk
+    return calls
+
+
+def time_steps(torch, plan, fn, steps, warmup, stages, sync=None, events=True):
     """warmup untimed + `steps` timed calls of fn; HIP events around `stages` only inside the timed region --
     and only on every EVENT_EVERY-th step there (an event pair costs the stream two barrier packets, ~6 us each:
     rocprofv3 shows them as gaps on both sides of the kernel) -- the other stages from a short pass afterwards.
+    events=False: no events and no pass afterwards (a plain run: the timed steps alone).
     Returns (seconds, {stage: (ms_sum, launches)})."""
     for _ in range(warmup):
         fn()
     if sync:
         sync()
     torch.cuda.synchronize()
+    if not events:
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        if sync:
+            sync()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, {}
     every = max(1, min(EVENT_EVERY, steps // 5))
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -457,6 +497,35 @@ def roofline_of(cfg, B, T, n_mod, with_mod, per_stage, fused_dct, traffic_key=No
     return out
 
 
+DUMP_BYTES_MAX = 48 << 20       # --dump-outputs: bytes of all arrays together, at most
+DUMP_ROW_SEED = 1234
+
+
+def dump_outputs(torch, outdir, arrays, R):
+    """arrays: {name: device tensor [R, ...], float32 or complex64} -> outdir/<name>.npy, float32 (complex: a trailing axis
+    of 2, real and imaginary part).  Every row when all arrays fit DUMP_BYTES_MAX together, otherwise the same fixed sample
+    of rows of each: the first k of numpy.random.RandomState(DUMP_ROW_SEED).permutation(R), in ascending order."""
+    import numpy as np
+    per_row = sum(t[0].numel() * t.element_size() for t in arrays.values())
+    idx = None
+    if R * per_row > DUMP_BYTES_MAX:
+        k = max(1, DUMP_BYTES_MAX // per_row)
+        idx = np.sort(np.random.RandomState(DUMP_ROW_SEED).permutation(R)[:k])
+    os.makedirs(outdir, exist_ok=True)
+    files = {}
+    for name, t in arrays.items():
+        if idx is not None:
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        if t.is_complex():
+            t = torch.view_as_real(t)
+        x = t.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(outdir, name + ".npy"), x)
+        files[name + ".npy"] = list(x.shape)
+    rows = "all" if idx is None else {"count": int(len(idx)), "of": R, "seed": DUMP_ROW_SEED,
+                                      "rule": "first count of numpy.random.RandomState(seed).permutation(of), sorted"}
+    return {"rows": rows, "files": files}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -464,18 +533,27 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
     ap.add_argument("--clips", type=int, default=0, help="override clips per GPU (debug)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-check", action="store_true", help="skip the oracle spot-check of three output clips")
-    ap.add_argument("--no-extra", action="store_true", help="skip the c2 / c4 / rFFT-stage passes (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the oracle checks, the per-kernel / roofline figures, the other sections "
+                         "(c2 / c4 / refdefault / rFFT stage / rows around the hot path) and, N > 1, the other gather variant")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy, float32")
+    ap.add_argument("--settle-ms", type=float, default=300.0,
+                    help="untimed steps for this long before the warm-up steps (clocks out of their idle state)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-check", action="store_true",
+                    help="--full without the oracle spot-check of three output clips (and, in any run, without those clips "
+                         "in the batch)")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the c2 / c4 / rFFT-stage passes (profiling runs)")
     ap.add_argument("--generic", action="store_true", help="force the generic kernels")
     ap.add_argument("--no-fuse-tail", action="store_true", help="separate launches for the clamp fix-up and the trajectory rFFT (development A/B)")
     ap.add_argument("--variant", default=None, help="pin a fused-kernel variant (m12, w16s, w16, w8, wpf): development A/B")
     ap.add_argument("--gather", default="full", choices=["mfcc", "full"],
                     help="N > 1: 'full' (default, the literal north star) -- every rank computes MFCC + modulation spectrum of "
                          "its clips in its one fused launch and both arrays travel in the ONE gather; 'mfcc' -- only the MFCC "
-                         "slab travels (half the bytes over xGMI) and the root transforms the gathered trajectories.  BOTH are "
-                         "timed with the same number of steps and reported side by side (value_literal, value_mfcc_only); "
-                         "`value` is the one named here")
+                         "slab travels (half the bytes over xGMI) and the root transforms the gathered trajectories.  `value` is "
+                         "the one named here; with --full BOTH are timed with the same number of steps and reported side "
+                         "by side (value_literal, value_mfcc_only)")
     a = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -502,10 +580,16 @@ def main():
     if a.clips:
         B = a.clips
     cpu = None
-    if world == 1 and rank == 0 and not a.no_cpu:
+    if a.full and world == 1 and rank == 0 and not a.no_cpu:
         cpu = cpu_baseline(kw, int(secs * kw["sr"]), with_mod)      # no torch / HIP yet in this process
     check_vecs = {}
-    if rank == 0 and not a.no_check:
+    if rank == 0 and not a.no_check and not a.full:
+        # the oracle's three clips without the oracle's answers: the batch is the one a --full run times
+        sys.path.insert(0, os.path.join(ROOT, "oracle"))
+        import mfcc_oracle as O
+        n_ = int(secs * kw["sr"])
+        check_vecs = {a.workload: [(O.synth_clip(sd, n_, kw["sr"], "am"), None, None) for sd in CHECK_SEEDS]}
+    elif rank == 0 and not a.no_check:
         jobs = {a.workload: (kw, int(secs * kw["sr"]), with_mod)}
         if world == 1 and not a.no_extra:
             for nm in ("c2", "c4", "refdefault"):
@@ -571,7 +655,7 @@ def main():
         mod_on_root = use_dist and with_mod and gather_mode == "mfcc"
         lay = SlabLayout.make(cfg, R, n, with_mod and not mod_on_root)
         pg = PipelinedGather(lay.numel, dev) if use_dist else None
-        if pg:
+        if pg and a.full:
             pg.time_every(EVENT_EVERY)
         last = {}
         slab1 = torch.empty(lay.numel, dtype=torch.float32, device=dev) if not use_dist else None
@@ -583,15 +667,19 @@ def main():
         def root_modspec(i):        # runs inside the gather's side stream, root only
             got = pg.recv_block[i][:, :lay.mfcc_numel].reshape(world * R, cfg.n_mfcc, T)
             plan.modspec(got, out=mod_all[i])
+            last["mod_root"] = mod_all[i][:R]           # rank 0's rows come first in the gathered block
 
-        def step():
-            slab = pg.acquire() if pg else slab1
+        def compute(slab):
             mfcc_out, mod_out = lay.views(slab)
-            last["mfcc"], last["mod"] = mfcc_out, mod_out
             if with_mod and not mod_on_root:
                 plan.mfcc_modspec(rows, out=mfcc_out, out_mod=mod_out)    # one launch where the plan can (fused tail)
             else:
                 plan.mfcc(rows, out=mfcc_out)
+            return mfcc_out, mod_out
+
+        def step():
+            slab = pg.acquire() if pg else slab1
+            last["mfcc"], last["mod"] = compute(slab)
             if pg:
                 pg.submit(post=root_modspec if mod_on_root else None)
 
@@ -601,19 +689,25 @@ def main():
             if use_dist:
                 dist.barrier()
 
+        # the kernels of the step without its gather (no collective: the ranks may settle for different numbers of calls),
+        # into a slab no gather has used yet
+        settle_slab = pg.slabs[0] if pg else slab1
+        settled = settle(torch, lambda: compute(settle_slab), a.settle_ms * 1e-3)
         if pg:
             for _ in range(warmup):
                 step()
             drain()
             pg.gather_ms()              # discard the warm-up gathers' events (communicator set-up is in the first one)
-            dt, stage = time_steps(torch, plan, step, steps, 0, ["logmel"], sync=drain)
+            dt, stage = time_steps(torch, plan, step, steps, 0, ["logmel"], sync=drain, events=a.full)
         else:
-            dt, stage = time_steps(torch, plan, step, steps, warmup, ["logmel"], sync=drain)
+            dt, stage = time_steps(torch, plan, step, steps, warmup, ["logmel"], sync=drain, events=a.full)
+        last["settle_calls"] = settled
         per_rank = None
         if use_dist:
             tt = torch.tensor([dt], dtype=torch.float64, device=dev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
+        if use_dist and a.full:
             # per rank: device time of the step's kernels (HIP events, every EVENT_EVERY-th step) and of its gather as
             # the side stream saw it -- what separates "compute" from "wire" in the scaling curve
             g_ms, g_n = pg.gather_ms()
@@ -742,12 +836,19 @@ def main():
                 ex["refdefault"]["vs_c2_per_frame_mel"] = ex["refdefault"]["ns_per_frame_mel"] / ex["c2"]["ns_per_frame_mel"]
         return ex
 
-    extras = run_extras() if not a.no_extra else {}
+    extras = run_extras() if a.full and not a.no_extra else {}
     dt, stage, mod_on_root, last, per_rank, lay = run_variant(a.gather, a.steps, a.warmup)
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        outs = {"mfcc": last["mfcc"]}
+        mod_ = last["mod"] if last["mod"] is not None else last.get("mod_root")
+        if mod_ is not None:
+            outs["modspec"] = mod_
+        dumped = dump_outputs(torch, a.dump_outputs, outs, R)
     # ---- spot-check of the TIMED output against the oracle, outside the timed region: the three rows that carry the
     # oracle's clips, MFCC (north-star bound: 1e-4 of max|MFCC|) and modulation spectrum ----
     check = None
-    if check_vec is not None and rank == 0:
+    if a.full and check_vec is not None and rank == 0:
         import numpy as np
         check = compare_rows(np, last["mfcc"], last["mod"], check_rows, check_vec)
     frames_total = world * R * T * a.steps
@@ -764,9 +865,12 @@ def main():
                    "rccl_ranks": (dist.get_world_size() if use_dist else None),
                    "gather_bytes_per_rank": (lay.numel * 4 if use_dist else None),
                    "csrc_sha16": csrc_sha16(),
-                   "hsa_ipc_mode_legacy": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY")},
+                   "hsa_ipc_mode_legacy": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY"),
+                   "settle_ms": a.settle_ms, "settle_calls": last["settle_calls"], "full": a.full},
     }
-    if use_dist and with_mod:
+    if dumped is not None:
+        res["dump"] = dumped
+    if a.full and use_dist and with_mod:
         # the other gather variant, SAME steps and warm-up, reported as a top-level peer of `value`
         other = "full" if a.gather == "mfcc" else "mfcc"
         dt2, _, _, _, per_rank2, lay2 = run_variant(other, a.steps, a.warmup)
@@ -792,17 +896,20 @@ def main():
 
     parity_failed, all_checks = False, {}
     if rank == 0:
+        ftail = bool(with_mod and not mod_on_root and plan.fused_tail(R, n))
+        res["config"]["fused_tail"] = ftail
+        if ftail:
+            res["config"]["launches_per_step"] = 1
+    if rank == 0 and a.full:
         # ---- roofline of the dominant kernel, from HIP events recorded around every launch -----
         # the n_fft 512 tile kernels also apply the (unclamped) DCT: their launch stores the MFCC rows too
         fused = plan.fused_dct
         per_stage = {k: {"avg_ms": v[0] / v[1], "launches": v[1]} for k, v in stage.items()}
         res["kernels_ms"] = {k: round(v["avg_ms"], 4) for k, v in per_stage.items()}
         key = {"radix16-w16s": s16_kernel_key(cfg, 1), "radix16-m12": "logmel12m", "radix16-wpf": "logmel_wpf"}.get(plan.kernel_path)
-        ftail = bool(with_mod and not mod_on_root and plan.fused_tail(R, n))
         if ftail:
             key = s16_kernel_key(cfg, 2)        # the clip-mode instantiation
         res["config"]["launches_per_step"] = 1 if ftail else (len(per_stage) if per_stage else None)
-        res["config"]["fused_tail"] = ftail
         rl = roofline_of(cfg, R, T, n_mod, with_mod, per_stage, fused, key, fused_tail=ftail)
         if rl:
             res["roofline"] = rl
@@ -832,6 +939,7 @@ def main():
         parity_failed = res["parity_ok"] is False
         if cpu is not None:
             res["cpu_baseline"] = cpu
+    if rank == 0:
         sys.stdout.flush()
         os.dup2(real_stdout, 1)
         print(json.dumps(res), flush=True)

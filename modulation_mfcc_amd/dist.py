@@ -11,7 +11,7 @@ float32 slab per rank, so that a single collective moves both.  ``modspec_on_roo
 spectrum is a fixed linear map (zero-padded rFFT) of the MFCC trajectories, i.e. redundancy on the wire -- as many bytes
 again as the MFCCs themselves over point-to-point xGMI links: only the MFCC slab is gathered and the root runs the
 trajectory rFFT over the gathered [B_total, n_mfcc, T] block (one launch, ~0.3 ms for 8192 clips) -- half the bytes, at
-the price of extra work on the root.  bench.py times both with equal steps and reports them side by side.
+the price of extra work on the root.  ``bench.py --full`` times both with equal steps and reports them side by side.
 """
 from __future__ import annotations
 

@@ -371,3 +371,33 @@ def test_bench_names_the_kernel_instantiation_of_a_workload():
     for hop, nr in ((56, 1), (57, 2), (121, 2), (122, 3), (186, 3), (187, 4), (252, 4)):
         assert bench.s16_kernel_key(MfccConfig(**dict(bench.WORKLOADS["c3"][4], hop_length=hop)), 1) == f"logmel512s_kernel<1, {nr},"
     assert bench.s16_kernel_key(MfccConfig(**dict(bench.WORKLOADS["refdefault"][4], preemph=0.97)), 1) == "logmel512s_kernel<1, 3,"
+
+
+def test_bench_dump_outputs_format_and_bound(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files, complex spectra as a trailing (real, imaginary) axis, at most
+    DUMP_BYTES_MAX in all; a batch too large for that gives the same fixed sample of rows in every file and every run."""
+    import os
+    import sys
+    import torch
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    g = torch.Generator().manual_seed(5)
+    R, K, T, F = 1024, 13, 1001, 513                         # the headline batch's output shapes
+    m = torch.randn((R, K, T), generator=g)
+    z = torch.complex(torch.randn((R, K, F), generator=g), torch.randn((R, K, F), generator=g))
+    info = bench.dump_outputs(torch, str(tmp_path / "a"), {"mfcc": m, "modspec": z}, R)
+    a = np.load(tmp_path / "a" / "mfcc.npy")
+    s = np.load(tmp_path / "a" / "modspec.npy")
+    assert a.dtype == np.float32 and s.dtype == np.float32
+    assert a.nbytes + s.nbytes <= bench.DUMP_BYTES_MAX <= 64 * 10 ** 6
+    k = info["rows"]["count"]
+    assert 0 < k < R and a.shape == (k, K, T) and s.shape == (k, K, F, 2)
+    idx = np.sort(np.random.RandomState(bench.DUMP_ROW_SEED).permutation(R)[:k])
+    np.testing.assert_array_equal(a, m.numpy()[idx])
+    np.testing.assert_array_equal(s[..., 0], z.real.numpy()[idx])
+    np.testing.assert_array_equal(s[..., 1], z.imag.numpy()[idx])
+    assert bench.dump_outputs(torch, str(tmp_path / "b"), {"mfcc": m, "modspec": z}, R) == info
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "mfcc.npy"), a)
+    small = bench.dump_outputs(torch, str(tmp_path / "c"), {"mfcc": m[:8]}, 8)       # fits: every row
+    assert small["rows"] == "all"
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "mfcc.npy"), m[:8].numpy())

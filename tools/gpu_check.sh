@@ -10,11 +10,11 @@ timeout -k 10 900 python -m pytest tests -m gpu -q "$@" > $out/${tag}_tests.log 
 rc=$?
 tail -5 $out/${tag}_tests.log
 if [ $rc -ge 124 ]; then echo "tests killed ($rc)"; exit $rc; fi
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 rb=$?
 if [ $rb -ge 124 ]; then echo "bench killed ($rb)"; exit $rb; fi
 if [ $rb -ne 0 ]; then tail -20 $out/${tag}_bench.err; fi
-MM_BENCH_FORCE_DIST=1 timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-cpu --no-extra > $out/${tag}_dist.json 2> $out/${tag}_dist.err
+MM_BENCH_FORCE_DIST=1 timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --no-cpu --no-extra > $out/${tag}_dist.json 2> $out/${tag}_dist.err
 rd=$?
 if [ $rd -ne 0 ]; then tail -20 $out/${tag}_dist.err; fi
 python - <<PY

@@ -4,7 +4,7 @@ tag=$1; ctrs=$2; shift 2
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d $out -- python3 bench.py --steps 3 --warmup 1 --no-cpu "$@" > $out/bench.json 2> $out/log.txt || { tail -5 $out/log.txt; exit 1; }
+rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d $out -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu "$@" > $out/bench.json 2> $out/log.txt || { tail -5 $out/log.txt; exit 1; }
 python3 - $out <<'PY'
 import csv, glob, sys, collections
 f = glob.glob(sys.argv[1] + "/*/*_counter_collection.csv")[0]
