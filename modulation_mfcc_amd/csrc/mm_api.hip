@@ -386,7 +386,7 @@ int mm_plan_create(const mm_config* cfg, mm_plan** out) {
   p->d_window = nullptr; p->d_tw = nullptr; p->d_mel_start = p->d_mel_len = p->d_mel_off = nullptr;
   p->d_mel_w = nullptr; p->d_dct_t = nullptr;
   p->d_sw_tab = nullptr; p->d_sw_part = nullptr;
-  p->d_w16_tab = p->d_lane_tab = nullptr; p->d_w16_part = nullptr; p->w16_ok = 0; p->s16_nr = 0; p->s16_lds_bytes = 0;
+  p->d_w16_tab = p->d_lane_tab = nullptr; p->d_w16_part = nullptr; p->w16_ok = 0; p->s16_nr = 0; p->s16_xa = 0; p->s16_lds_bytes = 0;
 
   p->d_k2_lane_tab = p->d_k2_mel_lane = nullptr; p->k2_ok = 0; p->d_window_e = nullptr; p->embed = 1;
   p->d_rf2k_lane_tab = nullptr; p->rf2k_ok = 0;
@@ -615,16 +615,19 @@ int mm_plan_create(const mm_config* cfg, mm_plan** out) {
           p->h16_ok = 1;
       }
       // staged-sample variant (mm_logmel16s.hip.inc): the tile's 63*hop + 512 samples must fit NR*4096 floats
-      p->s16_nr = 0;
+      p->s16_nr = 0; p->s16_xa = 0;
       if (p->w16_ok) {
         const int span = 63 * cfg->hop_length + 512;
         // 16-byte staging groups per thread: the fewest that hold the tile's samples (1 / 2 for short hops -- without
         // pre-emphasis only: those instantiations do not exist -- leave LDS for the log-mel tile of a 128-filter bank)
         int nr = span <= 4096 ? 1 : span <= 2 * 4096 ? 2 : span <= 3 * 4096 ? 3 : (span <= 4 * 4096 ? 4 : 0);
         if (nr && nr < 3 && cfg->preemph != 0.0f) nr = 3;
-        const size_t lds = nr ? (size_t)MM_S16_TAB_OFF(nr) + tab16.size() * 4 : 0;
+        // the addtid exchange (NR 3 / 4) costs 2 KB of LDS: taken where the tables still fit beside it (and, below, where
+        // the fused-DCT layout the plan has without it still fits)
+        const bool xa = nr >= 3 && (size_t)MM_S16_TAB_OFF(nr, true) + tab16.size() * 4 <= MM_LM_LDS_MAX;
+        const size_t lds = nr ? (size_t)MM_S16_TAB_OFF(nr, xa) + tab16.size() * 4 : 0;
         const bool ok = nr && lds <= MM_LM_LDS_MAX && set_s16_attr(MM_LM_LDS_MAX);
-        if (ok) { p->s16_nr = nr; p->s16_lds_bytes = lds; }
+        if (ok) { p->s16_nr = nr; p->s16_xa = xa ? 1 : 0; p->s16_lds_bytes = lds; }
       }
       // staged-sample variant with the DCT fused in.  Two layouts of the log-mel tile Lt[filter][frame]:
       //   double buffered (up to ~64 filters): parts 3 / 7 / 11 / 15 of a weighted partition are half size and their waves
@@ -651,8 +654,12 @@ int mm_plan_create(const mm_config* cfg, mm_plan** out) {
           while (last > 0 && empty[last]) --last;
           nk = last / 4 + 1;
         }
-        for (int layout = 0; layout < 2 && !p->s16f_ok; ++layout) {
-          const bool single = layout == 1;
+        // layouts: double Lt tile with (0) / without (1) the addtid exchange, then single (2 / 3): the addtid exchange never
+        // costs a plan its double tile or its fused DCT
+        for (int layout = 0; layout < 4 && !p->s16f_ok; ++layout) {
+          const bool single = layout >= 2;
+          const bool xa = p->s16_xa && (layout & 1) == 0;
+          if ((layout & 1) && !p->s16_xa) continue;
           const double wts_d[16] = {1, 1, 1, MM_S16F_W, 1, 1, 1, MM_S16F_W, 1, 1, 1, MM_S16F_W, 1, 1, 1, MM_S16F_W};
           double extra[16];
           for (int w = 0; w < 16; ++w) extra[w] = (!single && wts_d[w] < 1.0) ? 700.0 : 0.0;     // cost model units: instructions
@@ -697,7 +704,7 @@ int mm_plan_create(const mm_config* cfg, mm_plan** out) {
             for (int m = 0; m < cfg->n_mels; ++m) if (empty[m]) bits[m >> 5] |= 1u << (m & 31);
             std::memcpy(&dcta[(size_t)kbn * nk * 64 + (size_t)kbn * 16], bits, sizeof(bits));
           }
-          const size_t tab_end = (size_t)MM_S16_TAB_OFF(p->s16_nr) + tabf.size() * 4;
+          const size_t tab_end = (size_t)MM_S16_TAB_OFF(p->s16_nr, xa) + tabf.size() * 4;
           p->s16f_lt_off = (unsigned)align_up(tab_end, 16);
           p->s16f_dcta_off = p->s16f_lt_off + (single ? 1u : 2u) * (unsigned)lt_rows * 320u;
           p->s16f_red_off = (unsigned)align_up((size_t)p->s16f_dcta_off + dcta.size() * 4, 16);
@@ -710,6 +717,10 @@ int mm_plan_create(const mm_config* cfg, mm_plan** out) {
             p->s16f_lt_rows = lt_rows; p->s16f_nk = nk; p->s16f_kb = kbn; p->s16f_roles = roles;
             p->s16f_flags = (single ? MM_S16F_SINGLE : 0) | (skip ? MM_S16F_SKIP : 0);
             p->s16f_ok = 1;
+            if (!xa && p->s16_xa) {      // the unfused launches follow the fused layout's exchange
+              p->s16_xa = 0;
+              p->s16_lds_bytes = (size_t)MM_S16_TAB_OFF(p->s16_nr, false) + tab16.size() * 4;
+            }
           }
           break;
         }
@@ -1294,7 +1305,7 @@ static int launch_stft(mm_plan* p, int mode, const float* d_audio, int64_t batch
             mode = 2;
           }
         }
-        launch_s16(mode, p->s16_nr, pre, odd, unal, dim3((unsigned)grid), lds, st, q);
+        launch_s16(mode, p->s16_nr, p->s16_xa != 0, pre, odd, unal, dim3((unsigned)grid), lds, st, q);
         HIP_TRY(hipGetLastError());
         return MM_OK;
       }

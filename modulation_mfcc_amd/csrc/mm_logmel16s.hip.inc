@@ -1,5 +1,5 @@
 #pragma once
-// (included by mm_logmel16s.hip, its own translation unit: 72 instantiations)
+// (included by mm_logmel16s.hip, its own translation unit: 120 instantiations)
 // logmel512s_kernel<MODE, NR>: the 16-wave fused n_fft = 512 kernel of mm_logmel16w.hip.inc with the
 // tile's samples STAGED through LDS.  Measured on the direct-load variant (compile-time ablations, s_memtime
 // stamps in tools/stamps.py): its 16 x 8-byte global loads per item -- every sample is fetched
@@ -13,14 +13,15 @@
 //   * phase A reads its 16 complex points per lane from S with 16 x ds_read_b64 (one address
 //     register, immediate offsets): no clamping, no edge masks, no 64-bit address arithmetic;
 //   * the 16x16 exchange between the DFT-16 stages no longer has its own 80 KB: it runs inside the
-//     wave's OWN four power rows of P (they are written only after the exchange), 4 x 256 floats with
-//     an XOR swizzle on the 16-byte chunk index instead of row padding (b128 reads conflict-free).
+//     wave's OWN four power rows of P (they are written only after the exchange); NR 3 / 4: one
+//     ds_write_addtid_b32 per register (2 LDS cycles, a ds_write_b32 costs 4), 64-float blocks at
+//     mm_s16_xb offsets that keep the b128 reads conflict-free.
 //
 // Requirements (checked by launch_stft, which otherwise falls back to the direct-load kernel, or to the
 // generic one for odd hops / pre-emphasis, which only this kernel of the n_fft = 512 family handles):
 // n_samples >= 4, 63*hop + 512 <= NR*4096 (16-byte aligned rows and n_samples % 4 == 0 take the plain
 // instantiation, anything else UNAL).
-// LDS: P 66,560 | S NR*16,384 | lane records 5,376 | mel run table.
+// LDS: P 68,608 (NR 3 / 4, pitch 268) or 66,560 (NR 1 / 2) | S NR*16,384 | lane records 5,376 | mel run table.
 // PRE: pre-emphasis y[n] - a*y[n-1] (y[-1] := 0; the optional extension of this build, float32)
 // applied while the samples are staged -- one extra 4-byte load per 16-byte group for y[s0 - 1].
 // ODD: odd hop (odd frames start at 4-byte aligned samples only: two b32 LDS reads per point).
@@ -448,22 +449,63 @@ __device__ __attribute__((noinline)) void s16_finalize_all(S16Fin f, int c0, int
   else s16_fin_modspec<1>(f, c0, n_clips, wave, lane, (MM_LDS float*)lds, tab);
 }
 
-template <int MODE, int NR, bool PRE, bool ODD, bool UNAL>
+// One half (re or im) of the 16x16 exchange: v[k1] of every lane to the wave's area at mm_s16_xb(k1) + lane, sixteen
+// ds_write_addtid_b32 (address M0[15:0] + offset + 4 lane; m0v = the area's LDS byte address, below 64 KB: mm_s16.h).
+// M0 is reserved by the compiler and not preserved around inline assembly: saved, set and restored inside the
+// statement; the s_nop is the wait state an SALU write of M0 needs before an add-TID LDS instruction.  The LDS
+// operations of one wave execute in order: the reads behind the caller's wave_lds_sync() see these stores, and nothing
+// here returns data the compiler would have to count.
+__device__ __forceinline__ void s16_ex_store(unsigned m0v, const float (&v)[16]) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %1\n\t"
+      "s_nop 0\n\t"
+      "ds_write_addtid_b32 %3 offset:%c19\n\t"
+      "ds_write_addtid_b32 %4 offset:%c20\n\t"
+      "ds_write_addtid_b32 %5 offset:%c21\n\t"
+      "ds_write_addtid_b32 %6 offset:%c22\n\t"
+      "ds_write_addtid_b32 %7 offset:%c23\n\t"
+      "ds_write_addtid_b32 %8 offset:%c24\n\t"
+      "ds_write_addtid_b32 %9 offset:%c25\n\t"
+      "ds_write_addtid_b32 %10 offset:%c26\n\t"
+      "ds_write_addtid_b32 %11 offset:%c27\n\t"
+      "ds_write_addtid_b32 %12 offset:%c28\n\t"
+      "ds_write_addtid_b32 %13 offset:%c29\n\t"
+      "ds_write_addtid_b32 %14 offset:%c30\n\t"
+      "ds_write_addtid_b32 %15 offset:%c31\n\t"
+      "ds_write_addtid_b32 %16 offset:%c32\n\t"
+      "ds_write_addtid_b32 %17 offset:%c33\n\t"
+      "ds_write_addtid_b32 %18 offset:%c34\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "s"(m0v), "i"(0),
+        "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]), "v"(v[8]),
+        "v"(v[9]), "v"(v[10]), "v"(v[11]), "v"(v[12]), "v"(v[13]), "v"(v[14]), "v"(v[15]),
+        "i"(4 * mm_s16_xb(0)), "i"(4 * mm_s16_xb(1)), "i"(4 * mm_s16_xb(2)), "i"(4 * mm_s16_xb(3)),
+        "i"(4 * mm_s16_xb(4)), "i"(4 * mm_s16_xb(5)), "i"(4 * mm_s16_xb(6)), "i"(4 * mm_s16_xb(7)),
+        "i"(4 * mm_s16_xb(8)), "i"(4 * mm_s16_xb(9)), "i"(4 * mm_s16_xb(10)), "i"(4 * mm_s16_xb(11)),
+        "i"(4 * mm_s16_xb(12)), "i"(4 * mm_s16_xb(13)), "i"(4 * mm_s16_xb(14)), "i"(4 * mm_s16_xb(15))
+      : "memory");
+}
+
+template <int MODE, int NR, bool PRE, bool ODD, bool UNAL, bool XA>
 __global__ __launch_bounds__(1024) void logmel512s_kernel(Logmel512Params p) {
+  static_assert(!XA || NR >= 3, "the addtid exchange exists for NR 3 / 4 only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* P = reinterpret_cast<float*>(smem);
-  float* S = reinterpret_cast<float*>(smem + MM_S16_S_OFF);
+  float* S = reinterpret_cast<float*>(smem + MM_S16_S_OFF(XA));
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int q = lane & 15, row = lane >> 4;
-  const float* lt = reinterpret_cast<const float*>(smem + MM_S16_LT_OFF(NR)) + q * MM_W16_LT_PITCH;
+  const float* lt = reinterpret_cast<const float*>(smem + MM_S16_LT_OFF(NR, XA)) + q * MM_W16_LT_PITCH;
 
   for (int i = threadIdx.x; i < 16 * MM_W16_LT_PITCH; i += 1024)
-    reinterpret_cast<float*>(smem + MM_S16_LT_OFF(NR))[i] = p.lane_tab[i];
-  if (threadIdx.x < 64 * 3) P[(threadIdx.x / 3) * MM_LM_PITCH + 257 + threadIdx.x % 3] = 0.0f;
+    reinterpret_cast<float*>(smem + MM_S16_LT_OFF(NR, XA))[i] = p.lane_tab[i];
+  if (threadIdx.x < 64 * 3) P[(threadIdx.x / 3) * MM_S16_PITCH(XA) + 257 + threadIdx.x % 3] = 0.0f;
 
   for (int i = threadIdx.x; i < p.n_tab16; i += 1024)
-    reinterpret_cast<float4*>(smem + MM_S16_TAB_OFF(NR))[i] = p.mel_tab[i];
+    reinterpret_cast<float4*>(smem + MM_S16_TAB_OFF(NR, XA))[i] = p.mel_tab[i];
   const int run0 = p.wave_part[wave * 4 + 0], run1 = p.wave_part[wave * 4 + 1];
   const int m0 = p.wave_part[wave * 4 + 2];
   // Fused DCT (MODE 1, p.out_mfcc): phase B also leaves its log-mel values in an LDS tile Lt[m][frame]
@@ -575,18 +617,24 @@ __global__ __launch_bounds__(1024) void logmel512s_kernel(Logmel512Params p) {
   int b = tile_begin / tpc, tl = tile_begin - b * tpc;
   int nb = b, ntl = tl;
 
-  // exchange area = this wave's own four power rows; element (k1, n2) of frame `row` lives at
-  // row*256 + k1*16 + (n2 ^ 4*((k1 >> 2) & 3)): lane q writes column n2 = q, reads row k1 = q
-  float* exw = P + 4 * wave * MM_LM_PITCH + row * 256;
+  // exchange area = this wave's own four power rows.  XA (1068 of the rows' 1072 floats): register
+  // k1 of the 64 lanes goes out as ONE ds_write_addtid_b32 (lane l at mm_s16_xb(k1) + l: no address VGPR, 2 LDS cycles
+  // where a ds_write_b32 costs 4), so element (k1, n2) of frame `row` lives at mm_s16_xb(k1) + 16 row + n2: lane q
+  // writes column n2 = q of every k1 and reads block k1 = q of its frame as four b128 (conflict-free: mm_s16.h).
+  // NR 1 / 2: element (k1, n2) of frame `row` at row*256 + k1*16 + (n2 ^ 4*((k1 >> 2) & 3)), ds_write_b32 per element.
+  constexpr bool addtid = XA;
+  float* exw = P + 4 * wave * MM_S16_PITCH(XA) + (addtid ? mm_s16_xb(q) + 16 * row : row * 256);
+  const unsigned exm0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(MM_LDS float*)(P + 4 * wave * MM_S16_PITCH(XA)));
   float* wq0 = exw + (q ^ 0);
   float* wq1 = exw + (q ^ 4);
   float* wq2 = exw + (q ^ 8);
   float* wq3 = exw + (q ^ 12);
-  const int sq = (q >> 2) & 3;
-  const float4* rq0 = reinterpret_cast<const float4*>(exw + q * 16 + 4 * (0 ^ sq));
-  const float4* rq1 = reinterpret_cast<const float4*>(exw + q * 16 + 4 * (1 ^ sq));
-  const float4* rq2 = reinterpret_cast<const float4*>(exw + q * 16 + 4 * (2 ^ sq));
-  const float4* rq3 = reinterpret_cast<const float4*>(exw + q * 16 + 4 * (3 ^ sq));
+  const int sq = addtid ? 0 : (q >> 2) & 3;
+  const int rq = addtid ? 0 : q * 16;
+  const float4* rq0 = reinterpret_cast<const float4*>(exw + rq + 4 * (0 ^ sq));
+  const float4* rq1 = reinterpret_cast<const float4*>(exw + rq + 4 * (1 ^ sq));
+  const float4* rq2 = reinterpret_cast<const float4*>(exw + rq + 4 * (2 ^ sq));
+  const float4* rq3 = reinterpret_cast<const float4*>(exw + rq + 4 * (3 ^ sq));
   // this lane's 16 points of its frame: S[(4*wave + row)*hop + 2q + 32*n1]
   const float* sxf = S + (4 * wave + row) * p.hop + 2 * q;
   const float2* sx = reinterpret_cast<const float2*>(sxf);
@@ -765,8 +813,17 @@ __global__ __launch_bounds__(1024) void logmel512s_kernel(Logmel512Params p) {
     {
 #define MM_S16_WR(k1, val)                                                                         \
   (((k1) >> 2) == 0 ? wq0 : ((k1) >> 2) == 1 ? wq1 : ((k1) >> 2) == 2 ? wq2 : wq3)[(k1) * 16] = (val)
+      {
+        float re[16];
 #pragma unroll
-      for (int k1 = 0; k1 < 16; ++k1) MM_S16_WR(k1, x[f16::P16(k1)].x);
+        for (int k1 = 0; k1 < 16; ++k1) re[k1] = x[f16::P16(k1)].x;
+        if constexpr (addtid) {
+          s16_ex_store(exm0, re);
+        } else {
+#pragma unroll
+          for (int k1 = 0; k1 < 16; ++k1) MM_S16_WR(k1, re[k1]);
+        }
+      }
       wave_lds_sync();
       {
         const float4 v0 = *rq0, v1 = *rq1, v2 = *rq2, v3 = *rq3;
@@ -779,8 +836,12 @@ __global__ __launch_bounds__(1024) void logmel512s_kernel(Logmel512Params p) {
       float im[16];
 #pragma unroll
       for (int k1 = 0; k1 < 16; ++k1) im[k1] = x[f16::P16(k1)].y;
+      if constexpr (addtid) {
+        s16_ex_store(exm0, im);
+      } else {
 #pragma unroll
-      for (int k1 = 0; k1 < 16; ++k1) MM_S16_WR(k1, im[k1]);
+        for (int k1 = 0; k1 < 16; ++k1) MM_S16_WR(k1, im[k1]);
+      }
       wave_lds_sync();
       {
         const float4 v0 = *rq0, v1 = *rq1, v2 = *rq2, v3 = *rq3;
@@ -810,7 +871,7 @@ __global__ __launch_bounds__(1024) void logmel512s_kernel(Logmel512Params p) {
         }
       }
 #endif
-      float* pr = P + (4 * wave + row) * MM_LM_PITCH;
+      float* pr = P + (4 * wave + row) * MM_S16_PITCH(XA);
       // every lane of the frame has finished reading the exchange area (in-order LDS, one wave)
       // before any of its power values is written over it
       float pw[17];
@@ -857,15 +918,15 @@ __global__ __launch_bounds__(1024) void logmel512s_kernel(Logmel512Params p) {
       for (int r = wave; r < 64; r += 16) {
         if (t0 + r < p.n_frames) {
           float* o = p.out_power + (((int64_t)b * p.n_frames) + t0 + r) * 257;
-          const float* src = P + r * MM_LM_PITCH;
+          const float* src = P + r * MM_S16_PITCH(XA);
           for (int k = lane; k < 257; k += 64) o[k] = src[k];
         }
       }
     } else {
       const bool valid = (t0 + lane) < p.n_frames;
       float* o = p.out_logmel + ((int64_t)b * p.n_mels + m0) * p.n_frames + t0 + lane;
-      const float* pl = P + lane * MM_LM_PITCH;
-      const float4* hdr = reinterpret_cast<const float4*>(smem + MM_S16_TAB_OFF(NR));
+      const float* pl = P + lane * MM_S16_PITCH(XA);
+      const float4* hdr = reinterpret_cast<const float4*>(smem + MM_S16_TAB_OFF(NR, XA));
       const float4* grp = hdr + p.n_runs;
       float carry = 0.0f;
       if (run0 < run1) {
@@ -950,11 +1011,11 @@ __global__ __launch_bounds__(1024) void logmel512s_kernel(Logmel512Params p) {
   MM_STAMP_END(16)
 }
 
-// ---- host side: the instantiations (MODE 0/1/2 x NR 3/4 x PRE x ODD x UNAL = 48; NR 1/2 -- short hops, e.g. the
-// reference's own 10 kHz default with hop 50: 14.6 KB of samples per tile instead of 48 KB of LDS -- without PRE: 24) ----
-template <int MODE, int NR>
+// ---- host side: the instantiations (MODE 0/1/2 x NR 3/4 x PRE x ODD x UNAL x XA = 96; NR 1/2 -- short hops, e.g. the
+// reference's own 10 kHz default with hop 50: 14.6 KB of samples per tile instead of 48 KB of LDS -- without PRE or XA: 24) ----
+template <int MODE, int NR, bool XA>
 static void launch_s16_mn(bool pre, bool odd, bool unal, dim3 grid, size_t lds, hipStream_t st, const Logmel512Params& q) {
-#define MM_S16_GO(PP, OO, UU) hipLaunchKernelGGL((logmel512s_kernel<MODE, NR, PP, OO, UU>), grid, dim3(1024), lds, st, q)
+#define MM_S16_GO(PP, OO, UU) hipLaunchKernelGGL((logmel512s_kernel<MODE, NR, PP, OO, UU, XA>), grid, dim3(1024), lds, st, q)
   if (NR < 3) {          // (plans with pre-emphasis never ask for NR 1 / 2: mm_plan_create)
     switch ((odd ? 2 : 0) | (unal ? 1 : 0)) {
       case 0: MM_S16_GO(false, false, false); break;
@@ -965,7 +1026,7 @@ static void launch_s16_mn(bool pre, bool odd, bool unal, dim3 grid, size_t lds, 
     return;
   }
   constexpr int NRP = NR < 3 ? 3 : NR;      // (keeps the PRE instantiations of NR 1 / 2 from being generated)
-#define MM_S16_GOP(OO, UU) hipLaunchKernelGGL((logmel512s_kernel<MODE, NRP, true, OO, UU>), grid, dim3(1024), lds, st, q)
+#define MM_S16_GOP(OO, UU) hipLaunchKernelGGL((logmel512s_kernel<MODE, NRP, true, OO, UU, XA>), grid, dim3(1024), lds, st, q)
   switch ((pre ? 4 : 0) | (odd ? 2 : 0) | (unal ? 1 : 0)) {
     case 0: MM_S16_GO(false, false, false); break;
     case 1: MM_S16_GO(false, false, true); break;
@@ -980,38 +1041,47 @@ static void launch_s16_mn(bool pre, bool odd, bool unal, dim3 grid, size_t lds, 
 #undef MM_S16_GO
 }
 
-template <int NR>
+template <int NR, bool XA>
 static void launch_s16_n(int mode, bool pre, bool odd, bool unal, dim3 grid, size_t lds, hipStream_t st, const Logmel512Params& q) {
-  if (mode == 0) launch_s16_mn<0, NR>(pre, odd, unal, grid, lds, st, q);
-  else if (mode == 1) launch_s16_mn<1, NR>(pre, odd, unal, grid, lds, st, q);
-  else launch_s16_mn<2, NR>(pre, odd, unal, grid, lds, st, q);
+  if (mode == 0) launch_s16_mn<0, NR, XA>(pre, odd, unal, grid, lds, st, q);
+  else if (mode == 1) launch_s16_mn<1, NR, XA>(pre, odd, unal, grid, lds, st, q);
+  else launch_s16_mn<2, NR, XA>(pre, odd, unal, grid, lds, st, q);
 }
 
-void launch_s16(int mode, int nr, bool pre, bool odd, bool unal, dim3 grid, size_t lds, hipStream_t st,
+void launch_s16(int mode, int nr, bool xa, bool pre, bool odd, bool unal, dim3 grid, size_t lds, hipStream_t st,
                 const Logmel512Params& q) {
   if (mode == 1 && q.out_mod != nullptr) mode = 2;        // clip mode (fused tail); 2 may also be asked for directly (n_mod 0)
   switch (nr) {
-    case 1: launch_s16_n<1>(mode, pre, odd, unal, grid, lds, st, q); break;
-    case 2: launch_s16_n<2>(mode, pre, odd, unal, grid, lds, st, q); break;
-    case 3: launch_s16_n<3>(mode, pre, odd, unal, grid, lds, st, q); break;
-    default: launch_s16_n<4>(mode, pre, odd, unal, grid, lds, st, q); break;
+    case 1: launch_s16_n<1, false>(mode, pre, odd, unal, grid, lds, st, q); break;
+    case 2: launch_s16_n<2, false>(mode, pre, odd, unal, grid, lds, st, q); break;
+    case 3:
+      if (xa) launch_s16_n<3, true>(mode, pre, odd, unal, grid, lds, st, q);
+      else launch_s16_n<3, false>(mode, pre, odd, unal, grid, lds, st, q);
+      break;
+    default:
+      if (xa) launch_s16_n<4, true>(mode, pre, odd, unal, grid, lds, st, q);
+      else launch_s16_n<4, false>(mode, pre, odd, unal, grid, lds, st, q);
+      break;
   }
 }
 
-template <int MODE, int NR>
+template <int MODE, int NR, bool XA>
 static bool set_s16_attr_mn(int bytes) {
-  const void* fn[8] = {(const void*)logmel512s_kernel<MODE, NR, false, false, false>, (const void*)logmel512s_kernel<MODE, NR, false, false, true>,
-                       (const void*)logmel512s_kernel<MODE, NR, false, true, false>, (const void*)logmel512s_kernel<MODE, NR, false, true, true>,
-                       (const void*)logmel512s_kernel<MODE, (NR < 3 ? 3 : NR), true, false, false>, (const void*)logmel512s_kernel<MODE, (NR < 3 ? 3 : NR), true, false, true>,
-                       (const void*)logmel512s_kernel<MODE, (NR < 3 ? 3 : NR), true, true, false>, (const void*)logmel512s_kernel<MODE, (NR < 3 ? 3 : NR), true, true, true>};
+  constexpr int NRP = NR < 3 ? 3 : NR;
+  const void* fn[8] = {(const void*)logmel512s_kernel<MODE, NR, false, false, false, XA>, (const void*)logmel512s_kernel<MODE, NR, false, false, true, XA>,
+                       (const void*)logmel512s_kernel<MODE, NR, false, true, false, XA>, (const void*)logmel512s_kernel<MODE, NR, false, true, true, XA>,
+                       (const void*)logmel512s_kernel<MODE, NRP, true, false, false, XA>, (const void*)logmel512s_kernel<MODE, NRP, true, false, true, XA>,
+                       (const void*)logmel512s_kernel<MODE, NRP, true, true, false, XA>, (const void*)logmel512s_kernel<MODE, NRP, true, true, true, XA>};
   for (int i = 0; i < 8; ++i)
     if (hipFuncSetAttribute(fn[i], hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
   return true;
 }
 
 bool set_s16_attr(int bytes) {
-  return set_s16_attr_mn<0, 1>(bytes) && set_s16_attr_mn<1, 1>(bytes) && set_s16_attr_mn<2, 1>(bytes) &&
-         set_s16_attr_mn<0, 2>(bytes) && set_s16_attr_mn<1, 2>(bytes) && set_s16_attr_mn<2, 2>(bytes) &&
-         set_s16_attr_mn<0, 3>(bytes) && set_s16_attr_mn<1, 3>(bytes) && set_s16_attr_mn<2, 3>(bytes) &&
-         set_s16_attr_mn<0, 4>(bytes) && set_s16_attr_mn<1, 4>(bytes) && set_s16_attr_mn<2, 4>(bytes);
+  return set_s16_attr_mn<0, 1, false>(bytes) && set_s16_attr_mn<1, 1, false>(bytes) && set_s16_attr_mn<2, 1, false>(bytes) &&
+         set_s16_attr_mn<0, 2, false>(bytes) && set_s16_attr_mn<1, 2, false>(bytes) && set_s16_attr_mn<2, 2, false>(bytes) &&
+         set_s16_attr_mn<0, 3, false>(bytes) && set_s16_attr_mn<1, 3, false>(bytes) && set_s16_attr_mn<2, 3, false>(bytes) &&
+         set_s16_attr_mn<0, 4, false>(bytes) && set_s16_attr_mn<1, 4, false>(bytes) && set_s16_attr_mn<2, 4, false>(bytes) &&
+         set_s16_attr_mn<0, 3, true>(bytes) && set_s16_attr_mn<1, 3, true>(bytes) && set_s16_attr_mn<2, 3, true>(bytes) &&
+         set_s16_attr_mn<0, 4, true>(bytes) && set_s16_attr_mn<1, 4, true>(bytes) && set_s16_attr_mn<2, 4, true>(bytes);
 }

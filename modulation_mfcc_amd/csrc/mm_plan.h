@@ -46,6 +46,7 @@ struct mm_plan {
   int w16_n_runs, w16_n_tab16, w16_ok;
   size_t w16_lds_bytes;
   int s16_nr;                      // staged-sample variant: 16-byte groups per thread and tile (0: not usable)
+  int s16_xa;                      // its ds_write_addtid_b32 exchange (NR 3 / 4, when the plan's LDS layout allows: mm_s16.h)
   size_t s16_lds_bytes;
   // staged-sample variant with the (unclamped) DCT fused in: its own run table (four half-size parts for the
   // DCT waves), DCT A operands, LDS layout
