@@ -341,6 +341,72 @@ int mm_resample_banded_f32(const float* d_x, int64_t rows, int64_t n_in, int64_t
  * rFFT figure.  No reference counterpart. */
 int mm_devcopy_f32(const float* d_src, float* d_dst, int64_t n_floats, void* stream);
 
+/* ---- pYIN f0 tracking (get_f0(method='pyin'), script/calc.py:386-592: librosa.pyin) ---------------- */
+/* Parameters of one pyin call.  The host (modulation_mfcc_amd/pitch.py) derives every field with numpy, as librosa
+ * does: min_period = max(floor(sr / fmax), 1), max_period = min(ceil(sr / fmin), frame_length - win_length - 1),
+ * nbps = ceil(1 / resolution), n_bins = floor(12 nbps log2(fmax / fmin)) + 1, band_h = half-width of the
+ * transition band, max_troughs >= (max_period - min_period + 2) / 2 + 1 (trough slots per frame record),
+ * log_tiny = log(float64 tiny), log_p_init = {log(0 + tiny), log(1 / n_bins + tiny)}. */
+typedef struct mm_pyin_params {
+  double sr, fmin, fmax;
+  double no_trough_prob;
+  double log_tiny;
+  double fill_na;          /* f0 of unvoiced frames (NaN by default)                                   */
+  double log_p_init[2];    /* voiced, unvoiced                                                         */
+  int32_t frame_length, win_length, hop_length;
+  int32_t center;          /* 1: frame_length / 2 zeros each side (pad_mode='constant'); 0: no padding */
+  int32_t min_period, max_period, n_thresholds, nbps;
+  int32_t n_bins, band_h, max_troughs, reserved;
+} mm_pyin_params;
+
+/* Constant float64 tables, DEVICE pointers, built on the host with scipy / numpy. */
+typedef struct mm_pyin_tables {
+  const double* thresholds;  /* [n_thresholds + 1] linspace(0, 1)                                        */
+  const double* beta_probs;  /* [n_thresholds] diff(beta.cdf(thresholds, *beta_parameters))             */
+  const double* beta_cum;    /* [n_thresholds + 1] np.sum(beta_probs[:k])                                */
+  const double* boltzmann;   /* [max_troughs + 1][max_troughs] boltzmann.pmf(k, lambda, N) at [N][k]     */
+  const double* log_same;    /* [n_bins][2 band_h + 1] log(A + tiny) of source j - band_h + d, same voicing */
+  const double* log_cross;   /* [n_bins][2 band_h + 1] the same across voicing                           */
+  const double* freqs;       /* [n_bins] fmin 2 ** (k / (12 nbps))                                       */
+} mm_pyin_tables;
+
+/* MM_OK, MM_ERR_INVALID_ARG (fmin >= fmax, fmax > sr / 2, win_length >= frame_length,
+ * max_period < min_period + 2, inconsistent derived fields) or MM_ERR_UNSUPPORTED (beyond the kernels' LDS:
+ * max_troughs > 512, n_bins > ~800, win_length + max_period > ~8 k).  Host only. */
+int mm_pyin_check(const mm_pyin_params* p);
+/* 1 + (n + 2 (frame_length / 2) center - frame_length) / hop_length; 0 when the clip is too short. */
+int64_t mm_pyin_num_frames(const mm_pyin_params* p, int64_t n);
+/* Stage: the cumulative-mean-normalised difference rows of rows x n signals (dtype 0 = float32, 1 = float64;
+ * [rows][x_stride]) -> d_cmnd float64 [rows][n_frames][max_period - min_period + 1]. */
+int mm_pyin_cmnd(const mm_pyin_params* p, const void* d_x, int32_t dtype, int64_t rows, int64_t n, int64_t x_stride,
+                 double* d_cmnd, void* stream);
+/* Stage: CMND rows of `frames` frames -> per-frame records: d_count [frames], d_bins / d_probs [frames][max_troughs]
+ * (the observation's nonzero voiced bins, ascending lag = descending bin, duplicates resolved as librosa assigns them)
+ * and d_voiced_prob [frames]. */
+int mm_pyin_candidates(const mm_pyin_params* p, const mm_pyin_tables* t, const double* d_cmnd, int64_t frames,
+                       int32_t* d_count, int32_t* d_bins, double* d_probs, double* d_voiced_prob, void* stream);
+/* Stage: banded Viterbi decode of rows x n_frames records -> d_states int32, d_f0 float64, d_voiced uint8
+ * [rows][n_frames]; workspace = the int16 back-pointers. */
+size_t mm_pyin_decode_workspace_bytes(const mm_pyin_params* p, int64_t rows, int64_t n_frames);
+int mm_pyin_decode(const mm_pyin_params* p, const mm_pyin_tables* t, const int32_t* d_count, const int32_t* d_bins,
+                   const double* d_probs, const double* d_voiced_prob, int64_t rows, int64_t n_frames, int32_t* d_states,
+                   double* d_f0, uint8_t* d_voiced, void* d_ws, size_t ws_bytes, void* stream);
+/* Whole path, signal -> (f0, voiced_flag, voiced_prob, states) per [rows][n_frames]; workspace from
+ * mm_pyin_workspace_bytes (back-pointers + records of every frame, CMND scratch of at most 16 k frames). */
+size_t mm_pyin_workspace_bytes(const mm_pyin_params* p, int64_t rows, int64_t n);
+int mm_pyin_f32(const mm_pyin_params* p, const mm_pyin_tables* t, const float* d_x, int64_t rows, int64_t n,
+                int64_t x_stride, double* d_f0, uint8_t* d_voiced, double* d_voiced_prob, int32_t* d_states, void* d_ws,
+                size_t ws_bytes, void* stream);
+int mm_pyin_f64(const mm_pyin_params* p, const mm_pyin_tables* t, const double* d_x, int64_t rows, int64_t n,
+                int64_t x_stride, double* d_f0, uint8_t* d_voiced, double* d_voiced_prob, int32_t* d_states, void* d_ws,
+                size_t ws_bytes, void* stream);
+/* interp_NAN(method='linear') (script/calc.py:345-385) of float64 rows: NaN samples get scipy interp1d's linear
+ * interpolation between their valid neighbours, extrapolated from the first / last two valid samples at the ends.
+ * Rows with fewer than two valid samples are copied unchanged (scipy raises; the host checks). d_y may equal d_x
+ * only when the strides are equal. */
+int mm_interp_nan_linear_f64(const double* d_x, int64_t rows, int64_t n, int64_t x_stride, double* d_y, int64_t y_stride,
+                             void* stream);
+
 /* ---- per-kernel device timing (hipEvents on the launch stream) ------------------------- */
 /* on = 0: off; 1: every stage; otherwise a mask with bit (MM_STAGE_x + 1) set for each stage to time
  * (two hipEventRecord per timed launch: timing fewer stages perturbs the stream less). */

@@ -11,5 +11,6 @@ from .calc import (get_velocity, calculate_amplitude_envelope, velocity_batch, a
                    hilbert_envelope_batch)
 from .filters import sosfiltfilt_batch  # noqa: F401
 from .audio_io import load_audio, load_wav, resample_batch  # noqa: F401
+from .pitch import pyin_batch, pyin, interp_NAN, get_f0  # noqa: F401
 
 __version__ = "0.2.0"

@@ -57,6 +57,22 @@ class mm_stencil(C.Structure):
     ]
 
 
+class mm_pyin_params(C.Structure):
+    _fields_ = [
+        ("sr", C.c_double), ("fmin", C.c_double), ("fmax", C.c_double),
+        ("no_trough_prob", C.c_double), ("log_tiny", C.c_double), ("fill_na", C.c_double),
+        ("log_p_init", C.c_double * 2),
+        ("frame_length", C.c_int32), ("win_length", C.c_int32), ("hop_length", C.c_int32), ("center", C.c_int32),
+        ("min_period", C.c_int32), ("max_period", C.c_int32), ("n_thresholds", C.c_int32), ("nbps", C.c_int32),
+        ("n_bins", C.c_int32), ("band_h", C.c_int32), ("max_troughs", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class mm_pyin_tables(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("thresholds", "beta_probs", "beta_cum", "boltzmann", "log_same", "log_cross",
+                                           "freqs")]
+
+
 class MMError(RuntimeError):
     def __init__(self, status, what, detail=""):
         self.status = status
@@ -66,6 +82,8 @@ class MMError(RuntimeError):
 _vp = C.c_void_p
 _i64 = C.c_int64
 _cfgp = C.POINTER(mm_config)
+_pyp = C.POINTER(mm_pyin_params)
+_pyt = C.POINTER(mm_pyin_tables)
 
 # name -> (restype, argtypes); every symbol include/modmfcc.h declares
 PROTOTYPES = {
@@ -122,6 +140,16 @@ PROTOTYPES = {
     "mm_resample_banded_f32": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_int32, _vp, _i64, _vp]),
     "mm_devcopy_f32": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "mm_pyin_check": (C.c_int, [_pyp]),
+    "mm_pyin_num_frames": (_i64, [_pyp, _i64]),
+    "mm_pyin_cmnd": (C.c_int, [_pyp, _vp, C.c_int32, _i64, _i64, _i64, _vp, _vp]),
+    "mm_pyin_candidates": (C.c_int, [_pyp, _pyt, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "mm_pyin_decode_workspace_bytes": (C.c_size_t, [_pyp, _i64, _i64]),
+    "mm_pyin_decode": (C.c_int, [_pyp, _pyt, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "mm_pyin_workspace_bytes": (C.c_size_t, [_pyp, _i64, _i64]),
+    "mm_pyin_f32": (C.c_int, [_pyp, _pyt, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "mm_pyin_f64": (C.c_int, [_pyp, _pyt, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "mm_interp_nan_linear_f64": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp]),
     "mm_timing_enable": (C.c_int, [_vp, C.c_int]),
     "mm_timing_read": (C.c_int, [_vp, _vp, _vp]),
 }

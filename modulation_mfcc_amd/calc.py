@@ -3,7 +3,8 @@
 script/calc.py holds no MFCC arithmetic; what the north star names as the
 drop-in surface is ``applyFilter`` (script/calc.py:23-129), ``get_velocity`` (:593-650, applied by
 the UI to the MFCC-change curve, script/main.py:668-713) and the RMS / Hilbert amplitude envelope
-(:221-343).  Praat-backed functions (f0, formants, RMSpraat) and the EMA reader are out of scope.
+(:221-343), and the pYIN branch of ``get_f0`` with its ``interp_NAN`` (:345-592; modulation_mfcc_amd.pitch).  Praat-backed
+functions (f0 by 'praatac' / 'praatcc', formants, RMSpraat) and the EMA reader are out of scope.
 """
 from __future__ import annotations
 
@@ -11,8 +12,9 @@ import numpy as np
 from scipy.signal import savgol_filter
 
 from .filters import applyFilter
+from .pitch import get_f0, interp_NAN  # noqa: F401
 
-__all__ = ["applyFilter", "get_velocity", "calculate_amplitude_envelope", "velocity_stencil", "velocity_batch", "apply_stencil",
+__all__ = ["applyFilter", "get_f0", "interp_NAN", "get_velocity", "calculate_amplitude_envelope", "velocity_stencil", "velocity_batch", "apply_stencil",
            "hilbert_envelope_batch", "amplitude_envelope_batch"]
 
 

@@ -5,3 +5,4 @@
 #include "mm_reg2.hip"
 #include "mm_tail.hip"
 #include "mm_side.hip"
+#include "mm_pitch.hip"
