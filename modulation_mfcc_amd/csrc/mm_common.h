@@ -240,13 +240,6 @@ int ilog2(int v) {
   return l;
 }
 
-template <class T>
-int upload(T** dst, const void* src, size_t bytes) {
-  HIP_TRY(hipMalloc((void**)dst, bytes));
-  HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-  return MM_OK;
-}
-
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 }  // namespace

@@ -17,7 +17,7 @@
 //     ds_write_addtid_b32 per register (2 LDS cycles, a ds_write_b32 costs 4), 64-float blocks at
 //     mm_s16_xb offsets that keep the b128 reads conflict-free.
 //
-// Requirements (checked by launch_stft, which otherwise falls back to the direct-load kernel, or to the
+// Requirements (checked by choose_kernel, which otherwise falls back to the direct-load kernel, or to the
 // generic one for odd hops / pre-emphasis, which only this kernel of the n_fft = 512 family handles):
 // n_samples >= 4, 63*hop + 512 <= NR*4096 (16-byte aligned rows and n_samples % 4 == 0 take the plain
 // instantiation, anything else UNAL).
@@ -1016,7 +1016,7 @@ __global__ __launch_bounds__(1024) void logmel512s_kernel(Logmel512Params p) {
 template <int MODE, int NR, bool XA>
 static void launch_s16_mn(bool pre, bool odd, bool unal, dim3 grid, size_t lds, hipStream_t st, const Logmel512Params& q) {
 #define MM_S16_GO(PP, OO, UU) hipLaunchKernelGGL((logmel512s_kernel<MODE, NR, PP, OO, UU, XA>), grid, dim3(1024), lds, st, q)
-  if (NR < 3) {          // (plans with pre-emphasis never ask for NR 1 / 2: mm_plan_create)
+  if (NR < 3) {          // (plans with pre-emphasis never ask for NR 1 / 2: setup_tile512)
     switch ((odd ? 2 : 0) | (unal ? 1 : 0)) {
       case 0: MM_S16_GO(false, false, false); break;
       case 1: MM_S16_GO(false, false, true); break;

@@ -25,81 +25,102 @@ struct AnyPlan {
 #define MM_MAX_TIMED 16384
 #define MM_MAX_SAMPLES (((int64_t)1 << 29) - 8192)
 
+// Plan state, one part per kernel family (filled by the set-up functions of mm_plan_create, read by the launchers of
+// launch_stft).  A family whose `ok` stays false is not used.  The plan owns every device table: upload() records each
+// allocation and the destructor frees them.
 struct mm_plan {
-  mm_config cfg;
-  int device;
-  int n_bins, log2nc, kp;
-  float db_offset;
-  int path;           // 0 generic, 1 radix-16 register kernels
-  int force_generic;
-  float* d_window;
-  float2* d_tw;
-  int *d_mel_start, *d_mel_len, *d_mel_off;
-  float* d_mel_w;
-  float* d_dct_t;
-  float* d_sw_tab;             // mel run table of the fused kernel (headers + groups)
-  int* d_sw_part;
-  int sw_n_runs, sw_n_tab16;
-  size_t lm_lds_bytes;
-  float *d_w16_tab, *d_lane_tab;   // 16-wave variant: its own run table + per-lane records
-  int* d_w16_part;
-  int w16_n_runs, w16_n_tab16, w16_ok;
-  size_t w16_lds_bytes;
-  int s16_nr;                      // staged-sample variant: 16-byte groups per thread and tile (0: not usable)
-  int s16_xa;                      // its ds_write_addtid_b32 exchange (NR 3 / 4, when the plan's LDS layout allows: mm_s16.h)
-  size_t s16_lds_bytes;
-  // staged-sample variant with the (unclamped) DCT fused in: its own run table (four half-size parts for the
-  // DCT waves), DCT A operands, LDS layout
-  float *d_s16f_tab, *d_s16f_dcta;
-  int* d_s16f_part;
-  int s16f_ok, s16f_n_runs, s16f_n_tab16, s16f_lt_rows, s16f_nk, s16f_kb;
-  unsigned s16f_lt_off, s16f_dcta_off;
-  unsigned long long s16f_roles;
-  size_t s16f_lds_bytes;
-  int wpf_waves_half; size_t wpf_lds_half;   // launch geometry of the half-band instantiations (up to sixteen waves)
-  int wpf_half, wpf_pairs;         // the mel bank reads no bin >= NC / 2: split pairs the kernel forms (WpfParams::n_pairs / half_band)
-  int wpf_z;                       // 3: the window is zero for a lane's first and last three pairs (logmel_wpf_kernel<.., Z = 3>)
-  int s16_halfwin;                 // the 512-point window is zero outside [128, 384): the staged kernel prunes its first stage
-  int s16f_flags;                  // Logmel512Params::dct_flags (MM_S16F_SINGLE | MM_S16F_SKIP)
-  // 12-wave MFMA-mel variant (mm_logmel12m.hip.inc)
-  float *d_m12_a, *d_m12_dct, *d_zeros;
-  int m12_units[MM_M12_MW * MM_M12_UMAX * 4], m12_nunits[8];
-  int m12_ok, m12_nb, m12_nstep8, m12_nr, m12_s_floats, m12_fused_dct;
-  unsigned m12_win_off, m12_tw_off, m12_a_off, m12_dct_off, m12_part_off, m12_cnt_off;
-  int m12_n_a2;
-  size_t m12_lds_bytes;
-  float* d_dctfm_a;                // dct_clamp_fm_mfma_kernel: A operands [kb][nk][64] (nullptr: VALU kernel)
-  int dctfm_nk, dctfm_kb;
-  size_t dctfm_lds;
-  float* d_dctw_a;                 // dct_clamp_fm_wave_kernel<CH>: the same, steps padded to a multiple of CH with zeros
-  int dctw_nk, dctw_ch;
-  int variant;                     // mm_plan_set_variant: 0 = automatic
-  int no_fuse;                     // mm_plan_set_fuse_dct(0): always run the separate clamp + DCT kernel
-  int no_fuse_tail;                // mm_plan_set_fuse_tail(0): mm_mfcc_modspec_f32 always runs its separate launches
-  int fuse_tail_wide;              // mm_plan_set_fuse_tail(2): clip mode also for 2048-point trajectories and for mm_mfcc_f32 (empty filters)
-  unsigned s16f_red_off;           // clip mode: LDS offset of the per-wave clip max / min slots
+  mm_config cfg{};
+  int device = 0;
+  int n_bins = 0, log2nc = 0, kp = 0;
+  float db_offset = 0.0f;
+  int num_cus = 256;
 
-  float* d_window_e;                       // n_fft < 512 embedded in the 512-point kernels: window centred in 512
-  int embed;                               // 512 / n_fft for such plans, else 1
-  float *d_k2_lane_tab, *d_k2_mel_lane;   // wave-per-frame-group kernel (n_fft 512 / 1024 / 2048)
-  float* d_rf2k_lane_tab;                 // rfft_wpf_kernel<4> (stage-isolated rFFT, n = 2048)
-  int rf2k_ok;
-  int k2_ok, wpf_r, wpf_waves, wpf_group_max;
-  size_t wpf_lds_bytes;
-  size_t wpf_lds16;                        // sixteen-wave form of the same kernel (W16): LDS bytes, and whether it applies
-  int wpf_w16;
-  int num_cus;
-  float* d_h16_tab; int* d_h16_part;       // 32-frame-tile / two-workgroup experiment (mm_logmel16h.hip.inc)
-  int h16_ok, h16_n_pairs, h16_n_tab16;
-  size_t h16_lds_bytes;
-  AnyPlan any;                             // any-length STFT (mm_anyfft.hip.inc): n_fft that is not a power of two in [32, 4096]
-  // timing
-  int timing_on;
-  std::vector<hipEvent_t> ev_pool;  // pairs
-  std::vector<int> ev_stage;
-  int ev_used;
-  double t_sum[MM_NUM_STAGES];
-  int64_t t_cnt[MM_NUM_STAGES];
+  struct Base {                    // generic STFT, clamp + DCT, rFFT: every plan has these tables
+    float *d_window = nullptr, *d_mel_w = nullptr, *d_dct_t = nullptr;   // d_dct_t: [n_mels][kp]
+    float2* d_tw = nullptr;
+    int *d_mel_start = nullptr, *d_mel_len = nullptr, *d_mel_off = nullptr;
+  } base;
+  // n_fft < 512 embedded in the 512-point kernels: the window centred in 512, factor 512 / n_fft (else 1)
+  struct Embed { float* d_window = nullptr; int factor = 1; } embed;
+  struct W8 {                      // logmel512_kernel: mel run table (headers + groups) and wave parts
+    bool ok = false; float* d_tab = nullptr; int* d_part = nullptr;
+    int n_runs = 0, n_tab16 = 0; size_t lds_bytes = 0;
+  } w8;
+  struct W16 {                     // logmel512w_kernel: its own 16-way run table + per-lane records
+    bool ok = false; float *d_tab = nullptr, *d_lane_tab = nullptr; int* d_part = nullptr;
+    int n_runs = 0, n_tab16 = 0; size_t lds_bytes = 0;
+  } w16;
+  struct H16 {                     // 32-frame-tile / two-workgroup experiment (mm_logmel16h.hip.inc)
+    bool ok = false; float* d_tab = nullptr; int* d_part = nullptr;
+    int n_pairs = 0, n_tab16 = 0; size_t lds_bytes = 0;
+  } h16;
+  struct S16 {                     // staged-sample variant (mm_logmel16s.hip.inc), on the W16 tables
+    int nr = 0;                    // 16-byte groups per thread and tile (0: not usable)
+    bool xa = false;               // its ds_write_addtid_b32 exchange (NR 3 / 4, when the plan's LDS layout allows: mm_s16.h)
+    bool halfwin = false;          // the 512-point window is zero outside [128, 384): the kernel prunes its first stage
+    size_t lds_bytes = 0;
+  } s16;
+  struct S16F {                    // the staged-sample variant with the (unclamped) DCT fused in: its own run table (four
+    bool ok = false;               // half-size parts for the DCT waves), DCT A operands, LDS layout
+    float *d_tab = nullptr, *d_dcta = nullptr; int* d_part = nullptr;
+    int n_runs = 0, n_tab16 = 0, lt_rows = 0, nk = 0, kb = 0;
+    int flags = 0;                 // Logmel512Params::dct_flags (MM_S16F_SINGLE | MM_S16F_SKIP)
+    unsigned lt_off = 0, dcta_off = 0, red_off = 0;   // red_off: clip mode's per-wave clip max / min slots
+    unsigned long long roles = 0; size_t lds_bytes = 0;
+  } s16f;
+  struct M12 {                     // 12-wave MFMA-mel variant (mm_logmel12m.hip.inc)
+    bool ok = false, fused_dct = false;
+    float *d_a = nullptr, *d_dct = nullptr, *d_zeros = nullptr;
+    int units[MM_M12_MW * MM_M12_UMAX * 4] = {}, n_units[8] = {};
+    int nb = 0, nr = 0, s_floats = 0, n_a2 = 0;
+    unsigned win_off = 0, tw_off = 0, a_off = 0, dct_off = 0, part_off = 0, cnt_off = 0;
+    size_t lds_bytes = 0;
+  } m12;
+  struct Wpf {                     // wave-per-frame-group kernel (n_fft 512 / 1024 / 2048)
+    bool ok = false; float *d_lane_tab = nullptr, *d_mel_lane = nullptr;
+    int r = 0, waves = 0, group_max = 0; size_t lds_bytes = 0;
+    bool w16 = false; size_t lds16 = 0;         // sixteen-wave form (W16): whether it applies, its LDS bytes
+    bool half = false; int pairs = 0;           // the mel bank reads no bin >= NC / 2: split pairs the kernel forms (NI)
+    int waves_half = 0; size_t lds_half = 0;    // launch geometry of the half-band instantiations (up to sixteen waves)
+    int z = 0;                     // 3 / 5 / 6 / 7: the window is zero for a lane's first and last Z pairs (logmel_wpf_kernel<.., Z>)
+  } wpf;
+  struct DctFm {                   // clamp + DCT of the frame-major rows on the matrix pipe
+    float* d_a = nullptr;          // A operands [kb][nk][64] (nullptr: VALU kernel); d_wave_a: the same for
+    float* d_wave_a = nullptr;     // dct_clamp_fm_wave_kernel<CH>, steps padded to a multiple of CH with zeros
+    int kb = 0, wave_nk = 0, ch = 0;
+  } dctfm;
+  struct Rf2k { bool ok = false; float* d_lane_tab = nullptr; } rf2k;   // rfft_wpf_kernel<4> (stage-isolated rFFT, n = 2048)
+  AnyPlan any;                     // any-length STFT (mm_anyfft.hip.inc): n_fft that is not a power of two in [32, 4096]
+
+  struct Switches {
+    int variant = 0;               // mm_plan_set_variant: 0 = automatic
+    int force_generic = 0;         // mm_plan_force_generic
+    int no_fuse = 0;               // mm_plan_set_fuse_dct(0): always run the separate clamp + DCT kernel
+    int no_fuse_tail = 0;          // mm_plan_set_fuse_tail(0): mm_mfcc_modspec_f32 always runs its separate launches
+    int fuse_tail_wide = 0;        // mm_plan_set_fuse_tail(2): clip mode also for 2048-point trajectories and for mm_mfcc_f32 (empty filters)
+  } user;
+  struct Timing {
+    int on = 0, ev_used = 0;
+    std::vector<hipEvent_t> ev_pool;   // pairs
+    std::vector<int> ev_stage;
+    double t_sum[MM_NUM_STAGES] = {};
+    int64_t t_cnt[MM_NUM_STAGES] = {};
+  } timing;
+
+  mm_plan() = default;
+  mm_plan(const mm_plan&) = delete; mm_plan& operator=(const mm_plan&) = delete;
+  ~mm_plan() { for (void* d : owned) (void)hipFree(d); }
+  // device copy of a host table; the allocation is recorded before the copy, so a failed copy does not leak
+  template <class T>
+  int upload(T** dst, const void* src, size_t bytes) {
+    HIP_TRY(hipMalloc((void**)dst, bytes));
+    owned.push_back(*dst);
+    HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+    return MM_OK;
+  }
+
+ private:
+  std::vector<void*> owned;
 };
 
 namespace {
@@ -109,21 +130,22 @@ struct StageTimer {
   hipStream_t s;
   int idx;
   StageTimer(mm_plan* plan, int stage, hipStream_t stream) : p(plan), s(stream), idx(-1) {
-    if (!p->timing_on || p->ev_used >= MM_MAX_TIMED) return;
-    if (p->timing_on != 1 && !((p->timing_on >> (stage + 1)) & 1)) return;   // stage mask
-    if ((size_t)(2 * p->ev_used + 1) >= p->ev_pool.size()) {
+    mm_plan::Timing& t = p->timing;
+    if (!t.on || t.ev_used >= MM_MAX_TIMED) return;
+    if (t.on != 1 && !((t.on >> (stage + 1)) & 1)) return;   // stage mask
+    if ((size_t)(2 * t.ev_used + 1) >= t.ev_pool.size()) {
       hipEvent_t a, b;
       if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
-      p->ev_pool.push_back(a);
-      p->ev_pool.push_back(b);
+      t.ev_pool.push_back(a);
+      t.ev_pool.push_back(b);
     }
-    idx = p->ev_used++;
-    p->ev_stage.resize(p->ev_used);
-    p->ev_stage[idx] = stage;
-    (void)hipEventRecord(p->ev_pool[2 * idx], s);
+    idx = t.ev_used++;
+    t.ev_stage.resize(t.ev_used);
+    t.ev_stage[idx] = stage;
+    (void)hipEventRecord(t.ev_pool[2 * idx], s);
   }
   ~StageTimer() {
-    if (idx >= 0) (void)hipEventRecord(p->ev_pool[2 * idx + 1], s);
+    if (idx >= 0) (void)hipEventRecord(p->timing.ev_pool[2 * idx + 1], s);
   }
 };
 

@@ -7,7 +7,7 @@
 // 16x16 exchange with ds_write_addtid_b32 and need pitch 268 (4 rows = 1072 >= the 1068 floats of mm_s16_xb's blocks;
 // 268 = 4 x 67, 67 odd: phase B's lane-per-frame b128 reads stay conflict-free): 2 KB more LDS.  The others keep the
 // ds_write_b32 exchange at pitch 260: NR 1 / 2 (the reference default, NR 1, ran 2.5 % slower with it) and every plan
-// whose fused-DCT layout only fits without those 2 KB (mm_plan_create: s16_xa).
+// whose fused-DCT layout only fits without those 2 KB (setup_tile512 / setup_s16f in mm_api.hip: mm_plan::S16::xa).
 #define MM_S16_XA_PITCH 268
 #define MM_S16_PITCH(XA) ((XA) ? MM_S16_XA_PITCH : MM_LM_PITCH)
 #define MM_S16_S_OFF(XA) (64 * MM_S16_PITCH(XA) * 4)

@@ -79,10 +79,10 @@ static ChgForm change_form(const mm_plan* p, int64_t batch, int64_t n_frames, in
 #ifdef MM_DEV
   if (const char* e = getenv("MM_CHG_FORM")) few_long = e[0] == 's';      // side build only: A/B of the two forms (tools/chg_forms.py)
 #endif
-  if (!p->no_fuse_tail && small_sec && (r.cs.G < 1 || few_long)) {
+  if (!p->user.no_fuse_tail && small_sec && (r.cs.G < 1 || few_long)) {
     r.form = MM_CHG_SEGMENTED;
     r.need = chg_seg_workspace_doubles(batch, n_rows, n_frames, (int)p1, (int)p2);
-  } else if (!p->no_fuse_tail && small_sec && r.cs.G >= 1) {
+  } else if (!p->user.no_fuse_tail && small_sec && r.cs.G >= 1) {
     r.form = MM_CHG_CLIP;
     r.need = (size_t)r.cs.tab_n;        // filter tables only (a few KB): the clip lives in LDS
   } else {
