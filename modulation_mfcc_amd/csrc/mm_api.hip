@@ -13,6 +13,7 @@
 //                              trajectory rFFT of the modulation spectrum)
 // The register radix-16 kernels for n_fft 512/1024/2048 live in mm_fft16.hip.inc.
 #include <memory>
+#include <utility>
 
 #include "mm_common.h"
 #include "mm_plan.h"

@@ -395,6 +395,7 @@ struct Logmel512Params {
 #define MM_LM_WIN_OFF (MM_LM_EX_OFF + 8 * f16::Geo<1>::WAVE_C * 8)
 #define MM_LM_TAB_OFF (MM_LM_WIN_OFF + 512 * 4)
 
+#include "mm_tile512.hip.inc"                // what the five tile kernels share
 
 struct LmItem {      // wave-uniform description of one phase-A item (4 frames of this wave)
   const float* a;    // clip base
@@ -480,18 +481,9 @@ __device__ __forceinline__ void lm_compute_item(float2 (&x)[16], const Logmel512
   f16::cfft<1>(x, t, ex, row, q);
   float2 pb[9];
   f16::fetch_partners<1>(x, pb, lane, q);
-  float* pr = P + (32 * it + 4 * wave + row) * MM_LM_PITCH;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    float2 xa, xb;
-    f16::split_pair(x[f16::P16(j)], pb[j], t.wp[j], xa, xb);
-    pr[q + 16 * j] = fmaf(xa.x, xa.x, xa.y * xa.y);
-    pr[256 - q - 16 * j] = fmaf(xb.x, xb.x, xb.y * xb.y);
-  }
-  if (q == 0) {
-    const float2 zm = x[f16::P16(8)];
-    pr[128] = fmaf(zm.x, zm.x, zm.y * zm.y);
-  }
+  float pw[17];
+  tile512_split_power(x, pb, t.wp, pw);
+  tile512_store_power_row<false>(P + (32 * it + 4 * wave + row) * MM_LM_PITCH, q, pw);
 }
 
 template <int MODE>
@@ -537,13 +529,7 @@ __global__ __launch_bounds__(512) void logmel512_kernel(Logmel512Params p) {
     wg_barrier_lds();
     // ---------------- phase B ----------------
     if (MODE == 0) {
-      for (int r = wave; r < 64; r += 8) {
-        if (t0 + r < p.n_frames) {
-          float* o = p.out_power + ((b * p.n_frames) + t0 + r) * 257;
-          const float* src = P + r * MM_LM_PITCH;
-          for (int k = lane; k < 257; k += 64) o[k] = src[k];
-        }
-      }
+      tile512_store_power_tile(p.out_power, P, MM_LM_PITCH, b, t0, p.n_frames, wave, 8, lane);
     } else {
       const bool valid = (t0 + lane) < p.n_frames;
       float* o = p.out_logmel + (b * p.n_mels) * p.n_frames + t0 + lane;
@@ -553,27 +539,14 @@ __global__ __launch_bounds__(512) void logmel512_kernel(Logmel512Params p) {
       float vmax = -INFINITY, carry = 0.0f;
       float4 h = hdr[run0];
       for (int r = run0; r < run1; ++r) {
-        const int k4 = __builtin_amdgcn_readfirstlane(__float_as_int(h.x));
-        const int ng = __builtin_amdgcn_readfirstlane(__float_as_int(h.y));
-        const int go = __builtin_amdgcn_readfirstlane(__float_as_int(h.z));
-        const int dd = __builtin_amdgcn_readfirstlane(__float_as_int(h.w));
+        const Tile512Run rh = tile512_run_header(h);
         if (r + 1 < run1) h = hdr[r + 1];
-        const float4* pp = reinterpret_cast<const float4*>(pl + k4);
-        const float4* gw = grp + 2 * go;
         float sa = 0.0f, sb = 0.0f;
-#pragma unroll 2
-        for (int g = 0; g < ng; ++g) {
-          const float4 pv = pp[g], wa = gw[2 * g], wb = gw[2 * g + 1];   // (wlo, whi) of bins 0,1 | 2,3
-          sa = fmaf(wa.x, pv.x, sa); sb = fmaf(wa.y, pv.x, sb);
-          sa = fmaf(wa.z, pv.y, sa); sb = fmaf(wa.w, pv.y, sb);
-          sa = fmaf(wb.x, pv.z, sa); sb = fmaf(wb.y, pv.z, sb);
-          sa = fmaf(wb.z, pv.w, sa); sb = fmaf(wb.w, pv.w, sb);
-        }
-        if (dd >= m0) {   // filter dd is complete: rising half from the previous run + falling half
-          const float v = carry + sa;
-          const float db = 3.0102999566398120f * __builtin_amdgcn_logf(fmaxf(p.amin, v)) - p.db_offset;
+        tile512_group_dot<2>(reinterpret_cast<const float4*>(pl + rh.k4), grp + 2 * rh.go, rh.ng, sa, sb);
+        if (rh.dd >= m0) {   // filter dd is complete: rising half from the previous run + falling half
+          const float db = tile512_db(fmaxf(p.amin, carry + sa), p.db_offset);
           if (valid) {
-            o[(int64_t)dd * p.n_frames] = db;
+            o[(int64_t)rh.dd * p.n_frames] = db;
             vmax = fmaxf(vmax, db);
           }
         }

@@ -644,40 +644,30 @@ static bool build_m12_tables(const mm_config& c, const float* mel, const float* 
   return true;
 }
 
-template <int NR>
-static void launch_m12_n(bool pre, bool odd, bool unal, dim3 grid, size_t lds, hipStream_t st, const Logmel12mParams& q) {
-#define MM_M12_GO(PP, OO, UU) hipLaunchKernelGGL((logmel12m_kernel<NR, PP, OO, UU>), grid, dim3(MM_M12_THREADS), lds, st, q)
-  switch ((pre ? 4 : 0) | (odd ? 2 : 0) | (unal ? 1 : 0)) {
-    case 0: MM_M12_GO(false, false, false); break;
-    case 1: MM_M12_GO(false, false, true); break;
-    case 2: MM_M12_GO(false, true, false); break;
-    case 3: MM_M12_GO(false, true, true); break;
-    case 4: MM_M12_GO(true, false, false); break;
-    case 5: MM_M12_GO(true, false, true); break;
-    case 6: MM_M12_GO(true, true, false); break;
-    default: MM_M12_GO(true, true, true); break;
-  }
-#undef MM_M12_GO
+// ---- the instantiations, listed once: key = (nr - 1) << 3 | pre << 2 | odd << 1 | unal, NR 1 .. 3 ----
+using M12Kernel = void (*)(Logmel12mParams);
+#define MM_M12_KEYS 24
+template <int KEY>
+static constexpr M12Kernel m12_entry() {
+  return logmel12m_kernel<(KEY >> 3) + 1, (KEY & 4) != 0, (KEY & 2) != 0, (KEY & 1) != 0>;
 }
+template <int... KEY>
+static M12Kernel m12_lookup(int key, std::integer_sequence<int, KEY...>) {
+  static constexpr M12Kernel table[] = {m12_entry<KEY>()...};
+  return table[key];
+}
+static M12Kernel m12_kernel(int key) { return m12_lookup(key, std::make_integer_sequence<int, MM_M12_KEYS>()); }
 
 static void launch_m12(int nr, bool pre, bool odd, bool unal, dim3 grid, size_t lds, hipStream_t st,
                        const Logmel12mParams& q) {
-  if (nr <= 1) launch_m12_n<1>(pre, odd, unal, grid, lds, st, q);
-  else if (nr == 2) launch_m12_n<2>(pre, odd, unal, grid, lds, st, q);
-  else launch_m12_n<3>(pre, odd, unal, grid, lds, st, q);
-}
-
-template <int NR>
-static bool set_m12_attr_n(int bytes) {
-  const void* fn[8] = {(const void*)logmel12m_kernel<NR, false, false, false>, (const void*)logmel12m_kernel<NR, false, false, true>,
-                       (const void*)logmel12m_kernel<NR, false, true, false>, (const void*)logmel12m_kernel<NR, false, true, true>,
-                       (const void*)logmel12m_kernel<NR, true, false, false>, (const void*)logmel12m_kernel<NR, true, false, true>,
-                       (const void*)logmel12m_kernel<NR, true, true, false>, (const void*)logmel12m_kernel<NR, true, true, true>};
-  for (int i = 0; i < 8; ++i)
-    if (hipFuncSetAttribute(fn[i], hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
-  return true;
+  nr = nr <= 1 ? 1 : nr == 2 ? 2 : 3;
+  const int key = (nr - 1) << 3 | (pre ? 4 : 0) | (odd ? 2 : 0) | (unal ? 1 : 0);
+  hipLaunchKernelGGL(m12_kernel(key), grid, dim3(MM_M12_THREADS), lds, st, q);
 }
 
 static bool set_m12_attr(int bytes) {
-  return set_m12_attr_n<1>(bytes) && set_m12_attr_n<2>(bytes) && set_m12_attr_n<3>(bytes);
+  for (int key = 0; key < MM_M12_KEYS; ++key)
+    if (hipFuncSetAttribute((const void*)m12_kernel(key), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
+      return false;
+  return true;
 }

@@ -61,17 +61,7 @@ __global__ __launch_bounds__(512, 4) void logmel512h_kernel(Logmel512hParams p) 
   int b = tile_begin / tpc, tl = tile_begin - b * tpc;
   int nb = b, ntl = tl;
 
-  // exchange area = this wave's own four power rows (see mm_logmel16s.hip.inc)
-  float* exw = P + 4 * wave * MM_LM_PITCH + row * 256;
-  float* wq0 = exw + (q ^ 0);
-  float* wq1 = exw + (q ^ 4);
-  float* wq2 = exw + (q ^ 8);
-  float* wq3 = exw + (q ^ 12);
-  const int sq = (q >> 2) & 3;
-  const float4* rq0 = reinterpret_cast<const float4*>(exw + q * 16 + 4 * (0 ^ sq));
-  const float4* rq1 = reinterpret_cast<const float4*>(exw + q * 16 + 4 * (1 ^ sq));
-  const float4* rq2 = reinterpret_cast<const float4*>(exw + q * 16 + 4 * (2 ^ sq));
-  const float4* rq3 = reinterpret_cast<const float4*>(exw + q * 16 + 4 * (3 ^ sq));
+  const Tile512ExSwz ex(P + 4 * wave * MM_LM_PITCH, row, q);   // exchange area = this wave's own four power rows
   const float2* sx = reinterpret_cast<const float2*>(S + (4 * wave + row) * p.hop + 2 * q);
 
   float4 sreg[MM_H16_NR];
@@ -91,10 +81,8 @@ __global__ __launch_bounds__(512, 4) void logmel512h_kernel(Logmel512hParams p) 
 #pragma unroll
     for (int j = 0; j < MM_H16_NR; ++j) {
       const int s0 = first + 2048 * j;
-      const bool ok = s0 >= 0 && s0 < n;       // n % 4 == 0: groups never straddle a clip edge
-      float4 v = sreg[j];
-      v.x = ok ? v.x : 0.0f; v.y = ok ? v.y : 0.0f; v.z = ok ? v.z : 0.0f; v.w = ok ? v.w : 0.0f;
-      reinterpret_cast<float4*>(S)[threadIdx.x + 512 * j] = v;
+      // (n % 4 == 0: groups never straddle a clip edge)
+      reinterpret_cast<float4*>(S)[threadIdx.x + 512 * j] = tile512_stage_fix<false, false>(sreg[j], s0, n, 0.0f, 0.0f);
     }
   };
   if (tile_begin < tile_end) {
@@ -103,15 +91,7 @@ __global__ __launch_bounds__(512, 4) void logmel512h_kernel(Logmel512hParams p) 
   }
   __syncthreads();
   float2 wp[8];                               // split twiddles: registers for the whole launch
-  {
-    const float4* s4 = reinterpret_cast<const float4*>(lt + 64);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float4 t = s4[i];
-      wp[2 * i] = make_float2(t.x, t.y);
-      wp[2 * i + 1] = make_float2(t.z, t.w);
-    }
-  }
+  tile512_read_wp(wp, lt);
   const int fr = lane & 31, hh = lane >> 5;   // phase B: frame within the tile, half (part 2w / 2w + 1)
   const int m0h = hh ? m0B : m0A;
 
@@ -125,81 +105,17 @@ __global__ __launch_bounds__(512, 4) void logmel512h_kernel(Logmel512hParams p) 
       float2 x[16];
 #pragma unroll
       for (int n1 = 0; n1 < 16; ++n1) x[n1] = sx[16 * n1];
-      {
-        float2 w[16];
-        w16_read16(w, lt);                       // window
-#pragma unroll
-        for (int n1 = 0; n1 < 16; ++n1) { x[n1].x *= w[n1].x; x[n1].y *= w[n1].y; }
-      }
+      tile512_window(x, lt);
       f16::dft16(x);
-      {
-        float2 w[16];
-        const float4* t4 = reinterpret_cast<const float4*>(lt + 32);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const float4 t = t4[i];
-          w[2 * i] = make_float2(t.x, t.y);
-          w[2 * i + 1] = make_float2(t.z, t.w);
-        }
-#pragma unroll
-        for (int k1 = 1; k1 < 16; ++k1) x[f16::P16(k1)] = f16::cmulf(x[f16::P16(k1)], w[k1 - 1]);
-      }
-      {
-#define MM_H16_WR(k1, val)                                                                         \
-  (((k1) >> 2) == 0 ? wq0 : ((k1) >> 2) == 1 ? wq1 : ((k1) >> 2) == 2 ? wq2 : wq3)[(k1) * 16] = (val)
-#pragma unroll
-        for (int k1 = 0; k1 < 16; ++k1) MM_H16_WR(k1, x[f16::P16(k1)].x);
-        wave_lds_sync();
-        {
-          const float4 v0 = *rq0, v1 = *rq1, v2 = *rq2, v3 = *rq3;
-          x[0].x = v0.x; x[1].x = v0.y; x[2].x = v0.z; x[3].x = v0.w;
-          x[4].x = v1.x; x[5].x = v1.y; x[6].x = v1.z; x[7].x = v1.w;
-          x[8].x = v2.x; x[9].x = v2.y; x[10].x = v2.z; x[11].x = v2.w;
-          x[12].x = v3.x; x[13].x = v3.y; x[14].x = v3.z; x[15].x = v3.w;
-        }
-        wave_lds_sync();
-        float im[16];
-#pragma unroll
-        for (int k1 = 0; k1 < 16; ++k1) im[k1] = x[f16::P16(k1)].y;
-#pragma unroll
-        for (int k1 = 0; k1 < 16; ++k1) MM_H16_WR(k1, im[k1]);
-        wave_lds_sync();
-        {
-          const float4 v0 = *rq0, v1 = *rq1, v2 = *rq2, v3 = *rq3;
-          x[0].y = v0.x; x[1].y = v0.y; x[2].y = v0.z; x[3].y = v0.w;
-          x[4].y = v1.x; x[5].y = v1.y; x[6].y = v1.z; x[7].y = v1.w;
-          x[8].y = v2.x; x[9].y = v2.y; x[10].y = v2.z; x[11].y = v2.w;
-          x[12].y = v3.x; x[13].y = v3.y; x[14].y = v3.z; x[15].y = v3.w;
-        }
-        wave_lds_sync();
-#undef MM_H16_WR
-      }
+      tile512_twiddle(x, lt + MM_LT_TW);
+      tile512_exchange(x, ex);
       f16::dft16(x);
       {
         float2 pb[9];
         f16::fetch_partners<1>(x, pb, lane, q);
-        float* pr = P + (4 * wave + row) * MM_LM_PITCH;
         float pw[17];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float2 xa, xb;
-          f16::split_pair(x[f16::P16(j)], pb[j], wp[j], xa, xb);
-          pw[2 * j] = fmaf(xa.x, xa.x, xa.y * xa.y);
-          pw[2 * j + 1] = fmaf(xb.x, xb.x, xb.y * xb.y);
-        }
-        {
-          const float2 zm = x[f16::P16(8)];
-          pw[16] = fmaf(zm.x, zm.x, zm.y * zm.y);
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          pr[q + 16 * j] = pw[2 * j];
-          pr[256 - q - 16 * j] = pw[2 * j + 1];
-        }
-        if (q == 0) {
-          pr[128] = pw[16];
-          pr[257] = 0.0f; pr[258] = 0.0f; pr[259] = 0.0f;   // pad bins: the exchange of the next frame ran over them
-        }
+        tile512_split_power(x, pb, wp, pw);
+        tile512_store_power_row<true>(P + (4 * wave + row) * MM_LM_PITCH, q, pw);
       }
     }
     wg_barrier_lds();
@@ -223,17 +139,9 @@ __global__ __launch_bounds__(512, 4) void logmel512h_kernel(Logmel512hParams p) 
           const float4* pp = reinterpret_cast<const float4*>(pl + k4);
           const float4* gw = grp + 4 * go + 2 * hh;
           float sa = 0.0f, sb = 0.0f;
-#pragma unroll 2
-          for (int g = 0; g < ng; ++g) {
-            const float4 pv = pp[g], wa = gw[4 * g], wb = gw[4 * g + 1];   // (wlo, whi) of bins 0,1 | 2,3
-            sa = fmaf(wa.x, pv.x, sa); sb = fmaf(wa.y, pv.x, sb);
-            sa = fmaf(wa.z, pv.y, sa); sb = fmaf(wa.w, pv.y, sb);
-            sa = fmaf(wb.x, pv.z, sa); sb = fmaf(wb.y, pv.z, sb);
-            sa = fmaf(wb.z, pv.w, sa); sb = fmaf(wb.w, pv.w, sb);
-          }
+          tile512_group_dot<4>(pp, gw, ng, sa, sb);
           if (dd >= m0h) {
-            const float v = carry + sa;
-            const float db = 3.0102999566398120f * __builtin_amdgcn_logf(fmaxf(p.amin, v)) - p.db_offset;
+            const float db = tile512_db(fmaxf(p.amin, carry + sa), p.db_offset);
             if (valid) {
               obase[(int64_t)dd * p.n_frames] = db;
               vmax = fmaxf(vmax, db);

@@ -787,7 +787,7 @@ __global__ __launch_bounds__(1024) void logmel512s_kernel(Logmel512Params p) {
     }
     {
       float2 w[16];
-      w16_read16(w, lt);                       // window
+      tile512_read_rec<0, 8>(w, lt);                       // window
 #pragma unroll
       for (int n1 = 0; n1 < 16; ++n1) { x[n1].x *= w[n1].x; x[n1].y *= w[n1].y; }
     }
@@ -1011,77 +1011,40 @@ __global__ __launch_bounds__(1024) void logmel512s_kernel(Logmel512Params p) {
   MM_STAMP_END(16)
 }
 
-// ---- host side: the instantiations (MODE 0/1/2 x NR 3/4 x PRE x ODD x UNAL x XA = 96; NR 1/2 -- short hops, e.g. the
-// reference's own 10 kHz default with hop 50: 14.6 KB of samples per tile instead of 48 KB of LDS -- without PRE or XA: 24) ----
-template <int MODE, int NR, bool XA>
-static void launch_s16_mn(bool pre, bool odd, bool unal, dim3 grid, size_t lds, hipStream_t st, const Logmel512Params& q) {
-#define MM_S16_GO(PP, OO, UU) hipLaunchKernelGGL((logmel512s_kernel<MODE, NR, PP, OO, UU, XA>), grid, dim3(1024), lds, st, q)
-  if (NR < 3) {          // (plans with pre-emphasis never ask for NR 1 / 2: setup_tile512)
-    switch ((odd ? 2 : 0) | (unal ? 1 : 0)) {
-      case 0: MM_S16_GO(false, false, false); break;
-      case 1: MM_S16_GO(false, false, true); break;
-      case 2: MM_S16_GO(false, true, false); break;
-      default: MM_S16_GO(false, true, true); break;
-    }
-    return;
-  }
-  constexpr int NRP = NR < 3 ? 3 : NR;      // (keeps the PRE instantiations of NR 1 / 2 from being generated)
-#define MM_S16_GOP(OO, UU) hipLaunchKernelGGL((logmel512s_kernel<MODE, NRP, true, OO, UU, XA>), grid, dim3(1024), lds, st, q)
-  switch ((pre ? 4 : 0) | (odd ? 2 : 0) | (unal ? 1 : 0)) {
-    case 0: MM_S16_GO(false, false, false); break;
-    case 1: MM_S16_GO(false, false, true); break;
-    case 2: MM_S16_GO(false, true, false); break;
-    case 3: MM_S16_GO(false, true, true); break;
-    case 4: MM_S16_GOP(false, false); break;
-    case 5: MM_S16_GOP(false, true); break;
-    case 6: MM_S16_GOP(true, false); break;
-    default: MM_S16_GOP(true, true); break;
-  }
-#undef MM_S16_GOP
-#undef MM_S16_GO
+// ---- host side: the instantiations, listed once.  MODE 0/1/2 x NR 3/4 x PRE x ODD x UNAL x XA = 96; NR 1/2 -- short
+// hops, e.g. the reference's own 10 kHz default with hop 50: 14.6 KB of samples per tile instead of 48 KB of LDS --
+// without PRE or XA (plans with pre-emphasis never ask for NR 1 / 2: setup_tile512): 24.
+// key = mode << 6 | (nr - 1) << 4 | xa << 3 | pre << 2 | odd << 1 | unal; a key without an instantiation holds nullptr ----
+using S16Kernel = void (*)(Logmel512Params);
+#define MM_S16_KEYS 192
+template <int KEY>
+static constexpr S16Kernel s16_entry() {
+  constexpr int MODE = KEY >> 6, NR = ((KEY >> 4) & 3) + 1;
+  constexpr bool XA = (KEY & 8) != 0, PRE = (KEY & 4) != 0, ODD = (KEY & 2) != 0, UNAL = (KEY & 1) != 0;
+  if constexpr (NR < 3 && (XA || PRE)) return nullptr;
+  else return logmel512s_kernel<MODE, NR, PRE, ODD, UNAL, XA>;
 }
-
-template <int NR, bool XA>
-static void launch_s16_n(int mode, bool pre, bool odd, bool unal, dim3 grid, size_t lds, hipStream_t st, const Logmel512Params& q) {
-  if (mode == 0) launch_s16_mn<0, NR, XA>(pre, odd, unal, grid, lds, st, q);
-  else if (mode == 1) launch_s16_mn<1, NR, XA>(pre, odd, unal, grid, lds, st, q);
-  else launch_s16_mn<2, NR, XA>(pre, odd, unal, grid, lds, st, q);
+template <int... KEY>
+static S16Kernel s16_lookup(int key, std::integer_sequence<int, KEY...>) {
+  static constexpr S16Kernel table[] = {s16_entry<KEY>()...};
+  return table[key];
 }
+static S16Kernel s16_kernel(int key) { return s16_lookup(key, std::make_integer_sequence<int, MM_S16_KEYS>()); }
 
 void launch_s16(int mode, int nr, bool xa, bool pre, bool odd, bool unal, dim3 grid, size_t lds, hipStream_t st,
                 const Logmel512Params& q) {
   if (mode == 1 && q.out_mod != nullptr) mode = 2;        // clip mode (fused tail); 2 may also be asked for directly (n_mod 0)
-  switch (nr) {
-    case 1: launch_s16_n<1, false>(mode, pre, odd, unal, grid, lds, st, q); break;
-    case 2: launch_s16_n<2, false>(mode, pre, odd, unal, grid, lds, st, q); break;
-    case 3:
-      if (xa) launch_s16_n<3, true>(mode, pre, odd, unal, grid, lds, st, q);
-      else launch_s16_n<3, false>(mode, pre, odd, unal, grid, lds, st, q);
-      break;
-    default:
-      if (xa) launch_s16_n<4, true>(mode, pre, odd, unal, grid, lds, st, q);
-      else launch_s16_n<4, false>(mode, pre, odd, unal, grid, lds, st, q);
-      break;
-  }
-}
-
-template <int MODE, int NR, bool XA>
-static bool set_s16_attr_mn(int bytes) {
-  constexpr int NRP = NR < 3 ? 3 : NR;
-  const void* fn[8] = {(const void*)logmel512s_kernel<MODE, NR, false, false, false, XA>, (const void*)logmel512s_kernel<MODE, NR, false, false, true, XA>,
-                       (const void*)logmel512s_kernel<MODE, NR, false, true, false, XA>, (const void*)logmel512s_kernel<MODE, NR, false, true, true, XA>,
-                       (const void*)logmel512s_kernel<MODE, NRP, true, false, false, XA>, (const void*)logmel512s_kernel<MODE, NRP, true, false, true, XA>,
-                       (const void*)logmel512s_kernel<MODE, NRP, true, true, false, XA>, (const void*)logmel512s_kernel<MODE, NRP, true, true, true, XA>};
-  for (int i = 0; i < 8; ++i)
-    if (hipFuncSetAttribute(fn[i], hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
-  return true;
+  mode = mode == 0 || mode == 1 ? mode : 2;
+  nr = nr >= 1 && nr <= 3 ? nr : 4;
+  if (nr < 3) { xa = false; pre = false; }
+  const int key = mode << 6 | (nr - 1) << 4 | (xa ? 8 : 0) | (pre ? 4 : 0) | (odd ? 2 : 0) | (unal ? 1 : 0);
+  hipLaunchKernelGGL(s16_kernel(key), grid, dim3(1024), lds, st, q);
 }
 
 bool set_s16_attr(int bytes) {
-  return set_s16_attr_mn<0, 1, false>(bytes) && set_s16_attr_mn<1, 1, false>(bytes) && set_s16_attr_mn<2, 1, false>(bytes) &&
-         set_s16_attr_mn<0, 2, false>(bytes) && set_s16_attr_mn<1, 2, false>(bytes) && set_s16_attr_mn<2, 2, false>(bytes) &&
-         set_s16_attr_mn<0, 3, false>(bytes) && set_s16_attr_mn<1, 3, false>(bytes) && set_s16_attr_mn<2, 3, false>(bytes) &&
-         set_s16_attr_mn<0, 4, false>(bytes) && set_s16_attr_mn<1, 4, false>(bytes) && set_s16_attr_mn<2, 4, false>(bytes) &&
-         set_s16_attr_mn<0, 3, true>(bytes) && set_s16_attr_mn<1, 3, true>(bytes) && set_s16_attr_mn<2, 3, true>(bytes) &&
-         set_s16_attr_mn<0, 4, true>(bytes) && set_s16_attr_mn<1, 4, true>(bytes) && set_s16_attr_mn<2, 4, true>(bytes);
+  for (int key = 0; key < MM_S16_KEYS; ++key)
+    if (s16_kernel(key) &&
+        hipFuncSetAttribute((const void*)s16_kernel(key), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
+      return false;
+  return true;
 }

@@ -20,16 +20,6 @@
 #define MM_W16_LT_PITCH 84
 #define MM_W16_TAB_OFF (MM_W16_LT_OFF + 16 * MM_W16_LT_PITCH * 4)
 
-__device__ __forceinline__ void w16_read16(float2 (&v)[16], const float* src) {
-  const float4* s4 = reinterpret_cast<const float4*>(src);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const float4 t = s4[i];
-    v[2 * i] = make_float2(t.x, t.y);
-    v[2 * i + 1] = make_float2(t.z, t.w);
-  }
-}
-
 
 template <int MODE>
 __global__ __launch_bounds__(1024) void logmel512w_kernel(Logmel512Params p) {
@@ -40,6 +30,7 @@ __global__ __launch_bounds__(1024) void logmel512w_kernel(Logmel512Params p) {
   float* exf = reinterpret_cast<float*>(smem + MM_W16_EX_OFF) + wave * MM_W16_EX_FLOATS;
   const int q = lane & 15, row = lane >> 4;
   const float* lt = reinterpret_cast<const float*>(smem + MM_W16_LT_OFF) + q * MM_W16_LT_PITCH;
+  const Tile512ExP20 ex(exf, row, q);
 
   for (int i = threadIdx.x; i < 16 * MM_W16_LT_PITCH; i += 1024)
     reinterpret_cast<float*>(smem + MM_W16_LT_OFF)[i] = p.lane_tab[i];
@@ -73,76 +64,23 @@ __global__ __launch_bounds__(1024) void logmel512w_kernel(Logmel512Params p) {
     if (++ntl == tpc) { ntl = 0; ++nb; }
     // ---------------- phase A: one item per wave ----------------
     if (!item.interior) lm_mask_edge(x, p, item, row, q);
-    {
-      float2 w[16];
-      w16_read16(w, lt);                       // window
-#pragma unroll
-      for (int n1 = 0; n1 < 16; ++n1) { x[n1].x *= w[n1].x; x[n1].y *= w[n1].y; }
-    }
+    tile512_window(x, lt);
     MM_STAMP_AT(0)
     f16::dft16(x);
     MM_STAMP_AT(1)
-    {
-      float2 w[16];
-      w16_read16(w, lt + 32);                  // W_256^(q*k1), k1 = 1..15 in w[0..14]
-#pragma unroll
-      for (int k1 = 1; k1 < 16; ++k1) x[f16::P16(k1)] = f16::cmulf(x[f16::P16(k1)], w[k1 - 1]);
-    }
+    tile512_twiddle(x, lt + MM_LT_TW);
     MM_STAMP_AT(2)
-    {
-      float* wr = exf + row * 320 + q;
-      const float4* rd = reinterpret_cast<const float4*>(exf + row * 320 + q * 20);
-#pragma unroll
-      for (int k1 = 0; k1 < 16; ++k1) wr[k1 * 20] = x[f16::P16(k1)].x;
-      wave_lds_sync();
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float4 v = rd[i];
-        x[4 * i].x = v.x; x[4 * i + 1].x = v.y; x[4 * i + 2].x = v.z; x[4 * i + 3].x = v.w;
-      }
-      wave_lds_sync();
-      // imaginary parts are still in stage-1 order: x[P16(k1)].y
-      float im[16];
-#pragma unroll
-      for (int k1 = 0; k1 < 16; ++k1) im[k1] = x[f16::P16(k1)].y;
-#pragma unroll
-      for (int k1 = 0; k1 < 16; ++k1) wr[k1 * 20] = im[k1];
-      wave_lds_sync();
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float4 v = rd[i];
-        x[4 * i].y = v.x; x[4 * i + 1].y = v.y; x[4 * i + 2].y = v.z; x[4 * i + 3].y = v.w;
-      }
-      wave_lds_sync();
-    }
+    tile512_exchange(x, ex);
     MM_STAMP_AT(10)
     f16::dft16(x);
     MM_STAMP_AT(3)
     {
-      float2 pb[9];
+      float2 pb[9], wp[8];
       f16::fetch_partners<1>(x, pb, lane, q);
-      float2 wp[8];
-      {
-        const float4* s4 = reinterpret_cast<const float4*>(lt + 64);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float4 t = s4[i];
-          wp[2 * i] = make_float2(t.x, t.y);
-          wp[2 * i + 1] = make_float2(t.z, t.w);
-        }
-      }
-      float* pr = P + (4 * wave + row) * MM_LM_PITCH;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float2 xa, xb;
-        f16::split_pair(x[f16::P16(j)], pb[j], wp[j], xa, xb);
-        pr[q + 16 * j] = fmaf(xa.x, xa.x, xa.y * xa.y);
-        pr[256 - q - 16 * j] = fmaf(xb.x, xb.x, xb.y * xb.y);
-      }
-      if (q == 0) {
-        const float2 zm = x[f16::P16(8)];
-        pr[128] = fmaf(zm.x, zm.x, zm.y * zm.y);
-      }
+      tile512_read_wp(wp, lt);
+      float pw[17];
+      tile512_split_power(x, pb, wp, pw);
+      tile512_store_power_row<false>(P + (4 * wave + row) * MM_LM_PITCH, q, pw);
     }
     MM_STAMP_AT(4)
     // next tile's samples: in flight during the mel phase
@@ -153,13 +91,7 @@ __global__ __launch_bounds__(1024) void logmel512w_kernel(Logmel512Params p) {
     MM_STAMP_AT(6)
     // ---------------- phase B ----------------
     if (MODE == 0) {
-      for (int r = wave; r < 64; r += 16) {
-        if (t0 + r < p.n_frames) {
-          float* o = p.out_power + (((int64_t)b * p.n_frames) + t0 + r) * 257;
-          const float* src = P + r * MM_LM_PITCH;
-          for (int k = lane; k < 257; k += 64) o[k] = src[k];
-        }
-      }
+      tile512_store_power_tile(p.out_power, P, MM_LM_PITCH, b, t0, p.n_frames, wave, 16, lane);
     } else {
       const bool valid = (t0 + lane) < p.n_frames;
       // filters are emitted in increasing order starting at m0: a running row pointer
@@ -171,25 +103,12 @@ __global__ __launch_bounds__(1024) void logmel512w_kernel(Logmel512Params p) {
       if (run0 < run1) {
         float4 h = hdr[run0];
         for (int r = run0; r < run1; ++r) {
-          const int k4 = __builtin_amdgcn_readfirstlane(__float_as_int(h.x));
-          const int ng = __builtin_amdgcn_readfirstlane(__float_as_int(h.y));
-          const int go = __builtin_amdgcn_readfirstlane(__float_as_int(h.z));
-          const int dd = __builtin_amdgcn_readfirstlane(__float_as_int(h.w));
+          const Tile512Run rh = tile512_run_header(h);
           if (r + 1 < run1) h = hdr[r + 1];
-          const float4* pp = reinterpret_cast<const float4*>(pl + k4);
-          const float4* gw = grp + 2 * go;
           float sa = 0.0f, sb = 0.0f;
-#pragma unroll 2
-          for (int g = 0; g < ng; ++g) {
-            const float4 pv = pp[g], wa = gw[2 * g], wb = gw[2 * g + 1];   // (wlo, whi) of bins 0,1 | 2,3
-            sa = fmaf(wa.x, pv.x, sa); sb = fmaf(wa.y, pv.x, sb);
-            sa = fmaf(wa.z, pv.y, sa); sb = fmaf(wa.w, pv.y, sb);
-            sa = fmaf(wb.x, pv.z, sa); sb = fmaf(wb.y, pv.z, sb);
-            sa = fmaf(wb.z, pv.w, sa); sb = fmaf(wb.w, pv.w, sb);
-          }
-          if (dd >= m0) {
-            const float v = carry + sa;
-            const float db = 3.0102999566398120f * __builtin_amdgcn_logf(fmaxf(p.amin, v)) - p.db_offset;
+          tile512_group_dot<2>(reinterpret_cast<const float4*>(pl + rh.k4), grp + 2 * rh.go, rh.ng, sa, sb);
+          if (rh.dd >= m0) {
+            const float db = tile512_db(fmaxf(p.amin, carry + sa), p.db_offset);
             if (valid) {
               *o = db;
               vmax = fmaxf(vmax, db);
