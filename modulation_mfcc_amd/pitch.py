@@ -225,12 +225,27 @@ def _as_signal(audio):
         raise ValueError("audio must be [n] or [B, n]")
     if x.dtype not in (torch.float32, torch.float64):
         x = x.to(torch.float64)
-    if x.stride(1) != 1:
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        # the library takes a row pitch >= n: an expand()ed row (pitch 0) or overlapping rows are copied
         x = x.contiguous()
     return x, squeeze
 
 
+def _row_pitch(x):
+    """Elements between the rows of [B, n] as the kernels want it (>= n; the stride of a single row says nothing)."""
+    return x.stride(0) if x.shape[0] > 1 else x.shape[1]
+
+
 _TORCH_PAD = {"reflect": "reflect", "edge": "replicate", "wrap": "circular"}
+
+
+def _pad_center(x, frame_length, pad_mode):
+    """np.pad(x, frame_length // 2, mode=pad_mode) of every row of [B, n], on the device."""
+    import torch
+    if pad_mode not in _TORCH_PAD:
+        raise NotImplementedError(f"pad_mode={pad_mode!r}: the device path pads 'constant', 'reflect', 'edge', 'wrap'")
+    h = frame_length // 2
+    return torch.nn.functional.pad(x.unsqueeze(1), (h, h), mode=_TORCH_PAD[pad_mode]).squeeze(1).contiguous()
 
 
 def pyin_batch(audio, sr, *, fmin, fmax, frame_length=2048, win_length=None, hop_length=None, n_thresholds=100,
@@ -244,10 +259,7 @@ def pyin_batch(audio, sr, *, fmin, fmax, frame_length=2048, win_length=None, hop
     from . import _lib
     x, squeeze = _as_signal(audio)
     if center and pad_mode != "constant":
-        if pad_mode not in _TORCH_PAD:
-            raise NotImplementedError(f"pad_mode={pad_mode!r}: the device path pads 'constant', 'reflect', 'edge', 'wrap'")
-        h = frame_length // 2
-        x = torch.nn.functional.pad(x.unsqueeze(1), (h, h), mode=_TORCH_PAD[pad_mode]).squeeze(1).contiguous()
+        x = _pad_center(x, frame_length, pad_mode)
         center = False
     B, n = x.shape
     p, z = pyin_params(n, sr, fmin=fmin, fmax=fmax, frame_length=frame_length, win_length=win_length,
@@ -274,7 +286,7 @@ def pyin_batch(audio, sr, *, fmin, fmax, frame_length=2048, win_length=None, hop
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         for r0 in range(0, B, rows):
             r = min(rows, B - r0)
-            _lib.check(fn(C.byref(p), C.byref(tabs.c), x[r0].data_ptr(), r, n, x.stride(0), f0[r0].data_ptr(),
+            _lib.check(fn(C.byref(p), C.byref(tabs.c), x[r0].data_ptr(), r, n, _row_pitch(x), f0[r0].data_ptr(),
                           voiced[r0].data_ptr(), vprob[r0].data_ptr(), states[r0].data_ptr(), ws.data_ptr(), ws.numel(),
                           stream), name)
     if fill_na is None:                 # librosa keeps the decoded bin's frequency on unvoiced frames
@@ -295,7 +307,7 @@ def pyin_cmnd(audio, sr, *, fmin, fmax, frame_length=2048, win_length=None, hop_
     out = torch.empty((B, z["n_frames"], z["max_period"] - z["min_period"] + 1), dtype=torch.float64, device=x.device)
     with torch.cuda.device(x.device):
         _lib.check(_lib.load().mm_pyin_cmnd(C.byref(p), x.data_ptr(), 0 if x.dtype == torch.float32 else 1, B, n,
-                                            x.stride(0), out.data_ptr(),
+                                            _row_pitch(x), out.data_ptr(),
                                             C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), "mm_pyin_cmnd")
     return out[0] if squeeze else out
 
