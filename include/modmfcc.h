@@ -24,6 +24,8 @@
  *                             |scipy.signal.hilbert| -- row N3
  *   mm_pcm_decode_f32,
  *   mm_resample_f32        <- librosa.load(path, sr=sigSr, mono=False) (script/mfcc.py:284,373) -- row N4
+ *   mm_find_peaks          <- MinMaxFinder (script/calc.py:651-686; script/main.py:1546-1613):
+ *                             scipy.signal.find_peaks(y) / find_peaks(-y) on a batch of curves
  *   mm_build_window/mel/dct<- scipy.signal.get_window('hann'), librosa.filters.mel,
  *                             scipy.fftpack.dct(type=2, norm='ortho') constant tables
  *
@@ -406,6 +408,30 @@ int mm_pyin_f64(const mm_pyin_params* p, const mm_pyin_tables* t, const double* 
  * only when the strides are equal. */
 int mm_interp_nan_linear_f64(const double* d_x, int64_t rows, int64_t n, int64_t x_stride, double* d_y, int64_t y_stride,
                              void* stream);
+
+/* ---- peaks and troughs (MinMaxFinder, script/calc.py:651-686: scipy.signal.find_peaks) --------------- */
+/* Conditions of one call, each an interval [min, max] with -INFINITY / +INFINITY for an open side (scipy's None:
+ * that side is not tested); an interval counts only when its use_ flag is set.  negate: the peaks of -x (troughs). */
+typedef struct mm_peaks_opts {
+  double height[2];        /* x[p] (of -x when negate)                                                  */
+  double threshold[2];     /* min(x[p] - x[p-1], x[p] - x[p+1]) >= [0], max(...) <= [1]; NaN propagates  */
+  double prominence[2];    /* scipy's peak_prominences with wlen=None                                   */
+  int32_t negate, use_height, use_threshold, use_prominence;
+} mm_peaks_opts;
+
+/* scipy.signal.find_peaks of rows x n curves (dtype 0 = float32, promoted per element, 1 = float64; [rows][x_stride],
+ * x_stride >= n), conditions applied in scipy's order: height, threshold, prominence.  d_lo / d_hi (int32 [rows],
+ * either may be NULL = 0 / n; clamped to 0 <= lo <= hi <= n) restrict row r to the slice x[lo:hi]: indices and bases
+ * are relative to lo, the slice's ends are never peaks, the prominence scan stays inside it.
+ * d_count [rows] = the TRUE number of peaks; d_idx [rows][cap] = their plateau midpoints, ascending, -1 beyond
+ * min(count, cap) (peaks beyond cap are dropped, never written).  cap = (n - 1) / 2 always suffices.  With
+ * use_prominence, d_prom (NaN-padded), d_lbase, d_rbase [rows][cap] are written too (NULL otherwise).
+ * Workspace: segment counts and the candidate list of the prominence pass (20 bytes per possible peak).
+ * MM_ERR_INVALID_ARG (NULL pointers, rows / n < 1, x_stride < n, NaN bounds) or MM_ERR_WORKSPACE before any launch. */
+size_t mm_find_peaks_workspace_bytes(int64_t rows, int64_t n);
+int mm_find_peaks(const mm_peaks_opts* opts, const void* d_x, int32_t dtype, int64_t rows, int64_t n, int64_t x_stride,
+                  const int32_t* d_lo, const int32_t* d_hi, int64_t cap, int32_t* d_count, int32_t* d_idx, double* d_prom,
+                  int32_t* d_lbase, int32_t* d_rbase, void* d_ws, size_t ws_bytes, void* stream);
 
 /* ---- per-kernel device timing (hipEvents on the launch stream) ------------------------- */
 /* on = 0: off; 1: every stage; otherwise a mask with bit (MM_STAGE_x + 1) set for each stage to time

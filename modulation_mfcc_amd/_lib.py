@@ -73,6 +73,13 @@ class mm_pyin_tables(C.Structure):
                                            "freqs")]
 
 
+class mm_peaks_opts(C.Structure):
+    _fields_ = [
+        ("height", C.c_double * 2), ("threshold", C.c_double * 2), ("prominence", C.c_double * 2),
+        ("negate", C.c_int32), ("use_height", C.c_int32), ("use_threshold", C.c_int32), ("use_prominence", C.c_int32),
+    ]
+
+
 class MMError(RuntimeError):
     def __init__(self, status, what, detail=""):
         self.status = status
@@ -150,6 +157,9 @@ PROTOTYPES = {
     "mm_pyin_f32": (C.c_int, [_pyp, _pyt, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "mm_pyin_f64": (C.c_int, [_pyp, _pyt, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "mm_interp_nan_linear_f64": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp]),
+    "mm_find_peaks_workspace_bytes": (C.c_size_t, [_i64, _i64]),
+    "mm_find_peaks": (C.c_int, [C.POINTER(mm_peaks_opts), _vp, C.c_int32, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp,
+                                _vp, _vp, _vp, C.c_size_t, _vp]),
     "mm_timing_enable": (C.c_int, [_vp, C.c_int]),
     "mm_timing_read": (C.c_int, [_vp, _vp, _vp]),
 }

@@ -3,7 +3,9 @@
 script/calc.py holds no MFCC arithmetic; what the north star names as the
 drop-in surface is ``applyFilter`` (script/calc.py:23-129), ``get_velocity`` (:593-650, applied by
 the UI to the MFCC-change curve, script/main.py:668-713) and the RMS / Hilbert amplitude envelope
-(:221-343), and the pYIN branch of ``get_f0`` with its ``interp_NAN`` (:345-592; modulation_mfcc_amd.pitch).  Praat-backed
+(:221-343), the pYIN branch of ``get_f0`` with its ``interp_NAN`` (:345-592; modulation_mfcc_amd.pitch) and
+``MinMaxFinder`` (:651-686: the peaks and troughs of a drawn curve, scipy.signal.find_peaks on the device --
+``find_peaks_batch`` for [rows, n] device curves).  Praat-backed
 functions (f0 by 'praatac' / 'praatcc', formants, RMSpraat) and the EMA reader are out of scope.
 """
 from __future__ import annotations
@@ -15,7 +17,7 @@ from .filters import applyFilter
 from .pitch import get_f0, interp_NAN  # noqa: F401
 
 __all__ = ["applyFilter", "get_f0", "interp_NAN", "get_velocity", "calculate_amplitude_envelope", "velocity_stencil", "velocity_batch", "apply_stencil",
-           "hilbert_envelope_batch", "amplitude_envelope_batch"]
+           "hilbert_envelope_batch", "amplitude_envelope_batch", "find_peaks_batch", "peaks_to_list", "MinMaxFinder"]
 
 
 def _is_device_tensor(x):
@@ -390,3 +392,192 @@ def get_velocity(x: np.ndarray, sr: float, difference: int = 1, method: str = "g
             x = np.gradient(x, 1 / sr)
         return x
     raise ValueError("Méthode inconnue. Utilisez 'gradient', 'sg' ou 'finDiff'.")
+
+
+FIND_PEAKS_SEGMENT = 1024       # samples per workgroup of the peak kernels (csrc/mm_peaks.hip: kPkThreads * kPkPer)
+
+
+def _peak_interval(name, v):
+    """scipy's _unpack_condition_args for scalar bounds: a number is the minimum, a pair is (min, max), None an open side."""
+    import math
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2:
+            raise ValueError(f"{name} must be a number or a (min, max) pair")
+        vmin, vmax = v
+    else:
+        vmin, vmax = v, None
+    out = []
+    for b, open_side in ((vmin, -math.inf), (vmax, math.inf)):
+        if b is None:
+            out.append(open_side)
+            continue
+        if isinstance(b, bool) or not isinstance(b, (int, float, np.integer, np.floating)):
+            raise TypeError(f"{name}: bounds must be real numbers or None (per-sample arrays are not supported)")
+        if math.isnan(float(b)):
+            raise ValueError(f"{name}: bounds must not be NaN")
+        out.append(float(b))
+    return out
+
+
+def _peak_range(name, v, rows, n, device):
+    """lo / hi of find_peaks_batch as an int32 device tensor [rows] (None stays None)."""
+    import torch
+    if v is None:
+        return None
+    if isinstance(v, torch.Tensor):
+        if v.dtype not in (torch.int32, torch.int64) or v.numel() != rows:
+            raise TypeError(f"{name} must be an int32 / int64 tensor with one entry per row")
+        return v.reshape(rows).to(device=device, dtype=torch.int32).contiguous()
+    a = np.asarray(v)
+    if a.dtype.kind not in "iu":
+        raise TypeError(f"{name} must be an integer, a sequence of integers or an integer tensor")
+    a = np.broadcast_to(a.astype(np.int64), (rows,)) if a.ndim == 0 else a.astype(np.int64).reshape(-1)
+    if a.shape != (rows,):
+        raise ValueError(f"{name} must have one entry per row")
+    if (a < 0).any() or (a > n).any():
+        raise ValueError(f"{name} must lie in [0, n]")
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(device)
+
+
+def find_peaks_batch(x, *, negate=False, height=None, threshold=None, prominence=None, lo=None, hi=None):
+    """scipy.signal.find_peaks along the LAST axis of a float64 / float32 CUDA(HIP) tensor [rows, n] (or [n]) on the
+    device (mm_find_peaks) -- e.g. on the [B, T] output of MfccPlan.mfcc_change, velocity_batch or pyin_batch.
+
+    Returns ``(idx, count, props)``, all on the device, nothing synchronised: ``idx`` int32 [rows, cap] holds each row's
+    peak indices ascending, padded with -1, ``count`` int32 [rows] their number, ``cap = max(0, (n - 1) // 2)`` the most a
+    row can have.  Indices, bases and prominences equal scipy's bit for bit (float32 input is promoted to float64 per
+    element, as scipy does).
+
+    ``negate=True`` finds the peaks of ``-x`` (the troughs) without a negated copy; heights, thresholds and prominences
+    are then those of ``-x``, as ``find_peaks(-x, ...)`` returns them.  ``height``, ``threshold`` and ``prominence`` are
+    a minimum, or ``(min, max)`` with ``None`` for an open side, applied in scipy's order; ``props`` holds
+    ``peak_heights``, ``left_thresholds`` / ``right_thresholds``, ``prominences`` / ``left_bases`` / ``right_bases``,
+    each exactly when scipy returns it, shaped like ``idx`` (NaN / -1 beyond the count).  ``lo`` / ``hi`` (an integer, one
+    per row, or an integer tensor; tensors are clamped to 0 <= lo <= hi <= n on the device) restrict row r to
+    ``x[r, lo:hi]``: the result is scipy's on that slice, indices relative to ``lo``.  ``distance``, ``width``, ``wlen``
+    and ``plateau_size`` are not offered.  A 1-D input gives 1-D outputs."""
+    import ctypes as C
+    import math
+    import torch
+    from . import _lib
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype in (torch.float64, torch.float32)):
+        raise TypeError("x must be a float64 (or float32) CUDA(HIP) tensor")
+    squeeze = x.dim() == 1
+    x2 = x.unsqueeze(0) if squeeze else x
+    if x2.dim() != 2:
+        raise ValueError("x must be [n] or [rows, n]")
+    o = _lib.mm_peaks_opts()
+    o.negate = 1 if negate else 0
+    for name, v, field in (("height", height, o.height), ("threshold", threshold, o.threshold),
+                           ("prominence", prominence, o.prominence)):
+        field[0], field[1] = _peak_interval(name, v) if v is not None else (-math.inf, math.inf)
+        setattr(o, "use_" + name, 0 if v is None else 1)
+    rows, n = x2.shape
+    if (x2.stride(1) != 1 and n > 1) or (rows > 1 and x2.stride(0) < n):
+        x2 = x2.contiguous()
+    dev = x2.device
+    d_lo, d_hi = _peak_range("lo", lo, rows, n, dev), _peak_range("hi", hi, rows, n, dev)
+    cap = max(0, (n - 1) // 2)
+    idx = torch.empty((rows, cap), dtype=torch.int32, device=dev)
+    count = torch.zeros((rows,), dtype=torch.int32, device=dev)
+    props = {}
+    prom = lb = rb = None
+    if prominence is not None:
+        prom = torch.empty((rows, cap), dtype=torch.float64, device=dev)
+        lb = torch.empty((rows, cap), dtype=torch.int32, device=dev)
+        rb = torch.empty((rows, cap), dtype=torch.int32, device=dev)
+    if rows > 0 and n > 0:
+        lib = _lib.load()
+        stride = x2.stride(0) if rows > 1 else max(n, x2.stride(0))
+        ws = torch.empty(int(lib.mm_find_peaks_workspace_bytes(rows, n)), dtype=torch.uint8, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None   # noqa: E731
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        with torch.cuda.device(dev):
+            _lib.check(lib.mm_find_peaks(C.byref(o), x2.data_ptr(), 0 if x2.dtype == torch.float32 else 1, rows, n, stride,
+                                         ptr(d_lo), ptr(d_hi), cap, count.data_ptr(), ptr(idx), ptr(prom), ptr(lb),
+                                         ptr(rb), ws.data_ptr(), ws.numel(), stream), "mm_find_peaks")
+    if height is not None or threshold is not None:
+        # x[p], x[p] - x[p -+ 1]: gathers of the input at the indices the kernel returned, the same float64 differences
+        ok = idx >= 0
+        at = idx.long().clamp_(min=0)
+        if d_lo is not None:
+            at += d_lo.long().clamp_(0, n)[:, None]            # the kernel's clamp of a tensor lo
+        nan = torch.full((), math.nan, dtype=torch.float64, device=dev)
+
+        def val(off):
+            v = x2.gather(1, (at + off).clamp_(0, max(n - 1, 0))).double() if cap else x2.new_empty((rows, 0)).double()
+            return -v if negate else v
+        if height is not None:
+            props["peak_heights"] = torch.where(ok, val(0), nan)
+        if threshold is not None:
+            props["left_thresholds"] = torch.where(ok, val(0) - val(-1), nan)
+            props["right_thresholds"] = torch.where(ok, val(0) - val(1), nan)
+    if prominence is not None:
+        props["prominences"], props["left_bases"], props["right_bases"] = prom, lb, rb
+    if squeeze:
+        return idx[0], count[0], {k: v[0] for k, v in props.items()}
+    return idx, count, props
+
+
+def peaks_to_list(idx, count):
+    """``(idx, count)`` of find_peaks_batch -> a list with one int32 device tensor per row, trimmed to its count (a 1-D
+    pair gives one tensor).  Copies ``count`` to the host: this SYNCHRONISES the device once."""
+    if idx.dim() == 1:
+        return idx[:int(count.item())]
+    return [idx[r, :c] for r, c in enumerate(count.tolist())]
+
+
+class MinMaxFinder:
+    """script/calc.py:651-686: the minima / maxima of a drawn curve inside a time interval.  The peak search
+    (scipy.signal.find_peaks(values) / find_peaks(-values)) runs on the device (find_peaks_batch).  numpy / list input is
+    masked on the host as the reference does and returns numpy arrays; CUDA(HIP) tensors for ``x`` and ``y`` are masked
+    on the device and return device tensors.  There is no CPU fallback."""
+
+    def find_in_interval(self, times, values, interval):
+        """The samples whose time lies in ``start <= t <= end``: ``(times, values)`` as numpy arrays for host input, as
+        device tensors when both are CUDA(HIP) tensors.  One device tensor beside host data is a TypeError."""
+        start, end = interval
+        on_device = _is_device_tensor(times), _is_device_tensor(values)
+        if any(on_device):
+            if not all(on_device):
+                raise TypeError("times and values must both be host data or both CUDA(HIP) tensors")
+            keep = (times >= start) & (times <= end)
+            return times[keep], values[keep]
+        t, v = np.asarray(times), np.asarray(values)
+        m = min(t.shape[0], v.shape[0]) if t.ndim and v.ndim else 0     # pairs, as far as the shorter one goes
+        t, v = t[:m], v[:m]
+        keep = (t >= start) & (t <= end) if m else np.zeros(0, dtype=bool)
+        return t[keep], v[keep]
+
+    def _analyse(self, x, y, interval, negate):
+        if interval is None:
+            print("No interval specified.")
+            return [], []
+        import torch
+        interval_times, interval_values = self.find_in_interval(x, y, interval)
+        on_device = _is_device_tensor(interval_values)
+        if on_device:
+            d = interval_values if interval_values.dtype in (torch.float32, torch.float64) else interval_values.double()
+        else:
+            if not torch.cuda.is_available():
+                raise RuntimeError("modulation_mfcc_amd needs an AMD GPU (gfx950); there is no CPU fallback")
+            if interval_values.size == 0:
+                return [], []
+            # scipy.signal.find_peaks converts its argument to float64
+            d = torch.from_numpy(np.ascontiguousarray(interval_values, dtype=np.float64)).cuda()
+        if d.numel() == 0:
+            return [], []
+        peaks = peaks_to_list(*find_peaks_batch(d.reshape(-1), negate=negate)[:2])
+        if len(peaks) == 0:
+            return [], []
+        if on_device:
+            peaks = peaks.long()
+            return interval_times[peaks], interval_values[peaks]
+        peaks = peaks.cpu().numpy()
+        return interval_times[peaks], interval_values[peaks]
+
+    def analyse_minimum(self, x, y, interval):
+        return self._analyse(x, y, interval, True)
+
+    def analyse_maximum(self, x, y, interval):
+        return self._analyse(x, y, interval, False)

@@ -6,3 +6,4 @@
 #include "mm_tail.hip"
 #include "mm_side.hip"
 #include "mm_pitch.hip"
+#include "mm_peaks.hip"
