@@ -170,29 +170,7 @@ __global__ __launch_bounds__(MM_M12_THREADS) void logmel12m_kernel(Logmel12mPara
     for (int j = 0; j < NR; ++j) {
       const int gi = 4 * ((int)threadIdx.x + MM_M12_THREADS * j);
       const int s0 = first + 4 * MM_M12_THREADS * j;
-      const bool ok = s0 >= 0 && s0 < n;       // !UNAL: groups never straddle a clip edge (n % 4 == 0)
-      float4 v = sreg[DMA ? 0 : j];
-      if (UNAL) {      // the group that straddles the clip end was loaded k samples early (address clamped to n - 4)
-        const int k = s0 - (n - 4);
-        if (k > 0) {
-          const float4 l = v;
-          v.x = k == 1 ? l.y : (k == 2 ? l.z : l.w);
-          v.y = k == 1 ? l.z : l.w;
-          v.z = l.w;
-        }
-      }
-      if (PRE) {
-        const float pv = s0 > 0 ? sprev[j] : 0.0f;
-        const float4 r = v;
-        v.x = r.x - __fmul_rn(p.preemph, pv); v.y = r.y - __fmul_rn(p.preemph, r.x);
-        v.z = r.z - __fmul_rn(p.preemph, r.y); v.w = r.w - __fmul_rn(p.preemph, r.z);
-      }
-      if (UNAL) {
-        v.x = ok ? v.x : 0.0f; v.y = (ok && s0 + 1 < n) ? v.y : 0.0f;
-        v.z = (ok && s0 + 2 < n) ? v.z : 0.0f; v.w = (ok && s0 + 3 < n) ? v.w : 0.0f;
-      } else {
-        v.x = ok ? v.x : 0.0f; v.y = ok ? v.y : 0.0f; v.z = ok ? v.z : 0.0f; v.w = ok ? v.w : 0.0f;
-      }
+      const float4 v = tile512_stage_fix<PRE, UNAL>(sreg[DMA ? 0 : j], s0, n, sprev[PRE ? j : 0], p.preemph);
       if (gi < p.s_floats) *reinterpret_cast<float4*>(S + gi) = v;
     }
   };
@@ -407,7 +385,7 @@ __global__ __launch_bounds__(MM_M12_THREADS) void logmel12m_kernel(Logmel12mPara
           for (int r = 0; r < 4; ++r) {
             const int m = mblk * 16 + 4 * g + r;
             const float v = acc0[r] + acc1[r];
-            L[r] = 3.0102999566398120f * __builtin_amdgcn_logf(fmaxf(p.amin, v)) - p.db_offset;
+            L[r] = tile512_db(fmaxf(p.amin, v), p.db_offset);
             if (tv && m < p.n_mels) {
               if (p.out_logmel) p.out_logmel[((int64_t)mb_clip * p.n_mels + m) * T + t] = L[r];
               vmax = fmaxf(vmax, L[r]);

@@ -489,6 +489,8 @@ __device__ __forceinline__ void s16_ex_store(unsigned m0v, const float (&v)[16])
       : "memory");
 }
 
+// From mm_tile512.hip.inc this kernel takes the lane-record offsets, the split-twiddle read and the MODE 0 tile store; the
+// rest of phase A and the mel walk stay on its own code (docs/experiments.md, "S16 over the shared tile pieces").
 template <int MODE, int NR, bool PRE, bool ODD, bool UNAL, bool XA>
 __global__ __launch_bounds__(1024) void logmel512s_kernel(Logmel512Params p) {
   static_assert(!XA || NR >= 3, "the addtid exchange exists for NR 3 / 4 only");
@@ -718,31 +720,10 @@ __global__ __launch_bounds__(1024) void logmel512s_kernel(Logmel512Params p) {
     stage_store(tl);
   }
   __syncthreads();
-  // the split partners come through DPP now, which leaves ~40 VGPRs under the 128 of 4 waves/SIMD:
-  // the split twiddles and the first MM_S16_TW_REG stage-1 twiddles stay in registers for the
-  // whole launch (every ds_read_b128 of a per-lane constant costs the LDS pipe ~6 cycles per item)
-  float2 twr[MM_S16_TW_REG > 0 ? MM_S16_TW_REG : 1];
-#if MM_S16_WP_REG
+  // the split partners come through DPP, which leaves ~40 VGPRs under the 128 of 4 waves/SIMD: the split twiddles stay
+  // in registers for the whole launch (every ds_read_b128 of a per-lane constant costs the LDS pipe ~6 cycles per item)
   float2 wp[8];
-#endif
-  {
-#if MM_S16_WP_REG
-    const float4* s4 = reinterpret_cast<const float4*>(lt + 64);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float4 t = s4[i];
-      wp[2 * i] = make_float2(t.x, t.y);
-      wp[2 * i + 1] = make_float2(t.z, t.w);
-    }
-#endif
-    const float4* t4 = reinterpret_cast<const float4*>(lt + 32);
-#pragma unroll
-    for (int i = 0; i < MM_S16_TW_REG / 2; ++i) {
-      const float4 t = t4[i];
-      twr[2 * i] = make_float2(t.x, t.y);
-      twr[2 * i + 1] = make_float2(t.z, t.w);
-    }
-  }
+  tile512_read_wp(wp, lt);
 
   MM_STAMP_BEGIN(16)
   for (int tile = tile_begin; tile < tile_end; ++tile) {
@@ -796,18 +777,18 @@ __global__ __launch_bounds__(1024) void logmel512s_kernel(Logmel512Params p) {
     }
     MM_STAMP_AT(1)
     {
-      // W_256^(q*k1), k1 = 1..15: the first MM_S16_TW_REG from registers, the rest from the lane record
+      // W_256^(q*k1), k1 = 1..15, from the lane record
       float2 w[16];
-      const float4* t4 = reinterpret_cast<const float4*>(lt + 32);
+      const float4* t4 = reinterpret_cast<const float4*>(lt + MM_LT_TW);
 #pragma unroll
-      for (int i = MM_S16_TW_REG / 2; i < 8; ++i) {
+      for (int i = 0; i < 8; ++i) {
         const float4 t = t4[i];
         w[2 * i] = make_float2(t.x, t.y);
         w[2 * i + 1] = make_float2(t.z, t.w);
       }
 #pragma unroll
       for (int k1 = 1; k1 < 16; ++k1)
-        x[f16::P16(k1)] = f16::cmulf(x[f16::P16(k1)], (k1 - 1 < MM_S16_TW_REG) ? twr[(k1 - 1) % (MM_S16_TW_REG > 0 ? MM_S16_TW_REG : 1)] : w[k1 - 1]);
+        x[f16::P16(k1)] = f16::cmulf(x[f16::P16(k1)], w[k1 - 1]);
     }
     MM_STAMP_AT(2)
     {
@@ -859,18 +840,6 @@ __global__ __launch_bounds__(1024) void logmel512s_kernel(Logmel512Params p) {
     {
       float2 pb[9];
       f16::fetch_partners<1>(x, pb, lane, q);
-#if !MM_S16_WP_REG
-      float2 wp[8];
-      {
-        const float4* s4 = reinterpret_cast<const float4*>(lt + 64);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float4 t = s4[i];
-          wp[2 * i] = make_float2(t.x, t.y);
-          wp[2 * i + 1] = make_float2(t.z, t.w);
-        }
-      }
-#endif
       float* pr = P + (4 * wave + row) * MM_S16_PITCH(XA);
       // every lane of the frame has finished reading the exchange area (in-order LDS, one wave)
       // before any of its power values is written over it
@@ -915,13 +884,7 @@ __global__ __launch_bounds__(1024) void logmel512s_kernel(Logmel512Params p) {
     MM_STAMP_AT(5)
     // ---------------- phase B ----------------
     if (MODE == 0) {
-      for (int r = wave; r < 64; r += 16) {
-        if (t0 + r < p.n_frames) {
-          float* o = p.out_power + (((int64_t)b * p.n_frames) + t0 + r) * 257;
-          const float* src = P + r * MM_S16_PITCH(XA);
-          for (int k = lane; k < 257; k += 64) o[k] = src[k];
-        }
-      }
+      tile512_store_power_tile(p.out_power, P, MM_S16_PITCH(XA), b, t0, p.n_frames, wave, 16, lane);
     } else {
       const bool valid = (t0 + lane) < p.n_frames;
       float* o = p.out_logmel + ((int64_t)b * p.n_mels + m0) * p.n_frames + t0 + lane;

@@ -34,12 +34,6 @@ static_assert(1068 <= 4 * MM_S16_XA_PITCH && 15 * 4 * MM_S16_XA_PITCH * 4 < 6553
 #ifndef MM_S16F_W
 #define MM_S16F_W 0.5     // mel share of a DCT wave relative to the other waves
 #endif
-#ifndef MM_S16_TW_REG
-#define MM_S16_TW_REG 0    // stage-1 twiddles kept in registers (even, <= 14)
-#endif
-#ifndef MM_S16_WP_REG
-#define MM_S16_WP_REG 1    // split twiddles kept in registers
-#endif
 #define MM_S16_LT_OFF(NR, XA) (MM_S16_S_OFF(XA) + (NR) * 16384)
 #define MM_S16_TAB_OFF(NR, XA) (MM_S16_LT_OFF(NR, XA) + 16 * MM_W16_LT_PITCH * 4)
 

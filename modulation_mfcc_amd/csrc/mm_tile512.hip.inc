@@ -3,9 +3,9 @@
 // mm_logmel16w.hip.inc), logmel512h_kernel (H16, mm_logmel16h.hip.inc), logmel512s_kernel (S16, mm_logmel16s.hip.inc) and
 // logmel12m_kernel (M12, mm_logmel12m.hip.inc).  The five are the same arithmetic with different occupancy and staging
 // trades (tests/test_gpu_parity.py asserts bit-identical rows between them): what they share is said once, here.
-// W8, W16 and H16 are written with these pieces.  S16 and M12 still carry their own copies: written with the same pieces
-// their registers and spills stayed equal but their instruction schedule moved, and a moved schedule of the hot path wants
-// a measured A/B first (docs/experiments.md, "Shared pieces of the n_fft-512 tile kernels").
+// W8, W16 and H16 are written with these pieces.  S16 takes the record offsets, the split-twiddle read and the MODE 0 tile
+// store, M12 the staging fix-up and the dB conversion; the rest of those two is their own code: with the shared form their
+// registers change (M12) or the same-box A/B came out slower (S16; docs/experiments.md, "S16 over the shared tile pieces").
 // Included by mm_fft16.hip.inc behind namespace f16, which everything below builds on.
 
 // ---- lane record (one per lane q, pitch MM_W16_LT_PITCH floats in LDS): window pairs | stage-1 twiddles | split twiddles ----
