@@ -24,7 +24,8 @@
  *                             |scipy.signal.hilbert| -- row N3
  *   mm_pcm_decode_f32,
  *   mm_resample_f32        <- librosa.load(path, sr=sigSr, mono=False) (script/mfcc.py:284,373) -- row N4
- *   mm_find_peaks          <- MinMaxFinder (script/calc.py:651-686; script/main.py:1546-1613):
+ *   mm_find_peaks,
+ *   mm_find_peaks_ex       <- MinMaxFinder (script/calc.py:651-686; script/main.py:1546-1613):
  *                             scipy.signal.find_peaks(y) / find_peaks(-y) on a batch of curves
  *   mm_build_window/mel/dct<- scipy.signal.get_window('hann'), librosa.filters.mel,
  *                             scipy.fftpack.dct(type=2, norm='ortho') constant tables
@@ -432,6 +433,48 @@ size_t mm_find_peaks_workspace_bytes(int64_t rows, int64_t n);
 int mm_find_peaks(const mm_peaks_opts* opts, const void* d_x, int32_t dtype, int64_t rows, int64_t n, int64_t x_stride,
                   const int32_t* d_lo, const int32_t* d_hi, int64_t cap, int32_t* d_count, int32_t* d_idx, double* d_prom,
                   int32_t* d_lbase, int32_t* d_rbase, void* d_ws, size_t ws_bytes, void* stream);
+
+/* The remaining conditions of scipy.signal.find_peaks, beside mm_peaks_opts: plateau_size and width are intervals like
+ * the others, distance is scipy's ceil(distance) >= 1, wlen its ceil(wlen) >= 2 (<= 0: no window) and is looked at only
+ * when the prominence is computed, rel_height >= 0 that of peak_widths.  A zeroed struct asks for nothing. */
+typedef struct mm_peaks_ext {
+  double plateau_size[2];  /* right_edge - left_edge + 1                                                 */
+  double width[2];         /* scipy's peak_widths at rel_height, prominences taken inside wlen           */
+  double rel_height;
+  int32_t distance, wlen, use_plateau_size, use_distance, use_width;
+} mm_peaks_ext;
+
+/* Device outputs of mm_find_peaks_ex: count [rows], every other array [rows][cap], padded like d_idx (integers -1,
+ * doubles NaN).  NULL = not wanted, except count and (cap > 0) idx; prom, lbase and rbase are required when
+ * use_prominence or use_width is set.  An array of a condition that is not used is left untouched. */
+typedef struct mm_peaks_out {
+  int32_t* count;
+  int32_t* idx;
+  double* prom;
+  int32_t* lbase;
+  int32_t* rbase;
+  double* widths;
+  double* width_heights;
+  double* left_ips;
+  double* right_ips;
+  int32_t* plateau_sizes;
+  int32_t* left_edges;
+  int32_t* right_edges;
+} mm_peaks_out;
+
+/* mm_find_peaks with every condition of scipy.signal.find_peaks, applied in its order: plateau_size, height, threshold,
+ * distance, prominence, width.  ext == NULL, or an ext that uses none of its conditions, is mm_find_peaks itself: the
+ * same kernels and the same workspace.  Otherwise the conditions run as stages over the candidate list of the workspace
+ * (64 bytes per possible peak): distance is scipy's greedy selection (of two equally high peaks nearer than distance the
+ * one with the LARGER index survives -- scipy leaves that to an unstable sort), all its rounds in one launch; the
+ * prominence window is [p - wlen / 2, p + wlen / 2] clipped to the slice; widths, width heights and interpolated
+ * positions (relative to lo) equal scipy's peak_widths bit for bit.  Status codes, the true count beyond cap and the
+ * checks before any launch are those of mm_find_peaks; a NaN bound, use_distance with distance < 1, wlen == 1 or
+ * rel_height < 0 is MM_ERR_INVALID_ARG as well. */
+size_t mm_find_peaks_ex_workspace_bytes(const mm_peaks_opts* opts, const mm_peaks_ext* ext, int64_t rows, int64_t n);
+int mm_find_peaks_ex(const mm_peaks_opts* opts, const mm_peaks_ext* ext, const void* d_x, int32_t dtype, int64_t rows,
+                     int64_t n, int64_t x_stride, const int32_t* d_lo, const int32_t* d_hi, int64_t cap,
+                     const mm_peaks_out* out, void* d_ws, size_t ws_bytes, void* stream);
 
 /* ---- per-kernel device timing (hipEvents on the launch stream) ------------------------- */
 /* on = 0: off; 1: every stage; otherwise a mask with bit (MM_STAGE_x + 1) set for each stage to time

@@ -8,7 +8,8 @@ from .plan import MfccConfig, MfccPlan, get_plan, butter_sos  # noqa: F401
 from .batch import mfcc_batch, modspec_batch, mfcc_modspec_batch, rfft_batch, rms_batch  # noqa: F401
 from .mfcc import get_MFCCS_change, load_channel, applyFilter, get_amplitude  # noqa: F401
 from .calc import (get_velocity, calculate_amplitude_envelope, velocity_batch, amplitude_envelope_batch,  # noqa: F401
-                   hilbert_envelope_batch, find_peaks_batch, peaks_to_list, MinMaxFinder)
+                   hilbert_envelope_batch, find_peaks_batch, find_peaks_ex_batch,
+                   peaks_to_list, MinMaxFinder)
 from .filters import sosfiltfilt_batch  # noqa: F401
 from .audio_io import load_audio, load_wav, resample_batch  # noqa: F401
 from .pitch import pyin_batch, pyin, interp_NAN, get_f0  # noqa: F401

@@ -80,6 +80,19 @@ class mm_peaks_opts(C.Structure):
     ]
 
 
+class mm_peaks_ext(C.Structure):
+    _fields_ = [
+        ("plateau_size", C.c_double * 2), ("width", C.c_double * 2), ("rel_height", C.c_double),
+        ("distance", C.c_int32), ("wlen", C.c_int32), ("use_plateau_size", C.c_int32), ("use_distance", C.c_int32),
+        ("use_width", C.c_int32),
+    ]
+
+
+class mm_peaks_out(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("count", "idx", "prom", "lbase", "rbase", "widths", "width_heights", "left_ips",
+                                           "right_ips", "plateau_sizes", "left_edges", "right_edges")]
+
+
 class MMError(RuntimeError):
     def __init__(self, status, what, detail=""):
         self.status = status
@@ -160,6 +173,9 @@ PROTOTYPES = {
     "mm_find_peaks_workspace_bytes": (C.c_size_t, [_i64, _i64]),
     "mm_find_peaks": (C.c_int, [C.POINTER(mm_peaks_opts), _vp, C.c_int32, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp,
                                 _vp, _vp, _vp, C.c_size_t, _vp]),
+    "mm_find_peaks_ex_workspace_bytes": (C.c_size_t, [C.POINTER(mm_peaks_opts), C.POINTER(mm_peaks_ext), _i64, _i64]),
+    "mm_find_peaks_ex": (C.c_int, [C.POINTER(mm_peaks_opts), C.POINTER(mm_peaks_ext), _vp, C.c_int32, _i64, _i64, _i64, _vp,
+                                   _vp, _i64, C.POINTER(mm_peaks_out), _vp, C.c_size_t, _vp]),
     "mm_timing_enable": (C.c_int, [_vp, C.c_int]),
     "mm_timing_read": (C.c_int, [_vp, _vp, _vp]),
 }

@@ -5,7 +5,7 @@ drop-in surface is ``applyFilter`` (script/calc.py:23-129), ``get_velocity`` (:5
 the UI to the MFCC-change curve, script/main.py:668-713) and the RMS / Hilbert amplitude envelope
 (:221-343), the pYIN branch of ``get_f0`` with its ``interp_NAN`` (:345-592; modulation_mfcc_amd.pitch) and
 ``MinMaxFinder`` (:651-686: the peaks and troughs of a drawn curve, scipy.signal.find_peaks on the device --
-``find_peaks_batch`` for [rows, n] device curves).  Praat-backed
+``find_peaks_batch`` for [rows, n] device curves, ``find_peaks_ex_batch`` with scipy's remaining conditions).  Praat-backed
 functions (f0 by 'praatac' / 'praatcc', formants, RMSpraat) and the EMA reader are out of scope.
 """
 from __future__ import annotations
@@ -17,7 +17,8 @@ from .filters import applyFilter
 from .pitch import get_f0, interp_NAN  # noqa: F401
 
 __all__ = ["applyFilter", "get_f0", "interp_NAN", "get_velocity", "calculate_amplitude_envelope", "velocity_stencil", "velocity_batch", "apply_stencil",
-           "hilbert_envelope_batch", "amplitude_envelope_batch", "find_peaks_batch", "peaks_to_list", "MinMaxFinder"]
+           "hilbert_envelope_batch", "amplitude_envelope_batch", "find_peaks_batch", "find_peaks_ex_batch",
+           "peaks_to_list", "MinMaxFinder"]
 
 
 def _is_device_tensor(x):
@@ -455,7 +456,61 @@ def find_peaks_batch(x, *, negate=False, height=None, threshold=None, prominence
     each exactly when scipy returns it, shaped like ``idx`` (NaN / -1 beyond the count).  ``lo`` / ``hi`` (an integer, one
     per row, or an integer tensor; tensors are clamped to 0 <= lo <= hi <= n on the device) restrict row r to
     ``x[r, lo:hi]``: the result is scipy's on that slice, indices relative to ``lo``.  ``distance``, ``width``, ``wlen``
-    and ``plateau_size`` are not offered.  A 1-D input gives 1-D outputs."""
+    and ``plateau_size`` are those of ``find_peaks_ex_batch``, of which this function is the subset that needs no
+    candidate stages.  A 1-D input gives 1-D outputs."""
+    return _find_peaks(x, negate, height, threshold, prominence, lo, hi, None)
+
+
+def find_peaks_ex_batch(x, *, negate=False, height=None, threshold=None, distance=None, prominence=None, width=None,
+                        wlen=None, rel_height=0.5, plateau_size=None, lo=None, hi=None):
+    """``find_peaks_batch`` with every condition of scipy.signal.find_peaks (mm_find_peaks_ex): input, ``(idx, count,
+    props)``, ``negate``, ``lo`` / ``hi``, the 1-D squeeze and the TypeErrors are those of ``find_peaks_batch``; with only
+    its arguments the same kernels run.
+
+    The conditions are applied in scipy's order -- ``plateau_size``, ``height``, ``threshold``, ``distance``,
+    ``prominence``, ``width`` -- and ``props`` holds exactly the keys scipy returns for the same arguments, shaped like
+    ``idx``: ``plateau_sizes`` / ``left_edges`` / ``right_edges`` (int32, -1 beyond the count), ``peak_heights``,
+    ``left_thresholds`` / ``right_thresholds``, ``prominences`` / ``left_bases`` / ``right_bases`` (with ``width`` alone
+    too), ``widths`` / ``width_heights`` / ``left_ips`` / ``right_ips`` (float64, NaN beyond the count; positions relative
+    to ``lo``).  Every value equals scipy's bit for bit.
+
+    ``plateau_size`` and ``width`` are a minimum or ``(min, max)`` with ``None`` for an open side.  ``distance`` is a real
+    number >= 1, used as ``ceil(distance)``.  ``wlen`` is looked at only when ``prominence`` or ``width`` is given, as in
+    scipy: ``None`` is no window, a value > 1 is used as ``ceil(wlen)``, the window being ``[p - wlen // 2, p + wlen // 2]``
+    clipped to the row (to ``x[r, lo:hi]``).  ``rel_height`` >= 0 is that of scipy.signal.peak_widths.  scipy's
+    PeakPropertyWarning is not emitted.
+
+    Tied heights under ``distance``: scipy ranks the peaks with an unstable ``np.argsort``, so which of two equally high
+    peaks nearer than ``distance`` survives is not defined there.  Here the peak with the LARGER index has priority (a
+    stable argsort walked from its end)."""
+    import math
+    ext = {"plateau_size": None, "distance": 0, "width": None, "wlen": 0, "rel_height": float(rel_height)}
+    if plateau_size is not None:
+        ext["plateau_size"] = _peak_interval("plateau_size", plateau_size)
+    if distance is not None:
+        if isinstance(distance, bool) or not isinstance(distance, (int, float, np.integer, np.floating)):
+            raise TypeError("distance must be a real number")
+        if not distance >= 1:
+            raise ValueError("`distance` must be greater or equal to 1")
+        ext["distance"] = min(int(math.ceil(distance)), 0x7fffffff)
+    if width is not None:
+        ext["width"] = _peak_interval("width", width)
+    if prominence is not None or width is not None:
+        if wlen is not None:
+            if isinstance(wlen, bool) or not isinstance(wlen, (int, float, np.integer, np.floating)):
+                raise TypeError("wlen must be a real number")
+            if not 1 < wlen:
+                raise ValueError(f"`wlen` must be larger than 1, was {wlen}")
+            ext["wlen"] = min(int(wlen) if isinstance(wlen, (int, np.integer)) else int(math.ceil(wlen)), 0x7fffffff)
+        if width is not None and rel_height < 0:
+            raise ValueError("`rel_height` must be greater or equal to 0.0")
+    if not ext["rel_height"] >= 0:
+        ext["rel_height"] = 0.0                                 # unused without width; the C entry refuses it always
+    return _find_peaks(x, negate, height, threshold, prominence, lo, hi, ext)
+
+
+def _find_peaks(x, negate, height, threshold, prominence, lo, hi, ext):
+    """find_peaks_batch (ext None: mm_find_peaks) and find_peaks_ex_batch (ext: the checked extra conditions)."""
     import ctypes as C
     import math
     import torch
@@ -482,20 +537,43 @@ def find_peaks_batch(x, *, negate=False, height=None, threshold=None, prominence
     count = torch.zeros((rows,), dtype=torch.int32, device=dev)
     props = {}
     prom = lb = rb = None
-    if prominence is not None:
-        prom = torch.empty((rows, cap), dtype=torch.float64, device=dev)
-        lb = torch.empty((rows, cap), dtype=torch.int32, device=dev)
-        rb = torch.empty((rows, cap), dtype=torch.int32, device=dev)
+    f64 = lambda: torch.empty((rows, cap), dtype=torch.float64, device=dev)     # noqa: E731
+    i32 = lambda: torch.empty((rows, cap), dtype=torch.int32, device=dev)       # noqa: E731
+    plateau = ext is not None and ext["plateau_size"] is not None
+    widths = ext is not None and ext["width"] is not None
+    if prominence is not None or widths:
+        prom, lb, rb = f64(), i32(), i32()
+    wout = [f64() for _ in range(4)] if widths else [None] * 4
+    pout = [i32() for _ in range(3)] if plateau else [None] * 3
     if rows > 0 and n > 0:
         lib = _lib.load()
         stride = x2.stride(0) if rows > 1 else max(n, x2.stride(0))
-        ws = torch.empty(int(lib.mm_find_peaks_workspace_bytes(rows, n)), dtype=torch.uint8, device=dev)
         ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None   # noqa: E731
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        with torch.cuda.device(dev):
-            _lib.check(lib.mm_find_peaks(C.byref(o), x2.data_ptr(), 0 if x2.dtype == torch.float32 else 1, rows, n, stride,
-                                         ptr(d_lo), ptr(d_hi), cap, count.data_ptr(), ptr(idx), ptr(prom), ptr(lb),
-                                         ptr(rb), ws.data_ptr(), ws.numel(), stream), "mm_find_peaks")
+        dtype = 0 if x2.dtype == torch.float32 else 1
+        if ext is None:
+            ws = torch.empty(int(lib.mm_find_peaks_workspace_bytes(rows, n)), dtype=torch.uint8, device=dev)
+            with torch.cuda.device(dev):
+                _lib.check(lib.mm_find_peaks(C.byref(o), x2.data_ptr(), dtype, rows, n, stride, ptr(d_lo), ptr(d_hi), cap,
+                                             count.data_ptr(), ptr(idx), ptr(prom), ptr(lb), ptr(rb), ws.data_ptr(),
+                                             ws.numel(), stream), "mm_find_peaks")
+        else:
+            e = _lib.mm_peaks_ext()
+            for name, use in (("plateau_size", plateau), ("width", widths)):
+                field = getattr(e, name)
+                field[0], field[1] = ext[name] if use else (-math.inf, math.inf)
+                setattr(e, "use_" + name, 1 if use else 0)
+            e.rel_height, e.wlen = ext["rel_height"], ext["wlen"]
+            e.distance, e.use_distance = ext["distance"], 1 if ext["distance"] else 0
+            out = _lib.mm_peaks_out(count.data_ptr(), ptr(idx), ptr(prom), ptr(lb), ptr(rb), *(ptr(t) for t in wout + pout))
+            ws = torch.empty(int(lib.mm_find_peaks_ex_workspace_bytes(C.byref(o), C.byref(e), rows, n)), dtype=torch.uint8,
+                             device=dev)
+            with torch.cuda.device(dev):
+                _lib.check(lib.mm_find_peaks_ex(C.byref(o), C.byref(e), x2.data_ptr(), dtype, rows, n, stride, ptr(d_lo),
+                                                ptr(d_hi), cap, C.byref(out), ws.data_ptr(), ws.numel(), stream),
+                           "mm_find_peaks_ex")
+    if plateau:
+        props["plateau_sizes"], props["left_edges"], props["right_edges"] = pout
     if height is not None or threshold is not None:
         # x[p], x[p] - x[p -+ 1]: gathers of the input at the indices the kernel returned, the same float64 differences
         ok = idx >= 0
@@ -512,8 +590,10 @@ def find_peaks_batch(x, *, negate=False, height=None, threshold=None, prominence
         if threshold is not None:
             props["left_thresholds"] = torch.where(ok, val(0) - val(-1), nan)
             props["right_thresholds"] = torch.where(ok, val(0) - val(1), nan)
-    if prominence is not None:
+    if prom is not None:
         props["prominences"], props["left_bases"], props["right_bases"] = prom, lb, rb
+    if widths:
+        props["widths"], props["width_heights"], props["left_ips"], props["right_ips"] = wout
     if squeeze:
         return idx[0], count[0], {k: v[0] for k, v in props.items()}
     return idx, count, props

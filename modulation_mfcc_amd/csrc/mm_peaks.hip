@@ -6,6 +6,12 @@
 //   pk_write_kernel   the same test again, plateau midpoints written at scan offset + rank (ballot / popcount)
 //   pk_prom_kernel    one wave per candidate: prominence and bases, 64 samples a step
 //   pk_ccount_kernel / pk_cwrite_kernel   the candidates the prominence interval keeps, compacted the same way
+// mm_find_peaks_ex adds plateau_size, distance, wlen and width as stages over the candidate list of the workspace, each
+// clearing a candidate's keep flag, and one compaction on that flag at the end:
+//   pk_count / pk_write <T, true>   the plateau's edges beside its midpoint, plateau_size filtered with height / threshold
+//   pk_distance_kernel    a workgroup per row: scipy's greedy selection as a fixed point, every round inside the launch
+//   pk_promw_kernel       a wave per kept candidate: prominence inside wlen, then scipy's peak_widths at rel_height
+//   pk_ccount_kernel / pk_cwrite_ex_kernel   the kept candidates and every property the caller asked for
 // Every comparison is a plain IEEE one (NaN compares false, as in scipy's Cython loops); values are float64 throughout
 // (float32 input is promoted per element, exactly), so indices, bases and prominences equal scipy's bit for bit.
 #include "mm_common.h"
@@ -34,6 +40,8 @@ struct PkArgs {
   int32_t row0;             // first row of this launch (rows beyond the grid's y limit take further launches)
   int32_t negate, use_height, use_threshold;
   double hmin, hmax, tmin, tmax;
+  int32_t use_plateau;      // read by the <T, true> kernels only
+  double psmin, psmax;
 };
 
 // one row's samples as scipy sees them: float64, negated for troughs, restricted to [lo, hi)
@@ -61,9 +69,11 @@ __device__ __forceinline__ bool pk_in(double v, double vmin, double vmax) {
 }
 
 // scipy's _local_maxima_1d at sample i (absolute; lo < i < hi - 1): -1, or the plateau midpoint when i is the rising edge
-// of a plateau whose first different sample is lower.  Then height and threshold, scipy's order and arithmetic.
-template <class T>
-__device__ __forceinline__ int32_t pk_peak_at(const PkArgs& a, const PkRow<T>& r, int32_t i) {
+// of a plateau whose first different sample is lower.  Then height and threshold, scipy's order and arithmetic.  EX: the
+// plateau's edges (relative to lo) come back too -- the lane that owns the rising edge has walked to the falling one,
+// across segment boundaries as well -- and plateau_size is tested first.
+template <class T, bool EX>
+__device__ __forceinline__ int32_t pk_peak_at(const PkArgs& a, const PkRow<T>& r, int32_t i, int32_t& le, int32_t& re) {
   if (i <= r.lo || i >= r.hi - 1) return -1;
   const double v = r.at(i);
   if (!(r.at(i - 1) < v)) return -1;
@@ -72,6 +82,10 @@ __device__ __forceinline__ int32_t pk_peak_at(const PkArgs& a, const PkRow<T>& r
   while (j < last && r.at(j) == v) ++j;            // the lane walks its plateau alone
   if (!(r.at(j) < v)) return -1;
   const int32_t mid = (int32_t)(((int64_t)i + (j - 1)) / 2);
+  if (EX) {
+    le = i - r.lo; re = j - 1 - r.lo;
+    if (a.use_plateau && !pk_in((double)(j - i), a.psmin, a.psmax)) return -1;
+  }
   if (a.use_height && !pk_in(v, a.hmin, a.hmax)) return -1;
   if (a.use_threshold) {
     const double dl = v - r.at(mid - 1), dr = v - r.at(mid + 1);
@@ -84,7 +98,7 @@ __device__ __forceinline__ int32_t pk_peak_at(const PkArgs& a, const PkRow<T>& r
   return mid - r.lo;
 }
 
-template <class T>
+template <class T, bool EX>
 __global__ __launch_bounds__(kPkThreads) void pk_count_kernel(PkArgs a, int32_t* __restrict__ segcount) {
   __shared__ int s_w[kPkWaves];
   const int64_t row = (int64_t)a.row0 + blockIdx.y;
@@ -95,7 +109,8 @@ __global__ __launch_bounds__(kPkThreads) void pk_count_kernel(PkArgs a, int32_t*
 #pragma unroll
     for (int k = 0; k < kPkPer; ++k) {
       const int64_t i = base + k * kPkThreads + threadIdx.x;
-      const bool pk = i < a.n && pk_peak_at<T>(a, r, (int32_t)i) >= 0;
+      int32_t le, re;
+      const bool pk = i < a.n && pk_peak_at<T, EX>(a, r, (int32_t)i, le, re) >= 0;
       cnt += __popcll(__ballot(pk));
     }
   }
@@ -131,13 +146,17 @@ __device__ __forceinline__ int pk_block_exscan(int v, int* s_w, int* tot) {
   return before + inc - v;
 }
 
-// A workgroup per row: segcount[row][0 .. nseg) becomes its exclusive prefix, total[row] the sum; idx[row][min(total,
-// cap) .. cap) is filled with -1, as are the bases, the prominences with NaN (fill == nullptr: the candidate pass, whose
-// consumers read only below the count).
+// the output arrays whose unused slots a scan pads: i[0] the indices, then bases and edges; prominences and widths
+struct PkFill {
+  int32_t* i[6];
+  double* d[5];
+};
+
+// A workgroup per row: segcount[row][0 .. nseg) becomes its exclusive prefix, total[row] the sum; every array of f that
+// is not NULL is filled over [row][min(total, cap) .. cap), integers with -1, doubles with NaN (f.i[0] == nullptr: the
+// candidate pass, whose consumers read only below the count).
 __global__ __launch_bounds__(kPkThreads) void pk_scan_kernel(int32_t* __restrict__ segcount, int32_t nseg,
-                                                             int32_t* __restrict__ total, int32_t* __restrict__ fill,
-                                                             int32_t* __restrict__ fill_lb, int32_t* __restrict__ fill_rb,
-                                                             double* __restrict__ fill_prom, int64_t cap) {
+                                                             int32_t* __restrict__ total, PkFill f, int64_t cap) {
   __shared__ int s_w[kPkWaves];
   const int64_t row = blockIdx.x;
   int32_t* sc = segcount + row * nseg;
@@ -153,10 +172,14 @@ __global__ __launch_bounds__(kPkThreads) void pk_scan_kernel(int32_t* __restrict
     run += c;
   }
   if (threadIdx.x == 0) total[row] = tot;
-  if (fill) {
+  if (f.i[0]) {
     for (int64_t k = min<int64_t>(tot, cap) + threadIdx.x; k < cap; k += kPkThreads) {
-      fill[row * cap + k] = -1;
-      if (fill_lb) { fill_lb[row * cap + k] = -1; fill_rb[row * cap + k] = -1; fill_prom[row * cap + k] = NAN; }
+#pragma unroll
+      for (int u = 0; u < 6; ++u)
+        if (f.i[u]) f.i[u][row * cap + k] = -1;
+#pragma unroll
+      for (int u = 0; u < 5; ++u)
+        if (f.d[u]) f.d[u][row * cap + k] = NAN;
     }
   }
 }
@@ -173,20 +196,25 @@ __device__ __forceinline__ int pk_rank(const uint64_t (&m)[kPkPer], int k, int (
   return before + __popcll(m[k] & pk_lanemask_lt());
 }
 
-template <class T>
+// EX: the candidate's edges and its keep flag (1) go to the workspace beside the midpoint
+struct PkEdges {
+  int32_t *le, *re, *keep;
+};
+
+template <class T, bool EX>
 __global__ __launch_bounds__(kPkThreads) void pk_write_kernel(PkArgs a, const int32_t* __restrict__ segoff,
-                                                              int32_t* __restrict__ idx, int64_t cap) {
+                                                              int32_t* __restrict__ idx, int64_t cap, PkEdges e) {
   __shared__ int s_c[kPkPer][kPkWaves];
   const int64_t row = (int64_t)a.row0 + blockIdx.y;
   const PkRow<T> r(a, row);
   const int64_t base = (int64_t)blockIdx.x * kPkSeg;
   if (!(base < r.hi && base + kPkSeg > r.lo)) return;          // (workgroup-uniform)
-  int32_t mid[kPkPer];
+  int32_t mid[kPkPer], le[kPkPer], re[kPkPer];
   uint64_t m[kPkPer];
 #pragma unroll
   for (int k = 0; k < kPkPer; ++k) {
     const int64_t i = base + k * kPkThreads + threadIdx.x;
-    mid[k] = i < a.n ? pk_peak_at<T>(a, r, (int32_t)i) : -1;
+    mid[k] = i < a.n ? pk_peak_at<T, EX>(a, r, (int32_t)i, le[k], re[k]) : -1;
     m[k] = __ballot(mid[k] >= 0);
     if ((threadIdx.x & 63) == 0) s_c[k][threadIdx.x >> 6] = __popcll(m[k]);
   }
@@ -196,7 +224,10 @@ __global__ __launch_bounds__(kPkThreads) void pk_write_kernel(PkArgs a, const in
   for (int k = 0; k < kPkPer; ++k) {
     if (mid[k] >= 0) {
       const int64_t pos = off + pk_rank(m, k, s_c);
-      if (pos < cap) idx[row * cap + pos] = mid[k];
+      if (pos < cap) {
+        idx[row * cap + pos] = mid[k];
+        if (EX) { e.le[row * cap + pos] = le[k]; e.re[row * cap + pos] = re[k]; e.keep[row * cap + pos] = 1; }
+      }
     }
   }
 }
@@ -217,13 +248,15 @@ struct PkPromArgs {
   double pmin, pmax;
 };
 
+// lim: the last sample of the scan (inclusive): the row's (slice's) end, or the end of scipy's wlen window
 template <class T, int DIR>
-__device__ __forceinline__ void pk_scan_side(const PkRow<T>& r, int32_t p, double vp, double& best, int32_t& base) {
+__device__ __forceinline__ void pk_scan_side(const PkRow<T>& r, int32_t p, int32_t lim, double vp, double& best,
+                                             int32_t& base) {
   const int lane = threadIdx.x & 63;
   best = vp; base = p;
   for (int64_t step = 0;; step += 64) {
     const int64_t i = (int64_t)p + DIR * (step + 1 + lane);
-    const bool inside = DIR < 0 ? i >= r.lo : i < r.hi;
+    const bool inside = DIR < 0 ? i >= lim : i <= lim;
     const double v = inside ? r.at((int32_t)i) : 0.0;
     const bool stop = !inside || !(v <= vp);
     const uint64_t sm = __ballot(stop);
@@ -252,8 +285,8 @@ __global__ __launch_bounds__(64 * kPkPromWaves) void pk_prom_kernel(PkArgs a, Pk
     const double vp = r.at(p);
     double lmin, rmin;
     int32_t lb, rb;
-    pk_scan_side<T, -1>(r, p, vp, lmin, lb);
-    pk_scan_side<T, 1>(r, p, vp, rmin, rb);
+    pk_scan_side<T, -1>(r, p, r.lo, vp, lmin, lb);
+    pk_scan_side<T, 1>(r, p, r.hi - 1, vp, rmin, rb);
     const double prom = vp - (lmin > rmin ? lmin : rmin);
     const bool keep = pk_in(prom, q.pmin, q.pmax);
     if ((threadIdx.x & 63) == 0) {
@@ -264,18 +297,21 @@ __global__ __launch_bounds__(64 * kPkPromWaves) void pk_prom_kernel(PkArgs a, Pk
   }
 }
 
-__global__ __launch_bounds__(kPkThreads) void pk_ccount_kernel(PkPromArgs q, int32_t row0, int32_t ncseg,
+// keep [rows][ccap]: a candidate stays when its entry is >= 0 (the left bases of pk_prom_kernel, or the stages' flags)
+__global__ __launch_bounds__(kPkThreads) void pk_ccount_kernel(const int32_t* __restrict__ ccount,
+                                                               const int32_t* __restrict__ keep, int64_t ccap,
+                                                               int32_t row0, int32_t ncseg,
                                                                int32_t* __restrict__ segcount) {
   __shared__ int s_w[kPkWaves];
   const int64_t row = (int64_t)row0 + blockIdx.y;
-  const int32_t nc = (int32_t)min<int64_t>(q.ccount[row], q.ccap);
+  const int32_t nc = (int32_t)min<int64_t>(ccount[row], ccap);
   const int64_t base = (int64_t)blockIdx.x * kPkSeg;
   int cnt = 0;
   if (base < nc) {
 #pragma unroll
     for (int k = 0; k < kPkPer; ++k) {
       const int64_t c = base + k * kPkThreads + threadIdx.x;
-      cnt += __popcll(__ballot(c < nc && q.clb[row * q.ccap + c] >= 0));
+      cnt += __popcll(__ballot(c < nc && keep[row * ccap + c] >= 0));
     }
   }
   if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = cnt;
@@ -325,6 +361,183 @@ __global__ __launch_bounds__(kPkThreads) void pk_cwrite_kernel(PkPromArgs q, int
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// the stages of mm_find_peaks_ex.  Candidates keep the slot the first compaction gave them; a stage drops one by setting
+// its keep flag to -1, later stages skip it, the last compaction removes it.
+// ---------------------------------------------------------------------------------------------------------------------
+struct PkCand {
+  const int32_t* ccount;    // [rows] candidates per row
+  int32_t *idx, *keep, *le, *re, *lb, *rb;          // [rows][ccap]
+  double *prom, *w, *wh, *lip, *rip;                // [rows][ccap]; wh holds the heights while the distance stage runs
+  int64_t ccap;
+};
+
+constexpr int kPkDistThreads = 1024;
+
+__device__ __forceinline__ int32_t pk_ld(const int32_t* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void pk_st(int32_t* p, int32_t v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// scipy's _select_by_peak_distance (the highest peak first, each survivor deleting what is nearer than distance) as a
+// fixed point, a workgroup per row, all rounds in this launch.  Priority is (height, index): of two equally high peaks
+// the one with the larger index goes first, which is a stable argsort walked from its end.  keep: 0 undecided, -1
+// deleted, k >= 1 kept in round k.  Round k: an undecided peak with no undecided neighbour of higher priority nearer
+// than distance becomes kept (a peak marked k in this very pass still counts as undecided for its neighbours); after
+// the barrier the peaks kept in round k delete their undecided neighbours.  The highest undecided peak of a row is
+// always kept, so there are at most as many rounds as peaks (a ramp of peaks under a distance that reaches one
+// neighbour needs half as many); typical curves need a handful.
+template <class T>
+__global__ __launch_bounds__(kPkDistThreads) void pk_distance_kernel(PkArgs a, PkCand q, int32_t distance) {
+  const int64_t row = blockIdx.x;
+  const PkRow<T> r(a, row);
+  const int32_t nc = (int32_t)min<int64_t>(q.ccount[row], q.ccap);
+  const int32_t* pos = q.idx + row * q.ccap;
+  double* h = q.wh + row * q.ccap;
+  int32_t* keep = q.keep + row * q.ccap;
+  for (int32_t c = threadIdx.x; c < nc; c += kPkDistThreads) {
+    h[c] = r.at(pos[c] + r.lo);
+    pk_st(keep + c, 0);
+  }
+  __syncthreads();
+  for (int32_t round = 1; round <= nc + 1; ++round) {
+    int open = 0;
+    for (int32_t c = threadIdx.x; c < nc; c += kPkDistThreads) {
+      if (pk_ld(keep + c) != 0) continue;
+      open = 1;
+      const int32_t pc = pos[c];
+      const double hc = h[c];
+      bool top = true;
+      for (int32_t j = c - 1; top && j >= 0 && pc - pos[j] < distance; --j) {
+        const int32_t s = pk_ld(keep + j);
+        if ((s == 0 || s == round) && h[j] > hc) top = false;
+      }
+      for (int32_t j = c + 1; top && j < nc && pos[j] - pc < distance; ++j) {
+        const int32_t s = pk_ld(keep + j);
+        if ((s == 0 || s == round) && h[j] >= hc) top = false;
+      }
+      if (top) pk_st(keep + c, round);
+    }
+    if (!__syncthreads_or(open)) break;
+    for (int32_t c = threadIdx.x; c < nc; c += kPkDistThreads) {
+      if (pk_ld(keep + c) != round) continue;
+      const int32_t pc = pos[c];
+      for (int32_t j = c - 1; j >= 0 && pc - pos[j] < distance; --j)
+        if (pk_ld(keep + j) == 0) pk_st(keep + j, -1);
+      for (int32_t j = c + 1; j < nc && pos[j] - pc < distance; ++j)
+        if (pk_ld(keep + j) == 0) pk_st(keep + j, -1);
+    }
+    __syncthreads();
+  }
+}
+
+// scipy's _peak_widths on one side: from the peak towards its base, the first sample that is the base itself or not above
+// the evaluation height h; 64 samples a step, the first stopping lane decides (the lane at the peak itself included)
+template <class T, int DIR>
+__device__ __forceinline__ int32_t pk_cross_side(const PkRow<T>& r, int32_t p, int32_t base, double h) {
+  const int lane = threadIdx.x & 63;
+  for (int64_t step = 0;; step += 64) {
+    const int64_t i = (int64_t)p + DIR * (step + lane);
+    const bool inside = DIR < 0 ? i > base : i < base;
+    const double v = inside ? r.at((int32_t)i) : 0.0;
+    const uint64_t sm = __ballot(!inside || !(h < v));
+    if (sm) return (int32_t)((int64_t)p + DIR * (step + __ffsll((unsigned long long)sm) - 1));
+  }
+}
+
+struct PkPromwArgs {
+  double pmin, pmax, wmin, wmax, rel_height;
+  int32_t wlen, use_width;
+};
+
+// A wave per kept candidate: the prominence inside scipy's wlen window ([p - wlen / 2, p + wlen / 2] clipped to the
+// slice; wlen < 2: the slice), its interval, then -- for the survivors -- scipy's peak_widths, operation for operation in
+// float64 with contraction off (an fma in h or the interpolation changes the last bit), and the width interval.
+template <class T>
+__global__ __launch_bounds__(64 * kPkPromWaves) void pk_promw_kernel(PkArgs a, PkCand q, PkPromwArgs o) {
+#pragma clang fp contract(off)
+  const int64_t row = (int64_t)a.row0 + blockIdx.y;
+  const PkRow<T> r(a, row);
+  const int32_t nc = (int32_t)min<int64_t>(q.ccount[row], q.ccap);
+  const int w = threadIdx.x >> 6;
+  for (int64_t c = (int64_t)blockIdx.x * kPkPromWaves + w; c < nc; c += (int64_t)gridDim.x * kPkPromWaves) {
+    const int64_t at = row * q.ccap + c;
+    if (q.keep[at] < 0) continue;                     // (wave-uniform)
+    const int32_t p = q.idx[at] + r.lo;
+    const double vp = r.at(p);
+    int32_t wl = r.lo, wr = r.hi - 1;
+    if (o.wlen >= 2) {
+      wl = max(wl, p - o.wlen / 2);
+      wr = (int32_t)min<int64_t>(wr, (int64_t)p + o.wlen / 2);
+    }
+    double lmin, rmin;
+    int32_t lb, rb;
+    pk_scan_side<T, -1>(r, p, wl, vp, lmin, lb);
+    pk_scan_side<T, 1>(r, p, wr, vp, rmin, rb);
+    const double prom = vp - (lmin > rmin ? lmin : rmin);
+    bool keep = pk_in(prom, o.pmin, o.pmax);
+    double width = 0.0, h = 0.0, lip = 0.0, rip = 0.0;
+    if (keep && o.use_width) {
+      h = vp - prom * o.rel_height;                   // two roundings (contract off), as the host compiler gives scipy
+      const int32_t il = pk_cross_side<T, -1>(r, p, lb, h), ir = pk_cross_side<T, 1>(r, p, rb, h);
+      const double xl = r.at(il), xr = r.at(ir);
+      lip = (double)(il - r.lo);
+      if (xl < h) lip += (h - xl) / (r.at(il + 1) - xl);
+      rip = (double)(ir - r.lo);
+      if (xr < h) rip -= (h - xr) / (r.at(ir - 1) - xr);
+      width = rip - lip;
+      keep = pk_in(width, o.wmin, o.wmax);
+    }
+    if ((threadIdx.x & 63) == 0) {
+      q.prom[at] = prom; q.lb[at] = lb - r.lo; q.rb[at] = rb - r.lo;
+      if (o.use_width) { q.w[at] = width; q.wh[at] = h; q.lip[at] = lip; q.rip[at] = rip; }
+      if (!keep) q.keep[at] = -1;
+    }
+  }
+}
+
+// the kept candidates, and each property whose output pointer is not NULL, at scan offset + rank
+__global__ __launch_bounds__(kPkThreads) void pk_cwrite_ex_kernel(PkCand q, int32_t row0, int32_t ncseg,
+                                                                  const int32_t* __restrict__ segoff, mm_peaks_out out,
+                                                                  int64_t cap) {
+  __shared__ int s_c[kPkPer][kPkWaves];
+  const int64_t row = (int64_t)row0 + blockIdx.y;
+  const int32_t nc = (int32_t)min<int64_t>(q.ccount[row], q.ccap);
+  const int64_t base = (int64_t)blockIdx.x * kPkSeg;
+  if (base >= nc) return;                                      // (workgroup-uniform)
+  bool keep[kPkPer];
+  uint64_t m[kPkPer];
+#pragma unroll
+  for (int k = 0; k < kPkPer; ++k) {
+    const int64_t c = base + k * kPkThreads + threadIdx.x;
+    keep[k] = c < nc && q.keep[row * q.ccap + c] >= 0;
+    m[k] = __ballot(keep[k]);
+    if ((threadIdx.x & 63) == 0) s_c[k][threadIdx.x >> 6] = __popcll(m[k]);
+  }
+  __syncthreads();
+  const int64_t off = segoff[row * ncseg + blockIdx.x];
+#pragma unroll
+  for (int k = 0; k < kPkPer; ++k) {
+    if (keep[k]) {
+      const int64_t pos = off + pk_rank(m, k, s_c);
+      if (pos < cap) {
+        const int64_t c = row * q.ccap + base + k * kPkThreads + threadIdx.x, d = row * cap + pos;
+        out.idx[d] = q.idx[c];
+        if (out.prom) { out.prom[d] = q.prom[c]; out.lbase[d] = q.lb[c]; out.rbase[d] = q.rb[c]; }
+        if (out.widths) out.widths[d] = q.w[c];
+        if (out.width_heights) out.width_heights[d] = q.wh[c];
+        if (out.left_ips) out.left_ips[d] = q.lip[c];
+        if (out.right_ips) out.right_ips[d] = q.rip[c];
+        if (out.plateau_sizes) out.plateau_sizes[d] = q.re[c] - q.le[c] + 1;
+        if (out.left_edges) out.left_edges[d] = q.le[c];
+        if (out.right_edges) out.right_edges[d] = q.re[c];
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int64_t kPkMaxN = 0x7fffffff - 2 * kPkSeg;           // 32-bit sample indices, segment arithmetic included
@@ -336,10 +549,12 @@ int64_t pk_segs(int64_t n) { return std::max<int64_t>(1, (n + kPkSeg - 1) / kPkS
 struct PkWs {
   int32_t *segcount, *ccount, *cidx, *clb, *crb, *csegcount;
   double* cprom;
+  int32_t *ckeep, *cle, *cre;             // the stages of mm_find_peaks_ex only (ex)
+  double *cw, *cwh, *clip, *crip;
   size_t bytes;
 };
 
-PkWs pk_carve(void* d_ws, int64_t rows, int64_t n) {
+PkWs pk_carve(void* d_ws, int64_t rows, int64_t n, bool ex) {
   const size_t ccap = (size_t)pk_max_peaks(n), R = (size_t)rows;
   char* w = (char*)d_ws;
   size_t o = 0;
@@ -351,6 +566,17 @@ PkWs pk_carve(void* d_ws, int64_t rows, int64_t n) {
   s.cidx = (int32_t*)(w + o);      o += pk_align(R * ccap * sizeof(int32_t));
   s.clb = (int32_t*)(w + o);       o += pk_align(R * ccap * sizeof(int32_t));
   s.crb = (int32_t*)(w + o);       o += pk_align(R * ccap * sizeof(int32_t));
+  s.ckeep = s.cle = s.cre = nullptr;
+  s.cw = s.cwh = s.clip = s.crip = nullptr;
+  if (ex) {
+    s.cw = (double*)(w + o);       o += pk_align(R * ccap * sizeof(double));
+    s.cwh = (double*)(w + o);      o += pk_align(R * ccap * sizeof(double));
+    s.clip = (double*)(w + o);     o += pk_align(R * ccap * sizeof(double));
+    s.crip = (double*)(w + o);     o += pk_align(R * ccap * sizeof(double));
+    s.ckeep = (int32_t*)(w + o);   o += pk_align(R * ccap * sizeof(int32_t));
+    s.cle = (int32_t*)(w + o);     o += pk_align(R * ccap * sizeof(int32_t));
+    s.cre = (int32_t*)(w + o);     o += pk_align(R * ccap * sizeof(int32_t));
+  }
   s.bytes = o;
   return s;
 }
@@ -370,17 +596,21 @@ int pk_run(const mm_peaks_opts* o, PkArgs a, int64_t rows, int64_t cap, int32_t*
   for (int64_t r0 = 0; r0 < rows; r0 += kPkMaxGridY) {
     a.row0 = (int32_t)r0;
     const unsigned ry = (unsigned)std::min<int64_t>(rows - r0, kPkMaxGridY);
-    hipLaunchKernelGGL(pk_count_kernel<T>, dim3((unsigned)a.nseg, ry), dim3(kPkThreads), 0, st, a, ws.segcount);
+    hipLaunchKernelGGL((pk_count_kernel<T, false>), dim3((unsigned)a.nseg, ry), dim3(kPkThreads), 0, st, a, ws.segcount);
     HIP_TRY(hipGetLastError());
   }
+  PkFill f1 = {}, f2 = {};
+  f1.i[0] = prom ? nullptr : d_idx;
+  f2.i[0] = d_idx; f2.i[1] = d_lb; f2.i[2] = d_rb; f2.d[0] = d_prom;
   hipLaunchKernelGGL(pk_scan_kernel, dim3((unsigned)rows), dim3(kPkThreads), 0, st, ws.segcount, a.nseg,
-                     prom ? ws.ccount : d_count, prom ? (int32_t*)nullptr : d_idx, (int32_t*)nullptr, (int32_t*)nullptr, (double*)nullptr, cap);
+                     prom ? ws.ccount : d_count, f1, cap);
   HIP_TRY(hipGetLastError());
   if (cap1 > 0) {
     for (int64_t r0 = 0; r0 < rows; r0 += kPkMaxGridY) {
       a.row0 = (int32_t)r0;
       const unsigned ry = (unsigned)std::min<int64_t>(rows - r0, kPkMaxGridY);
-      hipLaunchKernelGGL(pk_write_kernel<T>, dim3((unsigned)a.nseg, ry), dim3(kPkThreads), 0, st, a, ws.segcount, idx1, cap1);
+      hipLaunchKernelGGL((pk_write_kernel<T, false>), dim3((unsigned)a.nseg, ry), dim3(kPkThreads), 0, st, a, ws.segcount, idx1,
+                         cap1, PkEdges{});
       HIP_TRY(hipGetLastError());
     }
   }
@@ -392,15 +622,14 @@ int pk_run(const mm_peaks_opts* o, PkArgs a, int64_t rows, int64_t cap, int32_t*
       const unsigned ry = (unsigned)std::min<int64_t>(rows - r0, kPkMaxGridY);
       hipLaunchKernelGGL(pk_prom_kernel<T>, dim3(gx, ry), dim3(64 * kPkPromWaves), 0, st, a, q);
       HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(pk_ccount_kernel, dim3((unsigned)ncseg, ry), dim3(kPkThreads), 0, st, q, (int32_t)r0, ncseg,
-                         ws.csegcount);
+      hipLaunchKernelGGL(pk_ccount_kernel, dim3((unsigned)ncseg, ry), dim3(kPkThreads), 0, st, q.ccount, q.clb, ccap,
+                         (int32_t)r0, ncseg, ws.csegcount);
       HIP_TRY(hipGetLastError());
     }
   } else {
     HIP_TRY(hipMemsetAsync(ws.csegcount, 0, (size_t)rows * ncseg * sizeof(int32_t), st));
   }
-  hipLaunchKernelGGL(pk_scan_kernel, dim3((unsigned)rows), dim3(kPkThreads), 0, st, ws.csegcount, ncseg, d_count, d_idx,
-                     d_lb, d_rb, d_prom, cap);
+  hipLaunchKernelGGL(pk_scan_kernel, dim3((unsigned)rows), dim3(kPkThreads), 0, st, ws.csegcount, ncseg, d_count, f2, cap);
   HIP_TRY(hipGetLastError());
   if (cap > 0 && ccap > 0) {
     for (int64_t r0 = 0; r0 < rows; r0 += kPkMaxGridY) {
@@ -415,34 +644,145 @@ int pk_run(const mm_peaks_opts* o, PkArgs a, int64_t rows, int64_t cap, int32_t*
 
 bool pk_interval_ok(const double (&v)[2]) { return !std::isnan(v[0]) && !std::isnan(v[1]); }
 
+// The stages of mm_find_peaks_ex: candidates with their edges, distance, prominence (wlen) and widths, one compaction.
+template <class T>
+int pk_run_ex(const mm_peaks_opts* o, const mm_peaks_ext* e, PkArgs a, int64_t rows, int64_t cap, const mm_peaks_out& out,
+              const PkWs& ws, hipStream_t st) {
+  const bool need_prom = o->use_prominence != 0 || e->use_width != 0;
+  const int64_t ccap = pk_max_peaks(a.n);
+  const int32_t ncseg = (int32_t)pk_segs(ccap);
+  PkCand q;
+  q.ccount = ws.ccount; q.idx = ws.cidx; q.keep = ws.ckeep; q.le = ws.cle; q.re = ws.cre; q.lb = ws.clb; q.rb = ws.crb;
+  q.prom = ws.cprom; q.w = ws.cw; q.wh = ws.cwh; q.lip = ws.clip; q.rip = ws.crip; q.ccap = ccap;
+  PkPromwArgs po;
+  po.pmin = o->use_prominence ? o->prominence[0] : -INFINITY; po.pmax = o->use_prominence ? o->prominence[1] : INFINITY;
+  po.wmin = e->width[0]; po.wmax = e->width[1]; po.rel_height = e->rel_height;
+  po.wlen = e->wlen; po.use_width = e->use_width != 0;
+  PkFill none = {}, f = {};
+  f.i[0] = out.idx; f.i[1] = out.lbase; f.i[2] = out.rbase; f.i[3] = out.plateau_sizes; f.i[4] = out.left_edges;
+  f.i[5] = out.right_edges;
+  f.d[0] = out.prom; f.d[1] = out.widths; f.d[2] = out.width_heights; f.d[3] = out.left_ips; f.d[4] = out.right_ips;
+  for (int64_t r0 = 0; r0 < rows; r0 += kPkMaxGridY) {
+    a.row0 = (int32_t)r0;
+    const unsigned ry = (unsigned)std::min<int64_t>(rows - r0, kPkMaxGridY);
+    hipLaunchKernelGGL((pk_count_kernel<T, true>), dim3((unsigned)a.nseg, ry), dim3(kPkThreads), 0, st, a, ws.segcount);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(pk_scan_kernel, dim3((unsigned)rows), dim3(kPkThreads), 0, st, ws.segcount, a.nseg, ws.ccount, none, cap);
+  HIP_TRY(hipGetLastError());
+  if (ccap > 0) {
+    const unsigned gx = (unsigned)std::min<int64_t>((ccap + kPkPromWaves - 1) / kPkPromWaves, kPkPromMaxGridX);
+    for (int64_t r0 = 0; r0 < rows; r0 += kPkMaxGridY) {
+      a.row0 = (int32_t)r0;
+      const unsigned ry = (unsigned)std::min<int64_t>(rows - r0, kPkMaxGridY);
+      hipLaunchKernelGGL((pk_write_kernel<T, true>), dim3((unsigned)a.nseg, ry), dim3(kPkThreads), 0, st, a, ws.segcount, ws.cidx,
+                         ccap, PkEdges{ws.cle, ws.cre, ws.ckeep});
+      HIP_TRY(hipGetLastError());
+    }
+    if (e->use_distance) {
+      a.row0 = 0;
+      hipLaunchKernelGGL(pk_distance_kernel<T>, dim3((unsigned)rows), dim3(kPkDistThreads), 0, st, a, q, e->distance);
+      HIP_TRY(hipGetLastError());
+    }
+    for (int64_t r0 = 0; r0 < rows; r0 += kPkMaxGridY) {
+      a.row0 = (int32_t)r0;
+      const unsigned ry = (unsigned)std::min<int64_t>(rows - r0, kPkMaxGridY);
+      if (need_prom) {
+        hipLaunchKernelGGL(pk_promw_kernel<T>, dim3(gx, ry), dim3(64 * kPkPromWaves), 0, st, a, q, po);
+        HIP_TRY(hipGetLastError());
+      }
+      hipLaunchKernelGGL(pk_ccount_kernel, dim3((unsigned)ncseg, ry), dim3(kPkThreads), 0, st, q.ccount, ws.ckeep, ccap,
+                         (int32_t)r0, ncseg, ws.csegcount);
+      HIP_TRY(hipGetLastError());
+    }
+  } else {
+    HIP_TRY(hipMemsetAsync(ws.csegcount, 0, (size_t)rows * ncseg * sizeof(int32_t), st));
+  }
+  hipLaunchKernelGGL(pk_scan_kernel, dim3((unsigned)rows), dim3(kPkThreads), 0, st, ws.csegcount, ncseg, out.count, f, cap);
+  HIP_TRY(hipGetLastError());
+  if (cap > 0 && ccap > 0) {
+    for (int64_t r0 = 0; r0 < rows; r0 += kPkMaxGridY) {
+      const unsigned ry = (unsigned)std::min<int64_t>(rows - r0, kPkMaxGridY);
+      hipLaunchKernelGGL(pk_cwrite_ex_kernel, dim3((unsigned)ncseg, ry), dim3(kPkThreads), 0, st, q, (int32_t)r0, ncseg,
+                         ws.csegcount, out, cap);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  return MM_OK;
+}
+
+// whether a call needs the stages (and their workspace), or is one that mm_find_peaks answers with its own kernels
+bool pk_is_ex(const mm_peaks_opts* o, const mm_peaks_ext* e) {
+  return e && (e->use_plateau_size || e->use_distance || e->use_width || (e->wlen > 0 && o->use_prominence));
+}
+
+bool pk_shape_ok(int64_t rows, int64_t n) { return rows >= 1 && rows <= 0x7fffffff && n >= 1 && n <= kPkMaxN; }
+
+// every check, then the kernels of mm_find_peaks or the stages
+int pk_find(const mm_peaks_opts* opts, const mm_peaks_ext* ext, const void* d_x, int32_t dtype, int64_t rows, int64_t n,
+            int64_t x_stride, const int32_t* d_lo, const int32_t* d_hi, int64_t cap, const mm_peaks_out* outp, void* d_ws,
+            size_t ws_bytes, void* stream) {
+  if (!opts || !d_x || !outp || !outp->count || !d_ws || (dtype != 0 && dtype != 1)) return MM_ERR_INVALID_ARG;
+  if (!pk_shape_ok(rows, n) || x_stride < n || cap < 0 || cap > kPkMaxN) return MM_ERR_INVALID_ARG;
+  mm_peaks_out out = *outp;
+  if (cap > 0 && !out.idx) return MM_ERR_INVALID_ARG;
+  if (!pk_interval_ok(opts->height) || !pk_interval_ok(opts->threshold) || !pk_interval_ok(opts->prominence))
+    return MM_ERR_INVALID_ARG;
+  if (ext) {
+    if (!pk_interval_ok(ext->plateau_size) || !pk_interval_ok(ext->width) || !(ext->rel_height >= 0.0))
+      return MM_ERR_INVALID_ARG;
+    if ((ext->use_distance && ext->distance < 1) || ext->wlen == 1) return MM_ERR_INVALID_ARG;
+  }
+  const bool ex = pk_is_ex(opts, ext);
+  const bool need_prom = opts->use_prominence || (ex && ext->use_width);
+  if (need_prom && cap > 0 && (!out.prom || !out.lbase || !out.rbase)) return MM_ERR_INVALID_ARG;
+  const PkWs ws = pk_carve(d_ws, rows, n, ex);
+  if (ws_bytes < ws.bytes) return MM_ERR_WORKSPACE;
+  // a property of a stage that does not run is not written
+  if (!need_prom) { out.prom = nullptr; out.lbase = out.rbase = nullptr; }
+  if (!ex || !ext->use_width) { out.widths = out.width_heights = nullptr; out.left_ips = out.right_ips = nullptr; }
+  if (!ex || !ext->use_plateau_size) { out.plateau_sizes = nullptr; out.left_edges = out.right_edges = nullptr; }
+  PkArgs a;
+  a.x = d_x; a.x_stride = x_stride; a.lo = d_lo; a.hi = d_hi; a.n = (int32_t)n; a.nseg = (int32_t)pk_segs(n); a.row0 = 0;
+  a.negate = opts->negate != 0; a.use_height = opts->use_height != 0; a.use_threshold = opts->use_threshold != 0;
+  a.hmin = opts->height[0]; a.hmax = opts->height[1]; a.tmin = opts->threshold[0]; a.tmax = opts->threshold[1];
+  a.use_plateau = ex && ext->use_plateau_size != 0;
+  a.psmin = ex ? ext->plateau_size[0] : -INFINITY; a.psmax = ex ? ext->plateau_size[1] : INFINITY;
+  hipStream_t st = (hipStream_t)stream;
+  if (ex) {
+    if (dtype == 0) return pk_run_ex<float>(opts, ext, a, rows, cap, out, ws, st);
+    return pk_run_ex<double>(opts, ext, a, rows, cap, out, ws, st);
+  }
+  if (dtype == 0) return pk_run<float>(opts, a, rows, cap, out.count, out.idx, out.prom, out.lbase, out.rbase, ws, st);
+  return pk_run<double>(opts, a, rows, cap, out.count, out.idx, out.prom, out.lbase, out.rbase, ws, st);
+}
+
 }  // namespace
 
 extern "C" {
 
 size_t mm_find_peaks_workspace_bytes(int64_t rows, int64_t n) {
-  if (rows < 1 || rows > 0x7fffffff || n < 1 || n > kPkMaxN) return 0;
-  return pk_carve(nullptr, rows, n).bytes;
+  if (!pk_shape_ok(rows, n)) return 0;
+  return pk_carve(nullptr, rows, n, false).bytes;
+}
+
+size_t mm_find_peaks_ex_workspace_bytes(const mm_peaks_opts* opts, const mm_peaks_ext* ext, int64_t rows, int64_t n) {
+  if (!opts || !pk_shape_ok(rows, n)) return 0;
+  return pk_carve(nullptr, rows, n, pk_is_ex(opts, ext)).bytes;
 }
 
 int mm_find_peaks(const mm_peaks_opts* opts, const void* d_x, int32_t dtype, int64_t rows, int64_t n, int64_t x_stride,
                   const int32_t* d_lo, const int32_t* d_hi, int64_t cap, int32_t* d_count, int32_t* d_idx, double* d_prom,
                   int32_t* d_lbase, int32_t* d_rbase, void* d_ws, size_t ws_bytes, void* stream) {
-  if (!opts || !d_x || !d_count || !d_ws || (dtype != 0 && dtype != 1)) return MM_ERR_INVALID_ARG;
-  if (rows < 1 || rows > 0x7fffffff || n < 1 || n > kPkMaxN || x_stride < n || cap < 0 || cap > kPkMaxN)
-    return MM_ERR_INVALID_ARG;
-  if (cap > 0 && !d_idx) return MM_ERR_INVALID_ARG;
-  if (!pk_interval_ok(opts->height) || !pk_interval_ok(opts->threshold) || !pk_interval_ok(opts->prominence))
-    return MM_ERR_INVALID_ARG;
-  if (opts->use_prominence && cap > 0 && (!d_prom || !d_lbase || !d_rbase)) return MM_ERR_INVALID_ARG;
-  const PkWs ws = pk_carve(d_ws, rows, n);
-  if (ws_bytes < ws.bytes) return MM_ERR_WORKSPACE;
-  PkArgs a;
-  a.x = d_x; a.x_stride = x_stride; a.lo = d_lo; a.hi = d_hi; a.n = (int32_t)n; a.nseg = (int32_t)pk_segs(n); a.row0 = 0;
-  a.negate = opts->negate != 0; a.use_height = opts->use_height != 0; a.use_threshold = opts->use_threshold != 0;
-  a.hmin = opts->height[0]; a.hmax = opts->height[1]; a.tmin = opts->threshold[0]; a.tmax = opts->threshold[1];
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == 0) return pk_run<float>(opts, a, rows, cap, d_count, d_idx, d_prom, d_lbase, d_rbase, ws, st);
-  return pk_run<double>(opts, a, rows, cap, d_count, d_idx, d_prom, d_lbase, d_rbase, ws, st);
+  mm_peaks_out out = {};
+  out.count = d_count; out.idx = d_idx; out.prom = d_prom; out.lbase = d_lbase; out.rbase = d_rbase;
+  return pk_find(opts, nullptr, d_x, dtype, rows, n, x_stride, d_lo, d_hi, cap, &out, d_ws, ws_bytes, stream);
+}
+
+int mm_find_peaks_ex(const mm_peaks_opts* opts, const mm_peaks_ext* ext, const void* d_x, int32_t dtype, int64_t rows,
+                     int64_t n, int64_t x_stride, const int32_t* d_lo, const int32_t* d_hi, int64_t cap,
+                     const mm_peaks_out* out, void* d_ws, size_t ws_bytes, void* stream) {
+  return pk_find(opts, ext, d_x, dtype, rows, n, x_stride, d_lo, d_hi, cap, out, d_ws, ws_bytes, stream);
 }
 
 }  // extern "C"
