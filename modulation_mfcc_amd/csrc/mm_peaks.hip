@@ -4,14 +4,14 @@
 //   pk_count_kernel   rising edges of a segment that resolve to a peak and pass height / threshold -> count per segment
 //   pk_scan_kernel    exclusive scan of a row's segment counts; the row's total; -1 fill of the unused index slots
 //   pk_write_kernel   the same test again, plateau midpoints written at scan offset + rank (ballot / popcount)
-//   pk_prom_kernel    one wave per candidate: prominence and bases, 64 samples a step
-//   pk_ccount_kernel / pk_cwrite_kernel   the candidates the prominence interval keeps, compacted the same way
+//   pk_prom_kernel <T, false>   one wave per candidate: prominence and bases, 64 samples a step; a drop is left base -1
+//   pk_ccount_kernel / pk_cwrite_kernel   the candidates a keep array (here the left bases) keeps, compacted the same way
 // mm_find_peaks_ex adds plateau_size, distance, wlen and width as stages over the candidate list of the workspace, each
-// clearing a candidate's keep flag, and one compaction on that flag at the end:
+// clearing a candidate's keep flag, and the same compaction on that flag at the end (one driver, pk_run, for both):
 //   pk_count / pk_write <T, true>   the plateau's edges beside its midpoint, plateau_size filtered with height / threshold
 //   pk_distance_kernel    a workgroup per row: scipy's greedy selection as a fixed point, every round inside the launch
-//   pk_promw_kernel       a wave per kept candidate: prominence inside wlen, then scipy's peak_widths at rel_height
-//   pk_ccount_kernel / pk_cwrite_ex_kernel   the kept candidates and every property the caller asked for
+//   pk_prom_kernel <T, true>    a wave per kept candidate: prominence inside wlen, then scipy's peak_widths at rel_height
+//   pk_ccount_kernel / pk_cwrite_kernel   the kept candidates and every property the caller asked for
 // Every comparison is a plain IEEE one (NaN compares false, as in scipy's Cython loops); values are float64 throughout
 // (float32 input is promoted per element, exactly), so indices, bases and prominences equal scipy's bit for bit.
 #include "mm_common.h"
@@ -98,21 +98,18 @@ __device__ __forceinline__ int32_t pk_peak_at(const PkArgs& a, const PkRow<T>& r
   return mid - r.lo;
 }
 
-template <class T, bool EX>
-__global__ __launch_bounds__(kPkThreads) void pk_count_kernel(PkArgs a, int32_t* __restrict__ segcount) {
+// The count of segment blockIdx.x: the number of its elements i (kPkPer rounds of kPkThreads) for which hit(i) holds goes
+// to *dst.  A segment outside [lo, hi) (workgroup-uniform) has nothing to test.
+// (The callables of this helper and of pk_seg_compact capture kernel arguments by value: captured by reference they
+// cost registers and about a tenth more instructions; docs/experiments.md, "One driver for the peak search".)
+template <class Hit>
+__device__ __forceinline__ void pk_seg_count(int32_t lo, int32_t hi, int32_t* dst, Hit hit) {
   __shared__ int s_w[kPkWaves];
-  const int64_t row = (int64_t)a.row0 + blockIdx.y;
-  const PkRow<T> r(a, row);
   const int64_t base = (int64_t)blockIdx.x * kPkSeg;
   int cnt = 0;                                       // wave-uniform
-  if (base < r.hi && base + kPkSeg > r.lo) {
+  if (base < hi && base + kPkSeg > lo) {
 #pragma unroll
-    for (int k = 0; k < kPkPer; ++k) {
-      const int64_t i = base + k * kPkThreads + threadIdx.x;
-      int32_t le, re;
-      const bool pk = i < a.n && pk_peak_at<T, EX>(a, r, (int32_t)i, le, re) >= 0;
-      cnt += __popcll(__ballot(pk));
-    }
+    for (int k = 0; k < kPkPer; ++k) cnt += __popcll(__ballot(hit(base + k * kPkThreads + threadIdx.x)));
   }
   if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = cnt;
   __syncthreads();
@@ -120,8 +117,18 @@ __global__ __launch_bounds__(kPkThreads) void pk_count_kernel(PkArgs a, int32_t*
     int t = 0;
 #pragma unroll
     for (int w = 0; w < kPkWaves; ++w) t += s_w[w];
-    segcount[row * a.nseg + blockIdx.x] = t;
+    *dst = t;
   }
+}
+
+template <class T, bool EX>
+__global__ __launch_bounds__(kPkThreads) void pk_count_kernel(PkArgs a, int32_t* __restrict__ segcount) {
+  const int64_t row = (int64_t)a.row0 + blockIdx.y;
+  const PkRow<T> r(a, row);
+  pk_seg_count(r.lo, r.hi, segcount + row * a.nseg + blockIdx.x, [=](int64_t i) {
+    int32_t le, re;
+    return i < a.n && pk_peak_at<T, EX>(a, r, (int32_t)i, le, re) >= 0;
+  });
 }
 
 // exclusive prefix over the workgroup's 256 values (v of thread t -> sum of v of threads < t); total in *tot
@@ -201,53 +208,70 @@ struct PkEdges {
   int32_t *le, *re, *keep;
 };
 
+// The compaction of segment blockIdx.x (every thread of the workgroup calls it): hit(k, i) says whether element i, this
+// thread's of round k, stays; the ones that stay take the positions *segoff + rank, ascending, and emit(k, i, pos) writes
+// one whose position is below cap.
+template <class Hit, class Emit>
+__device__ __forceinline__ void pk_seg_compact(const int32_t* segoff, int64_t cap, Hit hit, Emit emit) {
+  __shared__ int s_c[kPkPer][kPkWaves];
+  const int64_t i0 = (int64_t)blockIdx.x * kPkSeg + threadIdx.x;
+  bool h[kPkPer];
+  uint64_t m[kPkPer];
+#pragma unroll
+  for (int k = 0; k < kPkPer; ++k) {
+    h[k] = hit(k, i0 + k * kPkThreads);
+    m[k] = __ballot(h[k]);
+    if ((threadIdx.x & 63) == 0) s_c[k][threadIdx.x >> 6] = __popcll(m[k]);
+  }
+  __syncthreads();
+  const int64_t off = *segoff;
+#pragma unroll
+  for (int k = 0; k < kPkPer; ++k) {
+    if (h[k]) {
+      const int64_t pos = off + pk_rank(m, k, s_c);
+      if (pos < cap) emit(k, i0 + k * kPkThreads, pos);
+    }
+  }
+}
+
 template <class T, bool EX>
 __global__ __launch_bounds__(kPkThreads) void pk_write_kernel(PkArgs a, const int32_t* __restrict__ segoff,
                                                               int32_t* __restrict__ idx, int64_t cap, PkEdges e) {
-  __shared__ int s_c[kPkPer][kPkWaves];
   const int64_t row = (int64_t)a.row0 + blockIdx.y;
   const PkRow<T> r(a, row);
   const int64_t base = (int64_t)blockIdx.x * kPkSeg;
   if (!(base < r.hi && base + kPkSeg > r.lo)) return;          // (workgroup-uniform)
   int32_t mid[kPkPer], le[kPkPer], re[kPkPer];
-  uint64_t m[kPkPer];
-#pragma unroll
-  for (int k = 0; k < kPkPer; ++k) {
-    const int64_t i = base + k * kPkThreads + threadIdx.x;
-    mid[k] = i < a.n ? pk_peak_at<T, EX>(a, r, (int32_t)i, le[k], re[k]) : -1;
-    m[k] = __ballot(mid[k] >= 0);
-    if ((threadIdx.x & 63) == 0) s_c[k][threadIdx.x >> 6] = __popcll(m[k]);
-  }
-  __syncthreads();
-  const int64_t off = segoff[row * a.nseg + blockIdx.x];
-#pragma unroll
-  for (int k = 0; k < kPkPer; ++k) {
-    if (mid[k] >= 0) {
-      const int64_t pos = off + pk_rank(m, k, s_c);
-      if (pos < cap) {
+  pk_seg_compact(
+      segoff + row * a.nseg + blockIdx.x, cap,
+      [=, &mid, &le, &re](int k, int64_t i) {
+        mid[k] = i < a.n ? pk_peak_at<T, EX>(a, r, (int32_t)i, le[k], re[k]) : -1;
+        return mid[k] >= 0;
+      },
+      [=, &mid, &le, &re](int k, int64_t, int64_t pos) {
         idx[row * cap + pos] = mid[k];
         if (EX) { e.le[row * cap + pos] = le[k]; e.re[row * cap + pos] = re[k]; e.keep[row * cap + pos] = 1; }
-      }
-    }
-  }
+      });
 }
 
+// The candidate list of the workspace.  A candidate keeps the slot the first compaction gave it.  mm_find_peaks has the
+// first row of arrays only and drops a candidate by a left base of -1; the stages of mm_find_peaks_ex drop one by setting
+// its keep flag to -1, later stages skip it.  Either way the last compaction removes it.
+struct PkCand {
+  int32_t* ccount;                                  // [rows] candidates per row
+  int64_t ccap;
+  int32_t *idx, *lb, *rb;                           // [rows][ccap]; idx ascending, relative to lo
+  double* prom;
+  int32_t *keep, *le, *re;                          // the stages only (NULL otherwise)
+  double *w, *wh, *lip, *rip;                       // wh holds the heights while the distance stage runs
+};
+
 // ---------------------------------------------------------------------------------------------------------------------
-// prominence (scipy's _peak_prominences, wlen=None): a wave per candidate.  Each step looks at the next 64 samples away
+// prominence (scipy's _peak_prominences): a wave per candidate.  Each step looks at the next 64 samples away
 // from the peak; the first lane whose sample is above the peak, NaN or outside the row ends the scan (ballot), the lanes
 // before it take part in a (value, distance) min-reduction in which an equal value nearer the peak wins; a step's
 // minimum replaces the running one only when strictly lower -- together scipy's "first reached with <".
 // ---------------------------------------------------------------------------------------------------------------------
-struct PkPromArgs {
-  const int32_t* ccount;    // [rows] candidates per row
-  const int32_t* cidx;      // [rows][ccap] ascending, relative to lo
-  double* cprom;            // [rows][ccap]
-  int32_t* clb;             // [rows][ccap]; -1 where the prominence interval drops the candidate
-  int32_t* crb;
-  int64_t ccap;
-  double pmin, pmax;
-};
-
 // lim: the last sample of the scan (inclusive): the row's (slice's) end, or the end of scipy's wlen window
 template <class T, int DIR>
 __device__ __forceinline__ void pk_scan_side(const PkRow<T>& r, int32_t p, int32_t lim, double vp, double& best,
@@ -274,102 +298,119 @@ __device__ __forceinline__ void pk_scan_side(const PkRow<T>& r, int32_t p, int32
   }
 }
 
-template <class T>
-__global__ __launch_bounds__(64 * kPkPromWaves) void pk_prom_kernel(PkArgs a, PkPromArgs q) {
+// scipy's _peak_widths on one side: from the peak towards its base, the first sample that is the base itself or not above
+// the evaluation height h; 64 samples a step, the first stopping lane decides (the lane at the peak itself included)
+template <class T, int DIR>
+__device__ __forceinline__ int32_t pk_cross_side(const PkRow<T>& r, int32_t p, int32_t base, double h) {
+  const int lane = threadIdx.x & 63;
+  for (int64_t step = 0;; step += 64) {
+    const int64_t i = (int64_t)p + DIR * (step + lane);
+    const bool inside = DIR < 0 ? i > base : i < base;
+    const double v = inside ? r.at((int32_t)i) : 0.0;
+    const uint64_t sm = __ballot(!inside || !(h < v));
+    if (sm) return (int32_t)((int64_t)p + DIR * (step + __ffsll((unsigned long long)sm) - 1));
+  }
+}
+
+// pmin, pmax last and the kernel's PkCand behind them, ccap second in it: what the <T, false> kernel reads is then one
+// 64-byte stretch of the kernel arguments.  On a batch a wave of that kernel lives for one candidate, and with the
+// arguments scattered over six loads it took 1.3 % longer (docs/experiments.md, "One driver for the peak search").
+struct PkPromOpts {
+  double wmin, wmax, rel_height;                    // EX only, as wlen and use_width
+  int32_t wlen, use_width;
+  double pmin, pmax;
+};
+
+// A wave per candidate: the prominence, its bases and its interval.  EX = false: every candidate, the whole slice, and a
+// candidate the interval drops gets the left base -1.  EX = true: the kept candidates, inside scipy's wlen window
+// ([p - wlen / 2, p + wlen / 2] clipped to the slice; wlen < 2: the slice), then -- for the survivors -- scipy's
+// peak_widths, operation for operation in float64 with contraction off (an fma in h or the interpolation changes the
+// last bit), and the width interval; a drop clears the keep flag.
+template <class T, bool EX>
+__global__ __launch_bounds__(64 * kPkPromWaves) void pk_prom_kernel(PkArgs a, PkPromOpts o, PkCand q) {
+#pragma clang fp contract(off)
   const int64_t row = (int64_t)a.row0 + blockIdx.y;
   const PkRow<T> r(a, row);
   const int32_t nc = (int32_t)min<int64_t>(q.ccount[row], q.ccap);
   const int w = threadIdx.x >> 6;
   for (int64_t c = (int64_t)blockIdx.x * kPkPromWaves + w; c < nc; c += (int64_t)gridDim.x * kPkPromWaves) {
-    const int32_t p = q.cidx[row * q.ccap + c] + r.lo;
+    const int64_t at = row * q.ccap + c;
+    if constexpr (EX) {
+      if (q.keep[at] < 0) continue;                   // (wave-uniform)
+    }
+    const int32_t p = q.idx[at] + r.lo;
     const double vp = r.at(p);
+    int32_t wl = r.lo, wr = r.hi - 1;
+    if constexpr (EX) {
+      if (o.wlen >= 2) {
+        wl = max(wl, p - o.wlen / 2);
+        wr = (int32_t)min<int64_t>(wr, (int64_t)p + o.wlen / 2);
+      }
+    }
     double lmin, rmin;
     int32_t lb, rb;
-    pk_scan_side<T, -1>(r, p, r.lo, vp, lmin, lb);
-    pk_scan_side<T, 1>(r, p, r.hi - 1, vp, rmin, rb);
+    pk_scan_side<T, -1>(r, p, wl, vp, lmin, lb);
+    pk_scan_side<T, 1>(r, p, wr, vp, rmin, rb);
     const double prom = vp - (lmin > rmin ? lmin : rmin);
-    const bool keep = pk_in(prom, q.pmin, q.pmax);
-    if ((threadIdx.x & 63) == 0) {
-      q.cprom[row * q.ccap + c] = prom;
-      q.clb[row * q.ccap + c] = keep ? lb - r.lo : -1;
-      q.crb[row * q.ccap + c] = rb - r.lo;
+    bool keep = pk_in(prom, o.pmin, o.pmax);
+    if constexpr (EX) {
+      double width = 0.0, h = 0.0, lip = 0.0, rip = 0.0;
+      if (keep && o.use_width) {
+        h = vp - prom * o.rel_height;                 // two roundings (contract off), as the host compiler gives scipy
+        const int32_t il = pk_cross_side<T, -1>(r, p, lb, h), ir = pk_cross_side<T, 1>(r, p, rb, h);
+        const double xl = r.at(il), xr = r.at(ir);
+        lip = (double)(il - r.lo);
+        if (xl < h) lip += (h - xl) / (r.at(il + 1) - xl);
+        rip = (double)(ir - r.lo);
+        if (xr < h) rip -= (h - xr) / (r.at(ir - 1) - xr);
+        width = rip - lip;
+        keep = pk_in(width, o.wmin, o.wmax);
+      }
+      if ((threadIdx.x & 63) == 0) {
+        q.prom[at] = prom; q.lb[at] = lb - r.lo; q.rb[at] = rb - r.lo;
+        if (o.use_width) { q.w[at] = width; q.wh[at] = h; q.lip[at] = lip; q.rip[at] = rip; }
+        if (!keep) q.keep[at] = -1;
+      }
+    } else if ((threadIdx.x & 63) == 0) {
+      q.prom[at] = prom; q.lb[at] = keep ? lb - r.lo : -1; q.rb[at] = rb - r.lo;
     }
   }
 }
 
-// keep [rows][ccap]: a candidate stays when its entry is >= 0 (the left bases of pk_prom_kernel, or the stages' flags)
+// keep [rows][ccap]: a candidate stays when its entry is >= 0 (the left bases of mm_find_peaks, or the stages' flags)
 __global__ __launch_bounds__(kPkThreads) void pk_ccount_kernel(const int32_t* __restrict__ ccount,
                                                                const int32_t* __restrict__ keep, int64_t ccap,
                                                                int32_t row0, int32_t ncseg,
                                                                int32_t* __restrict__ segcount) {
-  __shared__ int s_w[kPkWaves];
   const int64_t row = (int64_t)row0 + blockIdx.y;
   const int32_t nc = (int32_t)min<int64_t>(ccount[row], ccap);
-  const int64_t base = (int64_t)blockIdx.x * kPkSeg;
-  int cnt = 0;
-  if (base < nc) {
-#pragma unroll
-    for (int k = 0; k < kPkPer; ++k) {
-      const int64_t c = base + k * kPkThreads + threadIdx.x;
-      cnt += __popcll(__ballot(c < nc && keep[row * ccap + c] >= 0));
-    }
-  }
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int t = 0;
-#pragma unroll
-    for (int w = 0; w < kPkWaves; ++w) t += s_w[w];
-    segcount[row * ncseg + blockIdx.x] = t;
-  }
+  pk_seg_count(0, nc, segcount + row * ncseg + blockIdx.x,
+               [=](int64_t c) { return c < nc && keep[row * ccap + c] >= 0; });
 }
 
-__global__ __launch_bounds__(kPkThreads) void pk_cwrite_kernel(PkPromArgs q, int32_t row0, int32_t ncseg,
-                                                               const int32_t* __restrict__ segoff,
-                                                               int32_t* __restrict__ idx, double* __restrict__ prom,
-                                                               int32_t* __restrict__ lb, int32_t* __restrict__ rb,
-                                                               int64_t cap) {
-  __shared__ int s_c[kPkPer][kPkWaves];
+// the candidates keep keeps, and each property whose output pointer is not NULL, at scan offset + rank
+__global__ __launch_bounds__(kPkThreads) void pk_cwrite_kernel(PkCand q, const int32_t* __restrict__ keep, int32_t row0,
+                                                               int32_t ncseg, const int32_t* __restrict__ segoff,
+                                                               mm_peaks_out out, int64_t cap) {
   const int64_t row = (int64_t)row0 + blockIdx.y;
   const int32_t nc = (int32_t)min<int64_t>(q.ccount[row], q.ccap);
-  const int64_t base = (int64_t)blockIdx.x * kPkSeg;
-  if (base >= nc) return;                                      // (workgroup-uniform)
-  bool keep[kPkPer];
-  uint64_t m[kPkPer];
-#pragma unroll
-  for (int k = 0; k < kPkPer; ++k) {
-    const int64_t c = base + k * kPkThreads + threadIdx.x;
-    keep[k] = c < nc && q.clb[row * q.ccap + c] >= 0;
-    m[k] = __ballot(keep[k]);
-    if ((threadIdx.x & 63) == 0) s_c[k][threadIdx.x >> 6] = __popcll(m[k]);
-  }
-  __syncthreads();
-  const int64_t off = segoff[row * ncseg + blockIdx.x];
-#pragma unroll
-  for (int k = 0; k < kPkPer; ++k) {
-    if (keep[k]) {
-      const int64_t pos = off + pk_rank(m, k, s_c);
-      if (pos < cap) {
-        const int64_t c = row * q.ccap + base + k * kPkThreads + threadIdx.x;
-        idx[row * cap + pos] = q.cidx[c];
-        prom[row * cap + pos] = q.cprom[c];
-        lb[row * cap + pos] = q.clb[c];
-        rb[row * cap + pos] = q.crb[c];
-      }
-    }
-  }
+  if ((int64_t)blockIdx.x * kPkSeg >= nc) return;              // (workgroup-uniform)
+  pk_seg_compact(
+      segoff + row * ncseg + blockIdx.x, cap,
+      [=](int, int64_t i) { return i < nc && keep[row * q.ccap + i] >= 0; },
+      [=](int, int64_t i, int64_t pos) {
+        const int64_t c = row * q.ccap + i, d = row * cap + pos;
+        out.idx[d] = q.idx[c];
+        if (out.prom) { out.prom[d] = q.prom[c]; out.lbase[d] = q.lb[c]; out.rbase[d] = q.rb[c]; }
+        if (out.widths) out.widths[d] = q.w[c];
+        if (out.width_heights) out.width_heights[d] = q.wh[c];
+        if (out.left_ips) out.left_ips[d] = q.lip[c];
+        if (out.right_ips) out.right_ips[d] = q.rip[c];
+        if (out.plateau_sizes) out.plateau_sizes[d] = q.re[c] - q.le[c] + 1;
+        if (out.left_edges) out.left_edges[d] = q.le[c];
+        if (out.right_edges) out.right_edges[d] = q.re[c];
+      });
 }
-
-// ---------------------------------------------------------------------------------------------------------------------
-// the stages of mm_find_peaks_ex.  Candidates keep the slot the first compaction gave them; a stage drops one by setting
-// its keep flag to -1, later stages skip it, the last compaction removes it.
-// ---------------------------------------------------------------------------------------------------------------------
-struct PkCand {
-  const int32_t* ccount;    // [rows] candidates per row
-  int32_t *idx, *keep, *le, *re, *lb, *rb;          // [rows][ccap]
-  double *prom, *w, *wh, *lip, *rip;                // [rows][ccap]; wh holds the heights while the distance stage runs
-  int64_t ccap;
-};
 
 constexpr int kPkDistThreads = 1024;
 
@@ -432,111 +473,6 @@ __global__ __launch_bounds__(kPkDistThreads) void pk_distance_kernel(PkArgs a, P
   }
 }
 
-// scipy's _peak_widths on one side: from the peak towards its base, the first sample that is the base itself or not above
-// the evaluation height h; 64 samples a step, the first stopping lane decides (the lane at the peak itself included)
-template <class T, int DIR>
-__device__ __forceinline__ int32_t pk_cross_side(const PkRow<T>& r, int32_t p, int32_t base, double h) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t step = 0;; step += 64) {
-    const int64_t i = (int64_t)p + DIR * (step + lane);
-    const bool inside = DIR < 0 ? i > base : i < base;
-    const double v = inside ? r.at((int32_t)i) : 0.0;
-    const uint64_t sm = __ballot(!inside || !(h < v));
-    if (sm) return (int32_t)((int64_t)p + DIR * (step + __ffsll((unsigned long long)sm) - 1));
-  }
-}
-
-struct PkPromwArgs {
-  double pmin, pmax, wmin, wmax, rel_height;
-  int32_t wlen, use_width;
-};
-
-// A wave per kept candidate: the prominence inside scipy's wlen window ([p - wlen / 2, p + wlen / 2] clipped to the
-// slice; wlen < 2: the slice), its interval, then -- for the survivors -- scipy's peak_widths, operation for operation in
-// float64 with contraction off (an fma in h or the interpolation changes the last bit), and the width interval.
-template <class T>
-__global__ __launch_bounds__(64 * kPkPromWaves) void pk_promw_kernel(PkArgs a, PkCand q, PkPromwArgs o) {
-#pragma clang fp contract(off)
-  const int64_t row = (int64_t)a.row0 + blockIdx.y;
-  const PkRow<T> r(a, row);
-  const int32_t nc = (int32_t)min<int64_t>(q.ccount[row], q.ccap);
-  const int w = threadIdx.x >> 6;
-  for (int64_t c = (int64_t)blockIdx.x * kPkPromWaves + w; c < nc; c += (int64_t)gridDim.x * kPkPromWaves) {
-    const int64_t at = row * q.ccap + c;
-    if (q.keep[at] < 0) continue;                     // (wave-uniform)
-    const int32_t p = q.idx[at] + r.lo;
-    const double vp = r.at(p);
-    int32_t wl = r.lo, wr = r.hi - 1;
-    if (o.wlen >= 2) {
-      wl = max(wl, p - o.wlen / 2);
-      wr = (int32_t)min<int64_t>(wr, (int64_t)p + o.wlen / 2);
-    }
-    double lmin, rmin;
-    int32_t lb, rb;
-    pk_scan_side<T, -1>(r, p, wl, vp, lmin, lb);
-    pk_scan_side<T, 1>(r, p, wr, vp, rmin, rb);
-    const double prom = vp - (lmin > rmin ? lmin : rmin);
-    bool keep = pk_in(prom, o.pmin, o.pmax);
-    double width = 0.0, h = 0.0, lip = 0.0, rip = 0.0;
-    if (keep && o.use_width) {
-      h = vp - prom * o.rel_height;                   // two roundings (contract off), as the host compiler gives scipy
-      const int32_t il = pk_cross_side<T, -1>(r, p, lb, h), ir = pk_cross_side<T, 1>(r, p, rb, h);
-      const double xl = r.at(il), xr = r.at(ir);
-      lip = (double)(il - r.lo);
-      if (xl < h) lip += (h - xl) / (r.at(il + 1) - xl);
-      rip = (double)(ir - r.lo);
-      if (xr < h) rip -= (h - xr) / (r.at(ir - 1) - xr);
-      width = rip - lip;
-      keep = pk_in(width, o.wmin, o.wmax);
-    }
-    if ((threadIdx.x & 63) == 0) {
-      q.prom[at] = prom; q.lb[at] = lb - r.lo; q.rb[at] = rb - r.lo;
-      if (o.use_width) { q.w[at] = width; q.wh[at] = h; q.lip[at] = lip; q.rip[at] = rip; }
-      if (!keep) q.keep[at] = -1;
-    }
-  }
-}
-
-// the kept candidates, and each property whose output pointer is not NULL, at scan offset + rank
-__global__ __launch_bounds__(kPkThreads) void pk_cwrite_ex_kernel(PkCand q, int32_t row0, int32_t ncseg,
-                                                                  const int32_t* __restrict__ segoff, mm_peaks_out out,
-                                                                  int64_t cap) {
-  __shared__ int s_c[kPkPer][kPkWaves];
-  const int64_t row = (int64_t)row0 + blockIdx.y;
-  const int32_t nc = (int32_t)min<int64_t>(q.ccount[row], q.ccap);
-  const int64_t base = (int64_t)blockIdx.x * kPkSeg;
-  if (base >= nc) return;                                      // (workgroup-uniform)
-  bool keep[kPkPer];
-  uint64_t m[kPkPer];
-#pragma unroll
-  for (int k = 0; k < kPkPer; ++k) {
-    const int64_t c = base + k * kPkThreads + threadIdx.x;
-    keep[k] = c < nc && q.keep[row * q.ccap + c] >= 0;
-    m[k] = __ballot(keep[k]);
-    if ((threadIdx.x & 63) == 0) s_c[k][threadIdx.x >> 6] = __popcll(m[k]);
-  }
-  __syncthreads();
-  const int64_t off = segoff[row * ncseg + blockIdx.x];
-#pragma unroll
-  for (int k = 0; k < kPkPer; ++k) {
-    if (keep[k]) {
-      const int64_t pos = off + pk_rank(m, k, s_c);
-      if (pos < cap) {
-        const int64_t c = row * q.ccap + base + k * kPkThreads + threadIdx.x, d = row * cap + pos;
-        out.idx[d] = q.idx[c];
-        if (out.prom) { out.prom[d] = q.prom[c]; out.lbase[d] = q.lb[c]; out.rbase[d] = q.rb[c]; }
-        if (out.widths) out.widths[d] = q.w[c];
-        if (out.width_heights) out.width_heights[d] = q.wh[c];
-        if (out.left_ips) out.left_ips[d] = q.lip[c];
-        if (out.right_ips) out.right_ips[d] = q.rip[c];
-        if (out.plateau_sizes) out.plateau_sizes[d] = q.re[c] - q.le[c] + 1;
-        if (out.left_edges) out.left_edges[d] = q.le[c];
-        if (out.right_edges) out.right_edges[d] = q.re[c];
-      }
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
@@ -547,166 +483,122 @@ int64_t pk_max_peaks(int64_t n) { return n < 3 ? 0 : (n - 1) / 2; }
 int64_t pk_segs(int64_t n) { return std::max<int64_t>(1, (n + kPkSeg - 1) / kPkSeg); }
 
 struct PkWs {
-  int32_t *segcount, *ccount, *cidx, *clb, *crb, *csegcount;
-  double* cprom;
-  int32_t *ckeep, *cle, *cre;             // the stages of mm_find_peaks_ex only (ex)
-  double *cw, *cwh, *clip, *crip;
+  int32_t *segcount, *csegcount;
+  PkCand q;                               // the arrays of the stages are NULL unless ex
   size_t bytes;
 };
 
 PkWs pk_carve(void* d_ws, int64_t rows, int64_t n, bool ex) {
   const size_t ccap = (size_t)pk_max_peaks(n), R = (size_t)rows;
-  char* w = (char*)d_ws;
+  PkWs s = {};
   size_t o = 0;
-  PkWs s;
-  s.segcount = (int32_t*)(w + o);  o += pk_align(R * (size_t)pk_segs(n) * sizeof(int32_t));
-  s.ccount = (int32_t*)(w + o);    o += pk_align(R * sizeof(int32_t));
-  s.csegcount = (int32_t*)(w + o); o += pk_align(R * (size_t)pk_segs((int64_t)ccap) * sizeof(int32_t));
-  s.cprom = (double*)(w + o);      o += pk_align(R * ccap * sizeof(double));
-  s.cidx = (int32_t*)(w + o);      o += pk_align(R * ccap * sizeof(int32_t));
-  s.clb = (int32_t*)(w + o);       o += pk_align(R * ccap * sizeof(int32_t));
-  s.crb = (int32_t*)(w + o);       o += pk_align(R * ccap * sizeof(int32_t));
-  s.ckeep = s.cle = s.cre = nullptr;
-  s.cw = s.cwh = s.clip = s.crip = nullptr;
+  auto take = [&](size_t bytes) {
+    void* p = (char*)d_ws + o;
+    o += pk_align(bytes);
+    return p;
+  };
+  s.segcount = (int32_t*)take(R * (size_t)pk_segs(n) * sizeof(int32_t));
+  s.q.ccount = (int32_t*)take(R * sizeof(int32_t));
+  s.csegcount = (int32_t*)take(R * (size_t)pk_segs((int64_t)ccap) * sizeof(int32_t));
+  const size_t di = R * ccap * sizeof(int32_t), dd = R * ccap * sizeof(double);
+  s.q.prom = (double*)take(dd);
+  s.q.idx = (int32_t*)take(di);
+  s.q.lb = (int32_t*)take(di);
+  s.q.rb = (int32_t*)take(di);
   if (ex) {
-    s.cw = (double*)(w + o);       o += pk_align(R * ccap * sizeof(double));
-    s.cwh = (double*)(w + o);      o += pk_align(R * ccap * sizeof(double));
-    s.clip = (double*)(w + o);     o += pk_align(R * ccap * sizeof(double));
-    s.crip = (double*)(w + o);     o += pk_align(R * ccap * sizeof(double));
-    s.ckeep = (int32_t*)(w + o);   o += pk_align(R * ccap * sizeof(int32_t));
-    s.cle = (int32_t*)(w + o);     o += pk_align(R * ccap * sizeof(int32_t));
-    s.cre = (int32_t*)(w + o);     o += pk_align(R * ccap * sizeof(int32_t));
+    s.q.w = (double*)take(dd);
+    s.q.wh = (double*)take(dd);
+    s.q.lip = (double*)take(dd);
+    s.q.rip = (double*)take(dd);
+    s.q.keep = (int32_t*)take(di);
+    s.q.le = (int32_t*)take(di);
+    s.q.re = (int32_t*)take(di);
   }
+  s.q.ccap = (int64_t)ccap;
   s.bytes = o;
   return s;
 }
 
-template <class T>
-int pk_run(const mm_peaks_opts* o, PkArgs a, int64_t rows, int64_t cap, int32_t* d_count, int32_t* d_idx, double* d_prom,
-           int32_t* d_lb, int32_t* d_rb, const PkWs& ws, hipStream_t st) {
-  const bool prom = o->use_prominence != 0;
-  const int64_t ccap = pk_max_peaks(a.n);
-  const int32_t ncseg = (int32_t)pk_segs(ccap);
-  PkPromArgs q;
-  q.ccount = ws.ccount; q.cidx = ws.cidx; q.cprom = ws.cprom; q.clb = ws.clb; q.crb = ws.crb; q.ccap = ccap;
-  q.pmin = o->prominence[0]; q.pmax = o->prominence[1];
-  // without prominence the first compaction writes the outputs; with it, the candidate list of the workspace
-  int32_t* idx1 = prom ? ws.cidx : d_idx;
-  const int64_t cap1 = prom ? ccap : cap;
+// launch(r0, ry) for every chunk of at most kPkMaxGridY rows: r0 is the chunk's first row, ry the grid's y extent
+template <class F>
+hipError_t pk_rows(int64_t rows, F launch) {
   for (int64_t r0 = 0; r0 < rows; r0 += kPkMaxGridY) {
-    a.row0 = (int32_t)r0;
-    const unsigned ry = (unsigned)std::min<int64_t>(rows - r0, kPkMaxGridY);
-    hipLaunchKernelGGL((pk_count_kernel<T, false>), dim3((unsigned)a.nseg, ry), dim3(kPkThreads), 0, st, a, ws.segcount);
-    HIP_TRY(hipGetLastError());
+    launch((int32_t)r0, (unsigned)std::min<int64_t>(rows - r0, kPkMaxGridY));
+    if (hipError_t err = hipGetLastError(); err != hipSuccess) return err;
   }
-  PkFill f1 = {}, f2 = {};
-  f1.i[0] = prom ? nullptr : d_idx;
-  f2.i[0] = d_idx; f2.i[1] = d_lb; f2.i[2] = d_rb; f2.d[0] = d_prom;
-  hipLaunchKernelGGL(pk_scan_kernel, dim3((unsigned)rows), dim3(kPkThreads), 0, st, ws.segcount, a.nseg,
-                     prom ? ws.ccount : d_count, f1, cap);
-  HIP_TRY(hipGetLastError());
-  if (cap1 > 0) {
-    for (int64_t r0 = 0; r0 < rows; r0 += kPkMaxGridY) {
-      a.row0 = (int32_t)r0;
-      const unsigned ry = (unsigned)std::min<int64_t>(rows - r0, kPkMaxGridY);
-      hipLaunchKernelGGL((pk_write_kernel<T, false>), dim3((unsigned)a.nseg, ry), dim3(kPkThreads), 0, st, a, ws.segcount, idx1,
-                         cap1, PkEdges{});
-      HIP_TRY(hipGetLastError());
-    }
-  }
-  if (!prom) return MM_OK;
-  if (ccap > 0) {
-    const unsigned gx = (unsigned)std::min<int64_t>((ccap + kPkPromWaves - 1) / kPkPromWaves, kPkPromMaxGridX);
-    for (int64_t r0 = 0; r0 < rows; r0 += kPkMaxGridY) {
-      a.row0 = (int32_t)r0;
-      const unsigned ry = (unsigned)std::min<int64_t>(rows - r0, kPkMaxGridY);
-      hipLaunchKernelGGL(pk_prom_kernel<T>, dim3(gx, ry), dim3(64 * kPkPromWaves), 0, st, a, q);
-      HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(pk_ccount_kernel, dim3((unsigned)ncseg, ry), dim3(kPkThreads), 0, st, q.ccount, q.clb, ccap,
-                         (int32_t)r0, ncseg, ws.csegcount);
-      HIP_TRY(hipGetLastError());
-    }
-  } else {
-    HIP_TRY(hipMemsetAsync(ws.csegcount, 0, (size_t)rows * ncseg * sizeof(int32_t), st));
-  }
-  hipLaunchKernelGGL(pk_scan_kernel, dim3((unsigned)rows), dim3(kPkThreads), 0, st, ws.csegcount, ncseg, d_count, f2, cap);
-  HIP_TRY(hipGetLastError());
-  if (cap > 0 && ccap > 0) {
-    for (int64_t r0 = 0; r0 < rows; r0 += kPkMaxGridY) {
-      const unsigned ry = (unsigned)std::min<int64_t>(rows - r0, kPkMaxGridY);
-      hipLaunchKernelGGL(pk_cwrite_kernel, dim3((unsigned)ncseg, ry), dim3(kPkThreads), 0, st, q, (int32_t)r0, ncseg,
-                         ws.csegcount, d_idx, d_prom, d_lb, d_rb, cap);
-      HIP_TRY(hipGetLastError());
-    }
-  }
-  return MM_OK;
+  return hipSuccess;
 }
 
 bool pk_interval_ok(const double (&v)[2]) { return !std::isnan(v[0]) && !std::isnan(v[1]); }
 
-// The stages of mm_find_peaks_ex: candidates with their edges, distance, prominence (wlen) and widths, one compaction.
+// count, scan, first compaction, [distance], [prominence (+ widths)], candidate count, scan, final compaction.  e is read
+// only when staged; out holds the arrays of the conditions that run and NULL for the others.
 template <class T>
-int pk_run_ex(const mm_peaks_opts* o, const mm_peaks_ext* e, PkArgs a, int64_t rows, int64_t cap, const mm_peaks_out& out,
-              const PkWs& ws, hipStream_t st) {
-  const bool need_prom = o->use_prominence != 0 || e->use_width != 0;
-  const int64_t ccap = pk_max_peaks(a.n);
-  const int32_t ncseg = (int32_t)pk_segs(ccap);
-  PkCand q;
-  q.ccount = ws.ccount; q.idx = ws.cidx; q.keep = ws.ckeep; q.le = ws.cle; q.re = ws.cre; q.lb = ws.clb; q.rb = ws.crb;
-  q.prom = ws.cprom; q.w = ws.cw; q.wh = ws.cwh; q.lip = ws.clip; q.rip = ws.crip; q.ccap = ccap;
-  PkPromwArgs po;
+int pk_run(const mm_peaks_opts* o, const mm_peaks_ext* e, bool staged, const PkArgs& a0, int64_t rows, int64_t cap,
+           const mm_peaks_out& out, const PkWs& ws, hipStream_t st) {
+  const bool need_prom = o->use_prominence != 0 || (staged && e->use_width != 0);
+  // with neither stages nor prominence the first compaction writes the outputs; otherwise the candidate list
+  const bool direct = !staged && !need_prom;
+  const PkCand& q = ws.q;
+  const int32_t ncseg = (int32_t)pk_segs(q.ccap);
+  const int32_t* keep = staged ? q.keep : q.lb;
+  const unsigned gseg = (unsigned)a0.nseg, gcseg = (unsigned)ncseg;
+  const dim3 thr(kPkThreads);
+  PkPromOpts po = {};
   po.pmin = o->use_prominence ? o->prominence[0] : -INFINITY; po.pmax = o->use_prominence ? o->prominence[1] : INFINITY;
-  po.wmin = e->width[0]; po.wmax = e->width[1]; po.rel_height = e->rel_height;
-  po.wlen = e->wlen; po.use_width = e->use_width != 0;
-  PkFill none = {}, f = {};
+  if (staged) {
+    po.wmin = e->width[0]; po.wmax = e->width[1]; po.rel_height = e->rel_height;
+    po.wlen = e->wlen; po.use_width = e->use_width != 0;
+  }
+  PkFill f1 = {}, f = {};
+  f1.i[0] = direct ? out.idx : nullptr;
   f.i[0] = out.idx; f.i[1] = out.lbase; f.i[2] = out.rbase; f.i[3] = out.plateau_sizes; f.i[4] = out.left_edges;
   f.i[5] = out.right_edges;
   f.d[0] = out.prom; f.d[1] = out.widths; f.d[2] = out.width_heights; f.d[3] = out.left_ips; f.d[4] = out.right_ips;
-  for (int64_t r0 = 0; r0 < rows; r0 += kPkMaxGridY) {
-    a.row0 = (int32_t)r0;
-    const unsigned ry = (unsigned)std::min<int64_t>(rows - r0, kPkMaxGridY);
-    hipLaunchKernelGGL((pk_count_kernel<T, true>), dim3((unsigned)a.nseg, ry), dim3(kPkThreads), 0, st, a, ws.segcount);
-    HIP_TRY(hipGetLastError());
-  }
-  hipLaunchKernelGGL(pk_scan_kernel, dim3((unsigned)rows), dim3(kPkThreads), 0, st, ws.segcount, a.nseg, ws.ccount, none, cap);
+
+  const auto from = [&](int32_t r0) {                // the kernel arguments of the chunk that starts at row r0
+    PkArgs a = a0;
+    a.row0 = r0;
+    return a;
+  };
+  const auto count = staged ? pk_count_kernel<T, true> : pk_count_kernel<T, false>;
+  HIP_TRY(pk_rows(rows, [&](int32_t r0, unsigned ry) {
+    hipLaunchKernelGGL(count, dim3(gseg, ry), thr, 0, st, from(r0), ws.segcount);
+  }));
+  hipLaunchKernelGGL(pk_scan_kernel, dim3((unsigned)rows), thr, 0, st, ws.segcount, a0.nseg,
+                     direct ? out.count : q.ccount, f1, cap);
   HIP_TRY(hipGetLastError());
-  if (ccap > 0) {
-    const unsigned gx = (unsigned)std::min<int64_t>((ccap + kPkPromWaves - 1) / kPkPromWaves, kPkPromMaxGridX);
-    for (int64_t r0 = 0; r0 < rows; r0 += kPkMaxGridY) {
-      a.row0 = (int32_t)r0;
-      const unsigned ry = (unsigned)std::min<int64_t>(rows - r0, kPkMaxGridY);
-      hipLaunchKernelGGL((pk_write_kernel<T, true>), dim3((unsigned)a.nseg, ry), dim3(kPkThreads), 0, st, a, ws.segcount, ws.cidx,
-                         ccap, PkEdges{ws.cle, ws.cre, ws.ckeep});
+  const int64_t cap1 = direct ? cap : q.ccap;
+  if (cap1 > 0) {
+    const auto write = staged ? pk_write_kernel<T, true> : pk_write_kernel<T, false>;
+    HIP_TRY(pk_rows(rows, [&](int32_t r0, unsigned ry) {
+      hipLaunchKernelGGL(write, dim3(gseg, ry), thr, 0, st, from(r0), ws.segcount, direct ? out.idx : q.idx, cap1,
+                         PkEdges{q.le, q.re, q.keep});
+    }));
+  }
+  if (direct) return MM_OK;
+  if (q.ccap > 0) {
+    if (staged && e->use_distance) {
+      hipLaunchKernelGGL(pk_distance_kernel<T>, dim3((unsigned)rows), dim3(kPkDistThreads), 0, st, from(0), q,
+                         e->distance);
       HIP_TRY(hipGetLastError());
     }
-    if (e->use_distance) {
-      a.row0 = 0;
-      hipLaunchKernelGGL(pk_distance_kernel<T>, dim3((unsigned)rows), dim3(kPkDistThreads), 0, st, a, q, e->distance);
-      HIP_TRY(hipGetLastError());
-    }
-    for (int64_t r0 = 0; r0 < rows; r0 += kPkMaxGridY) {
-      a.row0 = (int32_t)r0;
-      const unsigned ry = (unsigned)std::min<int64_t>(rows - r0, kPkMaxGridY);
-      if (need_prom) {
-        hipLaunchKernelGGL(pk_promw_kernel<T>, dim3(gx, ry), dim3(64 * kPkPromWaves), 0, st, a, q, po);
-        HIP_TRY(hipGetLastError());
-      }
-      hipLaunchKernelGGL(pk_ccount_kernel, dim3((unsigned)ncseg, ry), dim3(kPkThreads), 0, st, q.ccount, ws.ckeep, ccap,
-                         (int32_t)r0, ncseg, ws.csegcount);
-      HIP_TRY(hipGetLastError());
-    }
+    const auto prom = staged ? pk_prom_kernel<T, true> : pk_prom_kernel<T, false>;
+    const unsigned gx = (unsigned)std::min<int64_t>((q.ccap + kPkPromWaves - 1) / kPkPromWaves, kPkPromMaxGridX);
+    HIP_TRY(pk_rows(rows, [&](int32_t r0, unsigned ry) {
+      if (need_prom) hipLaunchKernelGGL(prom, dim3(gx, ry), dim3(64 * kPkPromWaves), 0, st, from(r0), po, q);
+      hipLaunchKernelGGL(pk_ccount_kernel, dim3(gcseg, ry), thr, 0, st, q.ccount, keep, q.ccap, r0, ncseg,
+                         ws.csegcount);
+    }));
   } else {
     HIP_TRY(hipMemsetAsync(ws.csegcount, 0, (size_t)rows * ncseg * sizeof(int32_t), st));
   }
-  hipLaunchKernelGGL(pk_scan_kernel, dim3((unsigned)rows), dim3(kPkThreads), 0, st, ws.csegcount, ncseg, out.count, f, cap);
+  hipLaunchKernelGGL(pk_scan_kernel, dim3((unsigned)rows), thr, 0, st, ws.csegcount, ncseg, out.count, f, cap);
   HIP_TRY(hipGetLastError());
-  if (cap > 0 && ccap > 0) {
-    for (int64_t r0 = 0; r0 < rows; r0 += kPkMaxGridY) {
-      const unsigned ry = (unsigned)std::min<int64_t>(rows - r0, kPkMaxGridY);
-      hipLaunchKernelGGL(pk_cwrite_ex_kernel, dim3((unsigned)ncseg, ry), dim3(kPkThreads), 0, st, q, (int32_t)r0, ncseg,
-                         ws.csegcount, out, cap);
-      HIP_TRY(hipGetLastError());
-    }
+  if (cap > 0 && q.ccap > 0) {
+    HIP_TRY(pk_rows(rows, [&](int32_t r0, unsigned ry) {
+      hipLaunchKernelGGL(pk_cwrite_kernel, dim3(gcseg, ry), thr, 0, st, q, keep, r0, ncseg, ws.csegcount, out, cap);
+    }));
   }
   return MM_OK;
 }
@@ -718,7 +610,7 @@ bool pk_is_ex(const mm_peaks_opts* o, const mm_peaks_ext* e) {
 
 bool pk_shape_ok(int64_t rows, int64_t n) { return rows >= 1 && rows <= 0x7fffffff && n >= 1 && n <= kPkMaxN; }
 
-// every check, then the kernels of mm_find_peaks or the stages
+// every check, then the one driver
 int pk_find(const mm_peaks_opts* opts, const mm_peaks_ext* ext, const void* d_x, int32_t dtype, int64_t rows, int64_t n,
             int64_t x_stride, const int32_t* d_lo, const int32_t* d_hi, int64_t cap, const mm_peaks_out* outp, void* d_ws,
             size_t ws_bytes, void* stream) {
@@ -749,12 +641,8 @@ int pk_find(const mm_peaks_opts* opts, const mm_peaks_ext* ext, const void* d_x,
   a.use_plateau = ex && ext->use_plateau_size != 0;
   a.psmin = ex ? ext->plateau_size[0] : -INFINITY; a.psmax = ex ? ext->plateau_size[1] : INFINITY;
   hipStream_t st = (hipStream_t)stream;
-  if (ex) {
-    if (dtype == 0) return pk_run_ex<float>(opts, ext, a, rows, cap, out, ws, st);
-    return pk_run_ex<double>(opts, ext, a, rows, cap, out, ws, st);
-  }
-  if (dtype == 0) return pk_run<float>(opts, a, rows, cap, out.count, out.idx, out.prom, out.lbase, out.rbase, ws, st);
-  return pk_run<double>(opts, a, rows, cap, out.count, out.idx, out.prom, out.lbase, out.rbase, ws, st);
+  if (dtype == 0) return pk_run<float>(opts, ext, ex, a, rows, cap, out, ws, st);
+  return pk_run<double>(opts, ext, ex, a, rows, cap, out, ws, st);
 }
 
 }  // namespace

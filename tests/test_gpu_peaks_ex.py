@@ -308,6 +308,50 @@ def test_capacity_through_the_abi(gpu):
         assert (v[rows * cap:] == -7).all()                                         # the padding is untouched
 
 
+def test_more_rows_than_one_grid_staged(gpu):
+    """Rows beyond the grid's y limit (65 535) take further launches of every stage kernel but the distance one, whose
+    grid is the rows themselves: 65 541 rows of 9 samples, tiled from 61 distinct rows so that the oracle runs once per
+    distinct row, under all four staged conditions at once.  Each of them alone drops candidates of these rows, and
+    some but not all candidates survive the four together."""
+    import torch
+    base = np.random.default_rng(29).integers(0, 3, (61, 9)).astype(np.float64)
+    rows, cap = 65541, 4
+    pick = np.arange(rows) % 61
+    cond = dict(plateau_size=(None, 2), distance=3, prominence=(None, 1), width=(None, 3), wlen=5)
+    maxima = sum(len(ref_find_peaks(r)[0]) for r in base)
+    dropped = [maxima - sum(len(ref_find_peaks(r, **{k: cond[k]})[0]) for r in base)
+               for k in ("plateau_size", "distance", "prominence", "width")]
+    assert maxima == 110 and dropped == [3, 19, 50, 3]
+    # rows 65535 .. 65540, the second launch of each kernel, repeat the distinct rows 21 .. 26: some of their maxima
+    # survive, so a wrong first row there shows
+    assert list(pick[65535:]) == [21, 22, 23, 24, 25, 26]
+    assert sum(len(ref_find_peaks(r)[0]) for r in base[21:27]) == 10
+    assert [len(ref_find_peaks(r, **cond)[0]) for r in base[21:27]] == [1, 1, 1, 0, 1, 0]
+    d = torch.from_numpy(base).to(gpu)[torch.from_numpy(pick).to(gpu)]
+    idx, count, props = find_peaks_ex_batch(d, **cond)
+    assert tuple(idx.shape) == (rows, cap) and len(props) == 10
+    idx, count = idx.cpu().numpy(), count.cpu().numpy()
+    props = {k: v.cpu().numpy() for k, v in props.items()}
+    kept = empty = 0
+    for k in range(61):
+        want, wp = ref_find_peaks(base[k], **cond)
+        m, sel = len(want), pick == k
+        kept += m
+        empty += m == 0
+        assert (count[sel] == m).all()
+        assert (idx[sel, :m] == want).all() and (idx[sel, m:] == -1).all()
+        assert sorted(props) == sorted(wp)
+        for name, v in wp.items():
+            got = props[name][sel]
+            if v.dtype.kind == "i":
+                assert got.dtype == np.int32 and (got[:, :m] == v).all() and (got[:, m:] == -1).all(), name
+            else:                                                  # doubles as bit patterns
+                assert got.dtype == np.float64 and not np.isnan(v).any()
+                assert (got[:, :m].view(np.int64) == v.astype(np.float64).view(np.int64)).all(), name
+                assert np.isnan(got[:, m:]).all(), name
+    assert 0 < kept < maxima and (kept, empty) == (63, 12)
+
+
 def test_end_to_end_change_curve(gpu):
     """The change curve of a golden clip stays on the device from MfccPlan.mfcc_change into find_peaks_ex_batch."""
     import torch
