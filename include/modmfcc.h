@@ -409,6 +409,34 @@ int mm_pyin_f64(const mm_pyin_params* p, const mm_pyin_tables* t, const double* 
  * only when the strides are equal. */
 int mm_interp_nan_linear_f64(const double* d_x, int64_t rows, int64_t n, int64_t x_stride, double* d_y, int64_t y_stride,
                              void* stream);
+/* interp_NAN for the other kinds that need no solve over all knots (csrc/mm_interp.hip).  Valid samples are copied
+ * through; a NaN sample i with the valid neighbours k1 < i < k2 gets
+ *   PCHIP       the reference's end fix (a NaN first / last sample becomes a knot with the first / last valid value),
+ *               then scipy's PchipInterpolator over the knots: weighted harmonic mean derivatives inside, the three-point
+ *               formula with its two sign corrections at the end knots, the straight line for two knots;
+ *   NEAREST / NEAREST_UP   the value of the closer of k1, k2, a tie going to k1 / to k2; the end value outside the knots;
+ *   PREVIOUS / NEXT        the value at k1 / at k2, NaN where there is none (before the first / after the last valid sample);
+ *   ZERO        PREVIOUS, but the first valid value before the first valid sample;
+ *   SLINEAR     the straight line through k1 and k2, through the first / last two valid samples outside them
+ * as scipy.interpolate.interp1d(kind, fill_value='extrapolate') does.  Rows are independent, n <= 2^31 - 1025.  A row with
+ * no valid sample (SLINEAR: fewer than two) is copied unchanged: scipy raises, the host checks.  d_y may equal d_x when
+ * the strides are equal.  Workspace: 32 bytes per segment of 1024 samples and 16 per row.  MM_ERR_INVALID_ARG (unknown
+ * kind, NULL pointers, rows / n < 1, strides < n) or MM_ERR_WORKSPACE before any launch. */
+enum {
+  MM_INTERP_PCHIP = 0, MM_INTERP_NEAREST = 1, MM_INTERP_NEAREST_UP = 2, MM_INTERP_PREVIOUS = 3, MM_INTERP_NEXT = 4,
+  MM_INTERP_ZERO = 5, MM_INTERP_SLINEAR = 6
+};
+size_t mm_interp_nan_workspace_bytes(int32_t kind, int64_t rows, int64_t n);
+int mm_interp_nan_f64(int32_t kind, const double* d_x, int64_t rows, int64_t n, int64_t x_stride, double* d_y,
+                      int64_t y_stride, void* d_ws, size_t ws_bytes, void* stream);
+/* The regrid of read_AG50x (script/calc.py:173-219): d_out[j][c] = scipy interp1d(t_in, y[:, c], 'linear')(t_out[j]) for
+ * the float32 samples d_y [n][y_stride] (time-major, cols <= y_stride interleaved columns) -> float64 d_out [m][out_stride].
+ * Per output time the index is scipy's: the first i with t_in[i] >= t (binary search of d_t_in, ascending), clipped to
+ * [1, n - 1]; the two samples are subtracted in float32, divided by the float64 step t_in[i] - t_in[i - 1], and
+ * slope * (t - t_in[i - 1]) + y[i - 1] is taken in float64 -- scipy's arithmetic for a float32 y.  Times outside t_in
+ * extrapolate from the end interval.  MM_ERR_INVALID_ARG: NULL pointers, n < 2, cols or m < 1, strides < cols. */
+int mm_regrid_linear_f32_f64(const float* d_y, int64_t n, int64_t cols, int64_t y_stride, const double* d_t_in,
+                             const double* d_t_out, int64_t m, double* d_out, int64_t out_stride, void* stream);
 
 /* ---- peaks and troughs (MinMaxFinder, script/calc.py:651-686: scipy.signal.find_peaks) --------------- */
 /* Conditions of one call, each an interval [min, max] with -INFINITY / +INFINITY for an open side (scipy's None:

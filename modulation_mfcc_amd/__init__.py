@@ -12,6 +12,7 @@ from .calc import (get_velocity, calculate_amplitude_envelope, velocity_batch, a
                    peaks_to_list, MinMaxFinder)
 from .filters import sosfiltfilt_batch  # noqa: F401
 from .audio_io import load_audio, load_wav, resample_batch  # noqa: F401
-from .pitch import pyin_batch, pyin, interp_NAN, get_f0  # noqa: F401
+from .pitch import pyin_batch, pyin, interp_NAN, interp_nan_batch, get_f0  # noqa: F401
+from .ema import read_AG50x, read_AG50x_arrays, read_pos_header  # noqa: F401
 
 __version__ = "0.2.0"

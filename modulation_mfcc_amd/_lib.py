@@ -170,6 +170,9 @@ PROTOTYPES = {
     "mm_pyin_f32": (C.c_int, [_pyp, _pyt, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "mm_pyin_f64": (C.c_int, [_pyp, _pyt, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "mm_interp_nan_linear_f64": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp]),
+    "mm_interp_nan_workspace_bytes": (C.c_size_t, [C.c_int32, _i64, _i64]),
+    "mm_interp_nan_f64": (C.c_int, [C.c_int32, _vp, _i64, _i64, _i64, _vp, _i64, _vp, C.c_size_t, _vp]),
+    "mm_regrid_linear_f32_f64": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _vp]),
     "mm_find_peaks_workspace_bytes": (C.c_size_t, [_i64, _i64]),
     "mm_find_peaks": (C.c_int, [C.POINTER(mm_peaks_opts), _vp, C.c_int32, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp,
                                 _vp, _vp, _vp, C.c_size_t, _vp]),

@@ -6,7 +6,8 @@ the UI to the MFCC-change curve, script/main.py:668-713) and the RMS / Hilbert a
 (:221-343), the pYIN branch of ``get_f0`` with its ``interp_NAN`` (:345-592; modulation_mfcc_amd.pitch) and
 ``MinMaxFinder`` (:651-686: the peaks and troughs of a drawn curve, scipy.signal.find_peaks on the device --
 ``find_peaks_batch`` for [rows, n] device curves, ``find_peaks_ex_batch`` with scipy's remaining conditions).  Praat-backed
-functions (f0 by 'praatac' / 'praatcc', formants, RMSpraat) and the EMA reader are out of scope.
+functions (f0 by 'praatac' / 'praatcc', formants, RMSpraat) are out of scope.  ``read_AG50x`` (:173-219), the
+articulograph reader whose data that chain runs on, is modulation_mfcc_amd.ema.
 """
 from __future__ import annotations
 
@@ -14,9 +15,11 @@ import numpy as np
 from scipy.signal import savgol_filter
 
 from .filters import applyFilter
-from .pitch import get_f0, interp_NAN  # noqa: F401
+from .pitch import get_f0, interp_NAN, interp_nan_batch  # noqa: F401
+from .ema import read_AG50x, read_AG50x_arrays, read_pos_header  # noqa: F401
 
-__all__ = ["applyFilter", "get_f0", "interp_NAN", "get_velocity", "calculate_amplitude_envelope", "velocity_stencil", "velocity_batch", "apply_stencil",
+__all__ = ["applyFilter", "get_f0", "interp_NAN", "interp_nan_batch", "read_AG50x", "read_AG50x_arrays", "read_pos_header",
+           "get_velocity", "calculate_amplitude_envelope", "velocity_stencil", "velocity_batch", "apply_stencil",
            "hilbert_envelope_batch", "amplitude_envelope_batch", "find_peaks_batch", "find_peaks_ex_batch",
            "peaks_to_list", "MinMaxFinder"]
 

@@ -7,3 +7,4 @@
 #include "mm_side.hip"
 #include "mm_pitch.hip"
 #include "mm_peaks.hip"
+#include "mm_interp.hip"

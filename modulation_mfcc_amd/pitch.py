@@ -416,10 +416,75 @@ def _interp_nan_host(X, method):
     return newX
 
 
+INTERP_SEGMENT = 1024       # samples per workgroup of the segmented interp_NAN kernels (kIpSeg of csrc/mm_interp.hip)
+# interp_NAN methods of mm_interp_nan_f64 (MM_INTERP_* of include/modmfcc.h)
+_INTERP_KINDS = {"pchip": 0, "nearest": 1, "nearest-up": 2, "previous": 3, "next": 4, "zero": 5, "slinear": 6}
+_INTERP_HOST_KINDS = ("quadratic", "cubic")     # a banded solve over all knots: scipy on the host
+
+
+def _interp_kind_device(X, method):
+    import torch
+    from . import _lib
+    kind = _INTERP_KINDS[method]
+    squeeze = X.dim() == 1
+    x = X.unsqueeze(0) if squeeze else X
+    if x.dim() != 2:
+        raise ValueError("X must be [n] or [rows, n]")
+    if not x.is_floating_point():
+        raise TypeError("X must be a floating-point tensor")
+    rows, n = x.shape
+    if rows == 0 or n == 0:
+        return X.clone()
+    xd = x.to(torch.float64)
+    if xd.stride(1) != 1 or xd.stride(0) < n:
+        xd = xd.contiguous()
+    fewest = int((~torch.isnan(xd)).sum(dim=1).min())   # the one read-back: what scipy would raise for
+    if fewest == n:
+        return X.clone()
+    if method == "slinear" and fewest < 2:
+        raise ValueError("x and y arrays must have at least 2 entries")
+    if fewest < 1:
+        if method == "pchip":                            # the reference's np.argwhere(...)[0] of an empty array
+            raise IndexError("index 0 is out of bounds for axis 0 with size 0")
+        raise ValueError("cannot reshape array of size 0 into shape (0,newaxis)")     # scipy interp1d of empty x
+    y = torch.empty((rows, n), dtype=torch.float64, device=xd.device)
+    lib = _lib.load()
+    with torch.cuda.device(xd.device):
+        ws = torch.empty(int(lib.mm_interp_nan_workspace_bytes(kind, rows, n)), dtype=torch.uint8, device=xd.device)
+        _lib.check(lib.mm_interp_nan_f64(kind, xd.data_ptr(), rows, n, xd.stride(0), y.data_ptr(), n, ws.data_ptr(),
+                                         ws.numel(), C.c_void_p(torch.cuda.current_stream(xd.device).cuda_stream)),
+                   "mm_interp_nan_f64")
+    y = y.to(X.dtype)
+    return y[0] if squeeze else y
+
+
+def interp_nan_batch(x, method: str = "linear"):
+    """interp_NAN along the last axis of a CUDA(HIP) tensor [n] or [rows, n] of any float dtype, on the device only:
+    computed in float64 and cast back.  ``method``: 'linear' (mm_interp_nan_linear_f64) or one of 'pchip', 'nearest',
+    'nearest-up', 'previous', 'next', 'zero', 'slinear' (mm_interp_nan_f64; rows are cut into segments of INTERP_SEGMENT
+    samples, one workgroup each).  'quadratic' and 'cubic' need a solve over all knots: NotImplementedError here
+    (interp_NAN runs them through scipy on the host); any other name is a ValueError.  Rows with too few valid samples
+    raise what the reference raises (interp_NAN's doc string), after one read-back of the smallest count."""
+    if not _is_device_tensor(x):
+        raise TypeError("interp_nan_batch takes a CUDA(HIP) tensor; interp_NAN also takes numpy curves")
+    if method == "linear":
+        return _interp_linear_device(x)
+    if method in _INTERP_KINDS:
+        return _interp_kind_device(x, method)
+    if method in _INTERP_HOST_KINDS:
+        raise NotImplementedError(f"method={method!r} needs a banded solve over all knots; not on the device")
+    raise ValueError(f"interp_nan_batch: unknown method {method!r}")
+
+
 def interp_NAN(X, method: str = "linear"):
     """script/calc.py:345-385: NaN samples of a curve filled by interpolation.  'linear' (scipy interp1d, extrapolated at
-    the ends) runs on the device (mm_interp_nan_linear_f64) for numpy curves and CUDA(HIP) tensors ([n] or [rows, n]);
-    'pchip' and the other interp1d kinds run the reference's own scipy calls on the host (the curve is short)."""
+    the ends) runs on the device (mm_interp_nan_linear_f64) for numpy curves and CUDA(HIP) tensors ([n] or [rows, n]).
+    A CUDA(HIP) tensor stays on the device for 'pchip' (PchipInterpolator after the reference's end fix), 'nearest',
+    'nearest-up', 'previous', 'next', 'zero' and 'slinear' too (interp_nan_batch, mm_interp_nan_f64); only 'quadratic' and
+    'cubic', which solve a banded system over all knots, take a device tensor through scipy on the host and back.  A
+    numpy curve with any method but 'linear' runs the reference's own scipy calls.  On the device a row without a valid
+    sample raises IndexError under 'pchip' and scipy's ValueError for empty input otherwise; 'linear' and 'slinear' need
+    two valid samples (ValueError)."""
     if method == "linear":
         if _is_device_tensor(X):
             return _interp_linear_device(X)
@@ -430,6 +495,8 @@ def interp_NAN(X, method: str = "linear"):
         y = _interp_linear_device(torch.from_numpy(np.ascontiguousarray(a)).to(_gpu()))
         return y.cpu().numpy()
     if _is_device_tensor(X):
+        if method in _INTERP_KINDS:
+            return _interp_kind_device(X, method)
         import torch
         rows = X.cpu().numpy()
         out = _interp_nan_host(rows, method) if rows.ndim == 1 else np.stack([_interp_nan_host(r, method) for r in rows])
@@ -453,6 +520,8 @@ def get_f0(x, sr: float, method: str = "praatac", hopSize: float = 0.01, minPitc
            pyinfill_na: float = np.nan, pyincenter: bool = True, pyinpad_mode: str = "constant"):
     """script/calc.py:386-592 -> (f0, f0t).  method='pyin' runs librosa.pyin's arithmetic on the GPU (pyin_batch), the
     minMaxQuant second pass with its quantiles taken on the host as the reference does, then interp_NAN and applyFilter.
+    The curve stays on the device between them for interpUnvoiced 'linear', 'pchip', 'nearest', 'nearest-up', 'previous',
+    'next', 'zero' and 'slinear' (interp_NAN); 'quadratic' and 'cubic' go through scipy on the host.
     A numpy signal returns numpy arrays; a CUDA(HIP) tensor [n] returns f0 as a device tensor (filtered on the device)
     and f0t as numpy, like calculate_amplitude_envelope.  'praatac' / 'praatcc' call Praat (parselmouth): not part of
     this package."""
