@@ -93,6 +93,9 @@ class mm_peaks_out(C.Structure):
                                            "right_ips", "plateau_sizes", "left_edges", "right_edges")]
 
 
+MM_MAX_SEC = 16            # sections per SOS filter (mm_change.hip.inc)
+
+
 class MMError(RuntimeError):
     def __init__(self, status, what, detail=""):
         self.status = status

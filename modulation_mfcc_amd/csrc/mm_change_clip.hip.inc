@@ -275,50 +275,78 @@ static void sos_coef_of(const SosFilt& f, SosCoef<NS>* c) {
   }
 }
 
+// The two tables the scans of this file and of mm_sos_rows.hip.inc close the recursion with, for chunks of `chunk` samples:
+//   W[chunk - 1 - m] = the state m zero-input steps after a unit sample                       [chunk][2 NS]
+//   P[j] = Phi^(2^j), j < J; Phi = the transition of one chunk with zero input, stored by columns, rows 2 * (b / 2) .. only
+// Built in the host's extended precision (x87 long double, 64-bit mantissa) and rounded ONCE when stored.  The powers
+// come from repeated squaring, and with the poles within 1e-3 of the unit circle the entries of Phi^k are large against
+// what they add up to: squared in double, a 12 Hz low-pass at 48 kHz (wn = 5e-4) came out 2e-8 of its maximum away from
+// the exact result, a thousand times scipy's own rounding; with exact-to-the-last-bit tables what is left is the
+// device's double arithmetic, which is scipy's (docs/experiments.md, "The IIR filter near the unit circle").
+#include <cfloat>
+#if !defined(__HIP_DEVICE_COMPILE__)
+static_assert(LDBL_MANT_DIG >= 64, "the scan tables need an extended-precision long double on the host");
+#endif
+template <int NS>
+static void sos_scan_tables(const SosCoef<NS>& f, int chunk, int J, double* W, double* P) {
+  typedef long double xreal;
+  constexpr int S2 = 2 * NS;
+  xreal c[NS][5];
+  for (int s = 0; s < NS; ++s) for (int k = 0; k < 5; ++k) c[s][k] = (xreal)f.c[s][k];
+  // one step of the cascade (direct form II transposed) on input x
+  auto step = [&](xreal x, xreal (&z0)[NS], xreal (&z1)[NS]) {
+    for (int s = 0; s < NS; ++s) {
+      const xreal y = c[s][0] * x + z0[s];
+      z0[s] = c[s][1] * x - c[s][3] * y + z1[s];
+      z1[s] = c[s][2] * x - c[s][4] * y;
+      x = y;
+    }
+  };
+  {
+    xreal z0[NS], z1[NS];
+    for (int s = 0; s < NS; ++s) { z0[s] = 0; z1[s] = 0; }
+    for (int m = 0; m < chunk; ++m) {
+      step(m == 0 ? (xreal)1 : (xreal)0, z0, z1);
+      double* Wm = W + (size_t)(chunk - 1 - m) * S2;
+      for (int s = 0; s < NS; ++s) { Wm[2 * s] = (double)z0[s]; Wm[2 * s + 1] = (double)z1[s]; }
+    }
+  }
+  xreal A[S2][S2], B[S2][S2];
+  for (int b = 0; b < S2; ++b) {
+    xreal z0[NS], z1[NS];
+    for (int s = 0; s < NS; ++s) { z0[s] = 0; z1[s] = 0; }
+    (b & 1 ? z1 : z0)[b >> 1] = 1;
+    for (int i = 0; i < chunk; ++i) step(0, z0, z1);
+    for (int s = 0; s < NS; ++s) { A[2 * s][b] = z0[s]; A[2 * s + 1][b] = z1[s]; }
+  }
+  constexpr int TRI = 2 * NS * (NS + 1);
+  for (int j = 0; j < J; ++j) {
+    double* Pj = P + (size_t)j * TRI;
+    int e = 0;
+    for (int b = 0; b < S2; ++b) for (int a = (b & ~1); a < S2; ++a) Pj[e++] = (double)A[a][b];
+    for (int a = 0; a < S2; ++a) for (int b = 0; b < S2; ++b) {
+      xreal acc = 0;
+      for (int k = 0; k < S2; ++k) acc += A[a][k] * A[k][b];
+      B[a][b] = acc;
+    }
+    for (int a = 0; a < S2; ++a) for (int b = 0; b < S2; ++b) A[a][b] = B[a][b];
+  }
+}
+
 // chunk length, scan depth and the two tables of one filter, appended to `tab`
 template <int NS>
 static void clip_filt_of(const SosFilt& f, int n, int K, ClipFilt<NS>* g, std::vector<double>& tab) {
-  constexpr int S2 = 2 * NS;
+  constexpr int S2 = 2 * NS, TRI = 2 * NS * (NS + 1);
   sos_coef_of<NS>(f, &g->f);
   g->K = K;
   g->chunk = ((n + K - 1) / K) | 1;          // odd: the chunks of a row start in different LDS banks
   g->J = 0;
   while ((1 << g->J) < K) ++g->J;            // (K is a power of two)
-  // W[chunk - 1 - m] = the state m zero-input steps after a unit sample
+  const int J = std::max(g->J, 1);
   g->offW = (int)tab.size();
-  tab.resize(tab.size() + (size_t)g->chunk * S2);
-  {
-    double z0[NS], z1[NS];
-    for (int s = 0; s < NS; ++s) { z0[s] = 0.0; z1[s] = 0.0; }
-    for (int m = 0; m < g->chunk; ++m) {
-      double x = m == 0 ? 1.0 : 0.0;
-      for (int s = 0; s < NS; ++s) {
-        const double y = g->f.c[s][0] * x + z0[s];
-        z0[s] = g->f.c[s][1] * x - g->f.c[s][3] * y + z1[s];
-        z1[s] = g->f.c[s][2] * x - g->f.c[s][4] * y;
-        x = y;
-      }
-      double* Wm = tab.data() + g->offW + (size_t)(g->chunk - 1 - m) * S2;
-      for (int s = 0; s < NS; ++s) { Wm[2 * s] = z0[s]; Wm[2 * s + 1] = z1[s]; }
-    }
-  }
-  // P[j] = Phi^(2^j), Phi = the transition of one chunk with zero input; stored by columns, rows 2 * (b / 2) .. only
-  constexpr int TRI = 2 * NS * (NS + 1);
-  g->offP = (int)tab.size();
-  tab.resize(tab.size() + (size_t)std::max(g->J, 1) * TRI);
-  double A[S2][S2], B[S2][S2];
-  sos_chunk_phi<NS>(g->f, g->chunk, A);
-  for (int j = 0; j < std::max(g->J, 1); ++j) {
-    double* P = tab.data() + g->offP + (size_t)j * TRI;
-    int e = 0;
-    for (int b = 0; b < S2; ++b) for (int a = (b & ~1); a < S2; ++a) P[e++] = A[a][b];
-    for (int a = 0; a < S2; ++a) for (int b = 0; b < S2; ++b) {
-      double acc = 0.0;
-      for (int c = 0; c < S2; ++c) acc += A[a][c] * A[c][b];
-      B[a][b] = acc;
-    }
-    memcpy(A, B, sizeof(A));
-  }
+  g->offP = g->offW + g->chunk * S2;
+  tab.resize((size_t)g->offP + (size_t)J * TRI);
+  sos_scan_tables<NS>(g->f, g->chunk, J, tab.data() + g->offW, tab.data() + g->offP);
 }
 
 struct ClipShape { int G, K1, K2, pitch, threads; size_t lds; int64_t tab_n; };

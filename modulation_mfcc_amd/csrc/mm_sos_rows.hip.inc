@@ -472,34 +472,7 @@ template <int NS>
 static void seg_tables(const SosCoef<NS>& c, std::vector<double>& tab) {
   constexpr int S2 = 2 * NS, TRI = 2 * NS * (NS + 1);
   tab.assign((size_t)MM_SEG_CH * S2 + (size_t)MM_SEG_JT * TRI, 0.0);
-  {
-    double z0[NS], z1[NS];
-    for (int s = 0; s < NS; ++s) { z0[s] = 0.0; z1[s] = 0.0; }
-    for (int m = 0; m < MM_SEG_CH; ++m) {                  // W[CH - 1 - m] = the state m zero-input steps after a unit sample
-      double x = m == 0 ? 1.0 : 0.0;
-      for (int s = 0; s < NS; ++s) {
-        const double y = c.c[s][0] * x + z0[s];
-        z0[s] = c.c[s][1] * x - c.c[s][3] * y + z1[s];
-        z1[s] = c.c[s][2] * x - c.c[s][4] * y;
-        x = y;
-      }
-      double* Wm = tab.data() + (size_t)(MM_SEG_CH - 1 - m) * S2;
-      for (int s = 0; s < NS; ++s) { Wm[2 * s] = z0[s]; Wm[2 * s + 1] = z1[s]; }
-    }
-  }
-  double A[S2][S2], B[S2][S2];
-  sos_chunk_phi<NS>(c, MM_SEG_CH, A);
-  for (int j = 0; j < MM_SEG_JT; ++j) {
-    double* P = tab.data() + (size_t)MM_SEG_CH * S2 + (size_t)j * TRI;
-    int e = 0;
-    for (int b = 0; b < S2; ++b) for (int a = (b & ~1); a < S2; ++a) P[e++] = A[a][b];
-    for (int a = 0; a < S2; ++a) for (int b = 0; b < S2; ++b) {
-      double acc = 0.0;
-      for (int k = 0; k < S2; ++k) acc += A[a][k] * A[k][b];
-      B[a][b] = acc;
-    }
-    memcpy(A, B, sizeof(A));
-  }
+  sos_scan_tables<NS>(c, MM_SEG_CH, MM_SEG_JT, tab.data(), tab.data() + (size_t)MM_SEG_CH * S2);   // mm_change_clip.hip.inc
 }
 
 static int64_t seg_count(int64_t n_ext) { return (n_ext + MM_SEG_LEN - 1) / MM_SEG_LEN; }

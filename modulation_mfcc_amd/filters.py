@@ -82,6 +82,25 @@ def _is_device_tensor(x):
     return type(x).__module__.startswith("torch") and getattr(x, "is_cuda", False)
 
 
+def sos_sections(sos):
+    """The float64 [n_sections, 6] array of an SOS argument, or scipy's own ValueError (signal._filter_design._validate_sos:
+    same conditions, same messages) -- a flat vector of 6 k numbers, or sections scaled so that a0 != 1, are refused as
+    scipy.signal.sosfiltfilt refuses them, before anything is launched.  More sections than the kernels take
+    (_lib.MM_MAX_SEC) is the library's limit, not scipy's: MMError."""
+    from . import _lib
+    s = np.atleast_2d(np.asarray(sos, dtype=np.float64))
+    if s.ndim != 2:
+        raise ValueError("sos array must be 2D")
+    if s.shape[1] != 6:
+        raise ValueError("sos array must be shape (n_sections, 6)")
+    if not (s[:, 3] == 1).all():
+        raise ValueError("sos[:, 3] should be all ones")
+    if s.shape[0] > _lib.MM_MAX_SEC:
+        raise _lib.MMError(_lib.MM_ERR_UNSUPPORTED, f"{s.shape[0]} second-order sections: the device filters take at most "
+                                                    f"{_lib.MM_MAX_SEC}")
+    return np.ascontiguousarray(s)
+
+
 def sosfiltfilt_batch(x, sos):
     """scipy.signal.sosfiltfilt(sos, x) along the last axis of a float64 or float32 CUDA(HIP) tensor [rows, n] (or [n])
     on the device (mm_sosfiltfilt_f64 / _f32_f64): the recursion of applyFilter(filt='iir') for a whole batch of
@@ -98,7 +117,7 @@ def sosfiltfilt_batch(x, sos):
     if x2.stride(1) != 1:
         x2 = x2.contiguous()
     rows, n = x2.shape
-    s = np.ascontiguousarray(np.asarray(sos, dtype=np.float64).reshape(-1, 6))
+    s = sos_sections(sos)
     ntaps = 2 * s.shape[0] + 1 - min(int((s[:, 2] == 0).sum()), int((s[:, 5] == 0).sum()))
     if n <= 3 * ntaps:   # scipy.signal.sosfiltfilt's own check and message
         raise ValueError(f"The length of the input vector x must be greater than padlen, which is {3 * ntaps}.")

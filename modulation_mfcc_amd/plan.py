@@ -378,8 +378,9 @@ class MfccPlan:
             raise TypeError("mfcc must be a float32 CUDA(HIP) tensor [B, n_mfcc, T]")
         mfcc = mfcc.contiguous()
         B, _, T = mfcc.shape
-        s1 = np.ascontiguousarray(np.asarray(sos1, dtype=np.float64).reshape(-1, 6))
-        s2 = s1 if sos2 is None else np.ascontiguousarray(np.asarray(sos2, dtype=np.float64).reshape(-1, 6))
+        from .filters import sos_sections      # scipy's own checks and messages (2-D, six columns, a0 == 1)
+        s1 = sos_sections(sos1)
+        s2 = s1 if sos2 is None else sos_sections(sos2)
         for s in ((s1, s2) if out_filter else (s1,)):
             ntaps = 2 * s.shape[0] + 1 - min(int((s[:, 2] == 0).sum()), int((s[:, 5] == 0).sum()))
             if T <= 3 * ntaps:   # scipy.signal.sosfiltfilt's own check and message

@@ -1,12 +1,18 @@
-"""dev: random shapes / filters through the float64 IIR paths on the device against scipy on the host (GPU box):
-  * applyFilter(filt='iir') on [rows, n] curves (mm_sosfiltfilt_f64: segmented rows up to 4 sections, time-major beyond)
-  * the MFCC-change tail (mm_mfcc_change_f64: clip-resident and time-major forms)
+"""dev: random shapes / filters through the float64 IIR paths on the device (GPU box):
+  * applyFilter(filt='iir') on [rows, n] curves (mm_sosfiltfilt_f64: segmented rows up to 4 sections, time-major beyond),
+    cut-offs from 5e-4 to 0.3 of Nyquist (log-uniform), scored against tests/sos_oracle.py -- sosfiltfilt in 80-bit long
+    double -- on rows 0 and last with the rule of tests/test_gpu_sos.py: E_dev <= R * max(E_ref, 1e-15), E_ref = scipy's own
+    error against the oracle, R = 16 (docs/experiments.md, "The IIR filter near the unit circle"; known to report high- and
+    band-pass filters with an edge near 1e-3 of Nyquist on inputs with a large constant part: 20 - 100 x, E_dev ~ 1e-11)
+  * the MFCC-change tail (mm_mfcc_change_f64: clip-resident and time-major forms) against scipy (wn >= 0.02 there)
 usage: python tools/fuzz_sos.py [cases] [seed]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle")); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np, torch
 import mfcc_oracle as O
+import sos_oracle as Q
+R_SWEEP = 16.0
 from modulation_mfcc_amd import applyFilter, MfccConfig, MfccPlan, tail
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
@@ -19,7 +25,7 @@ for c in range(cases):
     order = int(rng.integers(1, 9))
     kind = ["low", "high", "band"][int(rng.integers(0, 3))]
     sr = float(rng.choice([100.0, 200.0, 16000.0]))
-    lo = float(rng.uniform(0.02, 0.3)) * sr / 2
+    lo = float(np.exp(rng.uniform(np.log(5e-4), np.log(0.3)))) * sr / 2
     cut = [lo] if kind != "band" else [lo, min(lo * float(rng.uniform(1.5, 3.0)), 0.95 * sr / 2)]
     nsec = order if kind == "band" else (order + 1) // 2
     pad = 3 * (2 * nsec + 1)
@@ -33,12 +39,17 @@ for c in range(cases):
         if "padlen" in str(e): continue
         raise
     got = applyFilter(torch.from_numpy(x).to(dev), sr, filt="iir", cutOff=cut, filtLen=order, filtType=kind).cpu().numpy()
-    err = np.abs(got - want).max() / max(np.abs(want).max(), 1e-300)
-    worst = max(worst, err)
-    if not (err <= 1e-8):
+    from modulation_mfcc_amd.filters import iir_sos
+    pick = sorted({0, rows - 1})
+    ext = Q.sosfiltfilt_ext(iir_sos(sr, cutOff=cut, filtLen=order, filtType=kind), x[pick])
+    e_ref, err = Q.rel_err(want[pick], ext), Q.rel_err(got[pick], ext)
+    ratio = err / max(e_ref, 1e-15)
+    worst = max(worst, ratio)
+    if not (ratio <= R_SWEEP):
         bad += 1
-        print(f"FILTER MISMATCH case {c}: order {order} {kind} cut {cut} sr {sr} rows {rows} n {n}: rel err {err:.2e}", flush=True)
-print(f"applyFilter iir: {cases} cases, {bad} mismatches, worst rel err {worst:.2e}, {time.time()-t0:.0f} s", flush=True)
+        print(f"FILTER MISMATCH case {c}: order {order} {kind} cut {cut} sr {sr} rows {rows} n {n}: E_dev {err:.2e} E_ref {e_ref:.2e} "
+              f"ratio {ratio:.1f}", flush=True)
+print(f"applyFilter iir: {cases} cases, {bad} beyond {R_SWEEP:g} x scipy's own error, worst ratio {worst:.2f}, {time.time()-t0:.0f} s", flush=True)
 bad2 = 0; worst2 = 0.0
 plans = {}
 for c in range(cases):
