@@ -19,6 +19,9 @@
  *   mm_sosfiltfilt_f64     <- applyFilter(filt='iir') (script/mfcc.py:29-135): scipy sosfiltfilt on a batch
  *   mm_stencil_f64         <- get_velocity (script/calc.py:593-650): np.gradient / savgol_filter /
  *                             findiff derivative of a curve -- row N2
+ *   mm_fir_filtfilt_f64,
+ *   mm_savgol_f64          <- applyFilter(filt='fir' | 'sg') and get_velocity(method='sg') with filters of any length:
+ *                             scipy filtfilt(b, 1, x) / savgol_filter(mode='interp') on a batch
  *   mm_rms_f32,
  *   mm_hilbert_envelope    <- calculate_amplitude_envelope (script/calc.py:284-343): librosa.feature.rms /
  *                             |scipy.signal.hilbert| -- row N3
@@ -266,6 +269,36 @@ typedef struct mm_stencil {
 } mm_stencil;
 int mm_stencil_f64(const mm_stencil* st, const double* d_x, int64_t rows, int64_t n, int64_t x_stride,
                    double* d_y, void* stream);
+
+/* FIR filters and Savitzky-Golay windows of ANY length (csrc/mm_longfilt.hip): what mm_stencil does not hold.  Tables are
+ * DEVICE pointers, built on the host (modulation_mfcc_amd/filters.py: fir_filtfilt_taps, savgol_tables).  d_x
+ * [rows][x_stride] -> d_y [rows][y_stride], float64 out; d_y must not overlap d_x.  A workgroup computes 2048 consecutive
+ * outputs of a row, the taps in chunks of 128 (each chunk summed on its own, then the chunk sums).  No plan, no workspace.
+ * 256 rows x 160 000 samples: 101 FIR taps 0.51 ms, a Savitzky-Golay window of 101 samples 0.34 ms.
+ *
+ * mm_fir_filtfilt_f64: scipy.signal.filtfilt(b, 1, x) with its defaults for n_taps = len(b) >= 2 taps, n > 3 n_taps -- the
+ * 'fir' branch of applyFilter (script/mfcc.py:113-126).  Both start-up transients of filtfilt lie in the cropped padding,
+ * so every output is the correlation of the odd-extended row (2 x[0] - x[m] before, 2 x[n-1] - x[n-1-m] after it; formed
+ * while the samples are staged) with d_h [2 n_taps - 1] = b (*) reversed b.  Differs from scipy's two sequential passes by
+ * rounding only.  mm_fir_filtfilt_f32_f64: the same for FLOAT32 rows, the extension formed in float32 and then widened, as
+ * scipy forms it on a float32 array (cf. mm_sosfiltfilt_f32_f64).
+ *
+ * mm_savgol_f64: scipy.signal.savgol_filter(x, window, polyorder, deriv, delta, mode='interp'), window <= n.  Outputs
+ * [window / 2, n - window / 2) are the correlation with d_c [window] = savgol_coeffs(...)[::-1] on x[i - (window - 1) / 2
+ * ...] (an even window is centred as scipy's convolve1d centres it).  The first and last window / 2 outputs come from the
+ * polynomial fitted to the first / last window: a = Q x[window] with d_q [n_basis][window] an orthonormal basis of the
+ * polynomials of degree < n_basis = polyorder + 1 on the window, then y = P a with d_p [2][window / 2][n_basis] the basis'
+ * deriv-th derivatives (delta folded in) at the first, then at the last window / 2 positions.  d_q / d_p may be NULL when
+ * window == 1.
+ *
+ * MM_ERR_INVALID_ARG before any launch: NULL pointers, rows < 1, n <= 3 n_taps or n_taps < 2, window > n or < 1, n_basis
+ * outside [1, window], strides < n, more than 2^31 - 1 tiles. */
+int mm_fir_filtfilt_f64(const double* d_x, int64_t rows, int64_t n, int64_t x_stride, const double* d_h, int32_t n_taps,
+                        double* d_y, int64_t y_stride, void* stream);
+int mm_fir_filtfilt_f32_f64(const float* d_x, int64_t rows, int64_t n, int64_t x_stride, const double* d_h, int32_t n_taps,
+                            double* d_y, int64_t y_stride, void* stream);
+int mm_savgol_f64(const double* d_x, int64_t rows, int64_t n, int64_t x_stride, const double* d_c, const double* d_q,
+                  const double* d_p, int32_t window, int32_t n_basis, double* d_y, int64_t y_stride, void* stream);
 
 /* Framewise RMS (row N3): librosa.feature.rms(y, frame_length, hop_length, center, pad_mode=
  * 'constant') as called at script/calc.py:331 / script/mfcc.py:247.  d_audio [batch][audio_stride]

@@ -10,7 +10,7 @@ from .mfcc import get_MFCCS_change, load_channel, applyFilter, get_amplitude  # 
 from .calc import (get_velocity, calculate_amplitude_envelope, velocity_batch, amplitude_envelope_batch,  # noqa: F401
                    hilbert_envelope_batch, find_peaks_batch, find_peaks_ex_batch,
                    peaks_to_list, MinMaxFinder)
-from .filters import sosfiltfilt_batch  # noqa: F401
+from .filters import sosfiltfilt_batch, fir_filtfilt_batch, savgol_batch  # noqa: F401
 from .audio_io import load_audio, load_wav, resample_batch  # noqa: F401
 from .pitch import pyin_batch, pyin, interp_NAN, interp_nan_batch, get_f0  # noqa: F401
 from .ema import read_AG50x, read_AG50x_arrays, read_pos_header  # noqa: F401

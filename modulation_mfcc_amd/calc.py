@@ -251,7 +251,8 @@ def velocity_stencil(sr: float, difference: int = 1, method: str = "gradient", w
     """The derivative of get_velocity (script/calc.py:593-650) as the banded operator mm_stencil_f64 applies:
     (stencil dict, passes).  'gradient' is ONE first-derivative stencil applied ``difference`` times, exactly
     as the reference loops np.gradient.  Raises NotImplementedError when the stencil does not fit the C
-    struct (windows wider than 16 samples, edge zones longer than 8): callers then use the host path."""
+    struct (windows wider than 16 samples, edge zones longer than 8): velocity_batch then runs 'sg' through
+    filters.savgol_batch (any window, on the device); only 'finDiff' beyond the struct uses the host path."""
     from . import _lib
     W, E = _lib.MM_ST_MAXW, _lib.MM_ST_MAXE
     if method == "gradient":
@@ -341,7 +342,8 @@ def velocity_batch(x, sr: float, difference: int = 1, method: str = "gradient", 
                    accOrder: int = 2, polyOrder: int = 2):
     """get_velocity along the LAST axis of a float64 CUDA(HIP) tensor [rows, n] (or [n]) on the device
     (mm_stencil_f64; row N2) -- e.g. on the [B, T] output of MfccPlan.mfcc_change.  'gradient' equals
-    np.gradient(x, 1/sr) bit for bit, 'sg' / 'finDiff' agree with scipy / findiff to float64 round-off.  A float32
+    np.gradient(x, 1/sr) bit for bit, 'sg' / 'finDiff' agree with scipy / findiff to float64 round-off; 'sg' windows of
+    more than 16 samples run through filters.savgol_batch (mm_savgol_f64), any width up to the row's length.  A float32
     tensor (an RMS envelope) comes back float32 for 'gradient' / 'sg', as numpy / scipy return it, to float32 round-off."""
     import torch
     if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype in (torch.float64, torch.float32)):
@@ -351,7 +353,13 @@ def velocity_batch(x, sr: float, difference: int = 1, method: str = "gradient", 
         # savgol_filter in double, rounded once); here: float64 on the device, rounded once -- equal to float32 round-off
         y = velocity_batch(x.double(), sr, difference, method, width, accOrder, polyOrder)
         return y.float() if method in ("gradient", "sg") else y
-    st, passes = velocity_stencil(sr, difference, method, width, accOrder, polyOrder)
+    try:
+        st, passes = velocity_stencil(sr, difference, method, width, accOrder, polyOrder)
+    except NotImplementedError:
+        if method != "sg":
+            raise
+        from .filters import savgol_batch       # windows beyond the stencil: mm_savgol_f64 (delta 1, as the reference calls it)
+        return savgol_batch(x, width, polyOrder, deriv=difference, delta=1.0)
     squeeze = x.dim() == 1
     x2 = x.unsqueeze(0) if squeeze else x
     if x2.dim() != 2:
@@ -376,7 +384,8 @@ def get_velocity(x: np.ndarray, sr: float, difference: int = 1, method: str = "g
     of accuracy ``accOrder``).  Unknown methods raise the reference's ValueError.
 
     A float64 CUDA(HIP) tensor (a curve, or [rows, n] curves along the last axis) is differentiated on
-    the device (``velocity_batch``); numpy input keeps the reference's host arithmetic.
+    the device (``velocity_batch``: 'gradient', 'sg' of any width, 'finDiff' stencils that fit mm_stencil; a wider
+    'finDiff' stencil makes the round trip through the host); numpy input keeps the reference's host arithmetic.
     """
     if type(x).__module__.startswith("torch") and getattr(x, "is_cuda", False):
         if method not in ("gradient", "sg", "finDiff"):

@@ -8,3 +8,4 @@
 #include "mm_pitch.hip"
 #include "mm_peaks.hip"
 #include "mm_interp.hip"
+#include "mm_longfilt.hip"

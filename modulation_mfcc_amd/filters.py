@@ -1,10 +1,12 @@
 """``applyFilter`` -- shared by the reference's script/mfcc.py:29-135 and script/calc.py:23-129
 (the two copies are identical in behaviour).  Filter DESIGN (butter, firwin, savgol_coeffs) is scipy on the
 host exactly as in the reference.  numpy input is filtered by the reference's own scipy calls; float64 curves
-that live on the GPU are filtered there (mm_sosfiltfilt_f64, mm_stencil_f64) -- SURVEY.md 8(f) row N1.
+that live on the GPU are filtered there (mm_sosfiltfilt_f64; mm_stencil_f64 for FIR filters up to 8 taps and
+Savitzky-Golay windows up to 16 samples, mm_fir_filtfilt_f64 / mm_savgol_f64 for every longer one) -- SURVEY.md 8(f) row N1.
 """
 from __future__ import annotations
 
+import collections
 import functools
 
 import numpy as np
@@ -165,6 +167,161 @@ def fir_filtfilt_stencil(taps):
                 el=el.tolist(), er=np.ascontiguousarray(er).tolist(), den_e=1.0)
 
 
+LONGFILT_TILE = 2048        # outputs per workgroup of the long-filter kernel (kLfTile of csrc/mm_longfilt.hip)
+LONGFILT_CHUNK = 128        # taps per chunk: each chunk is staged and summed on its own (kLfChunk)
+LONGFILT_MAX_TABLES = 16    # device tables kept (a 1001-tap FIR is 16 kB, a 1001 x 5 Savitzky-Golay set 60 kB)
+
+_LONG_TABLES = collections.OrderedDict()    # (kind, arguments ..., device) -> device tables, least recently used first
+
+
+def _device_tables(key, dev, build):
+    """The float64 device tables of one argument set on one device (LRU of LONGFILT_MAX_TABLES sets); ``build`` returns
+    the host arrays."""
+    import torch
+    key = key + (str(dev),)
+    if key in _LONG_TABLES:
+        _LONG_TABLES.move_to_end(key)
+    else:
+        while len(_LONG_TABLES) >= LONGFILT_MAX_TABLES:
+            torch.cuda.synchronize(dev)          # nothing in flight may still read the evicted tables
+            _LONG_TABLES.popitem(last=False)
+        _LONG_TABLES[key] = tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev) for a in build())
+    return _LONG_TABLES[key]
+
+
+def fir_filtfilt_taps(taps):
+    """h = taps (*) reversed taps, the 2 L - 1 correlation taps of scipy.signal.filtfilt(taps, 1, x) on the odd-extended
+    signal (see fir_filtfilt_stencil), h[k] on x_ext[i - (L - 1) + k]: formed in long double, rounded once."""
+    b = np.asarray(taps, dtype=np.float64).ravel().astype(np.longdouble)
+    return np.convolve(b, b[::-1]).astype(np.float64)
+
+
+def _savgol_basis(window, polyorder, deriv, pos):
+    """The polynomials of degree <= polyorder that are orthonormal over the window positions 0 .. window - 1:
+    (phi [polyorder + 1][window], their values there; dphi [polyorder + 1][len(pos)], their deriv-th derivatives with respect
+    to the position at ``pos``), in long double.  phi_{k+1} is t phi_k orthogonalised (twice) against phi_0 .. phi_k on
+    the abscissa scaled to [-1, 1] and normalised; the derivatives follow the same linear steps, (t phi_k)^(m) =
+    t phi_k^(m) + m phi_k^(m-1) -- no power basis, no least-squares solve: the fit of degree p through samples x is
+    sum_q (phi_q . x) phi_q."""
+    LD = np.longdouble
+    s = LD(2) / LD(window - 1) if window > 1 else LD(1)
+    mid = LD(window - 1) / LD(2)
+    t = (np.arange(window).astype(LD) - mid) * s
+    te = (np.asarray(pos, dtype=np.float64).astype(LD) - mid) * s
+    phi = np.zeros((polyorder + 1, window), dtype=LD)
+    d = np.zeros((deriv + 1, polyorder + 1, len(te)), dtype=LD)        # d[m][q]: m-th derivative of polynomial q at te
+    phi[0] = 1 / np.sqrt(LD(window))
+    d[0, 0] = phi[0, 0]
+    for k in range(polyorder):
+        v = t * phi[k]
+        dv = te * d[:, k]
+        dv[1:] += np.arange(1, deriv + 1).astype(LD)[:, None] * d[:-1, k]
+        for _ in range(2):
+            r = phi[:k + 1] @ v
+            v = v - r @ phi[:k + 1]
+            dv = dv - np.einsum("q,mqe->me", r, d[:, :k + 1])
+        norm = np.sqrt((v * v).sum())
+        phi[k + 1] = v / norm
+        d[:, k + 1] = dv / norm
+    return phi, d[deriv] * s ** deriv
+
+
+def savgol_tables(window_length, polyorder, deriv=0, delta=1.0):
+    """The three float64 tables of mm_savgol_f64 for scipy.signal.savgol_filter(x, window_length, polyorder, deriv, delta,
+    mode='interp'), built in long double and rounded once:
+        c [W]              interior taps as a correlation, savgol_coeffs(W, p, deriv, delta)[::-1]: c[k] on
+                           x[i - (W - 1) // 2 + k] (the fit evaluated at the window's centre (W - 1) / 2, which for an
+                           even window lies between two samples: scipy's centring)
+        Q [p + 1][W]       an orthonormal basis of the polynomials of degree <= p on the window
+        P [2][W // 2][p + 1]   the basis' deriv-th derivatives / delta^deriv at positions 0 .. W // 2 - 1 (the first outputs,
+                           fitted to x[:W]) and at W - W // 2 .. W - 1 (the last ones, fitted to x[-W:])
+    The fit's coefficients are a = Q x[window], the edge outputs P a.  Raises scipy's own ValueErrors."""
+    from scipy.signal import savgol_coeffs
+    W, p, deriv = int(window_length), int(polyorder), int(deriv)
+    savgol_coeffs(W, p, deriv=deriv, delta=delta)          # scipy's argument checks, scipy's messages
+    if deriv < 0:
+        raise ValueError("deriv must be a nonnegative integer")
+    half = W // 2
+    pos = np.concatenate(([(W - 1) / 2.0], np.arange(half), np.arange(W - half, W)))
+    phi, dphi = _savgol_basis(W, p, deriv, pos)
+    dphi = dphi / np.longdouble(delta) ** deriv
+    c = (dphi[:, 0][:, None] * phi).sum(axis=0)
+    P = np.ascontiguousarray(dphi[:, 1:].T).reshape(2, half, p + 1)
+    return c.astype(np.float64), phi.astype(np.float64), P.astype(np.float64)
+
+
+def _long_rows(x):
+    """[n] or [rows, n] -> ([rows, n] with unit inner stride and a row stride >= n: other layouts are copied, was 1-D)."""
+    squeeze = x.dim() == 1
+    x2 = x.unsqueeze(0) if squeeze else x
+    if x2.dim() != 2:
+        raise ValueError("x must be [n] or [rows, n]")
+    rows, n = x2.shape
+    if (n > 1 and x2.stride(1) != 1) or (rows > 1 and x2.stride(0) < n):
+        x2 = x2.contiguous()
+    return x2, squeeze
+
+
+def fir_filtfilt_batch(x, taps):
+    """scipy.signal.filtfilt(taps, 1, x) along the last axis of a float64 or float32 CUDA(HIP) tensor [rows, n] (or [n])
+    on the device, for ANY number of taps L >= 2 (mm_fir_filtfilt_f64 / _f32_f64): the correlation of the odd-extended rows
+    with the 2 L - 1 taps of fir_filtfilt_taps.  Rows may be strided (row stride >= n).  float64 result, as scipy returns
+    for either input type; a float32 row's extension is formed in float32, as scipy forms it.  n <= 3 L raises scipy's
+    ValueError."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    if not (_is_device_tensor(x) and x.dtype in (torch.float64, torch.float32)):
+        raise TypeError("x must be a float64 or float32 CUDA(HIP) tensor")
+    b = np.asarray(taps, dtype=np.float64).ravel()
+    L = len(b)
+    if L < 2:
+        raise ValueError("fir_filtfilt_batch needs at least two taps")
+    x2, squeeze = _long_rows(x)
+    rows, n = x2.shape
+    if n <= 3 * L:      # scipy.signal.filtfilt's own check and message
+        raise ValueError(f"The length of the input vector x must be greater than padlen, which is {3 * L}.")
+    out = torch.empty((rows, n), dtype=torch.float64, device=x.device)
+    if rows:
+        (h,) = _device_tables(("fir", b.tobytes()), x.device, lambda: (fir_filtfilt_taps(b),))
+        lib = _lib.load()
+        fn, name = (lib.mm_fir_filtfilt_f64, "mm_fir_filtfilt_f64") if x2.dtype == torch.float64 else \
+            (lib.mm_fir_filtfilt_f32_f64, "mm_fir_filtfilt_f32_f64")
+        with torch.cuda.device(x.device):
+            _lib.check(fn(x2.data_ptr(), rows, n, x2.stride(0) if rows > 1 else n, h.data_ptr(), L, out.data_ptr(), n,
+                          C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), name)
+    return out[0] if squeeze else out
+
+
+def savgol_batch(x, window_length, polyorder, deriv=0, delta=1.0):
+    """scipy.signal.savgol_filter(x, window_length, polyorder, deriv=deriv, delta=delta, mode='interp') along the last axis
+    of a float64 or float32 CUDA(HIP) tensor [rows, n] (or [n]) on the device, for ANY window_length <= n (mm_savgol_f64,
+    tables: savgol_tables).  Rows may be strided.  A float32 tensor comes back float32, filtered in float64 and rounded
+    once, as scipy does.  Bad arguments raise scipy's ValueErrors."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    if not (_is_device_tensor(x) and x.dtype in (torch.float64, torch.float32)):
+        raise TypeError("x must be a float64 or float32 CUDA(HIP) tensor")
+    W, p, deriv, delta = int(window_length), int(polyorder), int(deriv), float(delta)
+    c, q, pe = _device_tables(("sg", W, p, deriv, delta), x.device, lambda: savgol_tables(W, p, deriv, delta))
+    was_f32 = x.dtype == torch.float32
+    x2, squeeze = _long_rows(x.double() if was_f32 else x)
+    rows, n = x2.shape
+    if W > n:           # scipy.signal.savgol_filter's own check and message
+        raise ValueError("If mode is 'interp', window_length must be less than or equal to the size of x.")
+    out = torch.empty((rows, n), dtype=torch.float64, device=x.device)
+    if rows:
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().mm_savgol_f64(x2.data_ptr(), rows, n, x2.stride(0) if rows > 1 else n, c.data_ptr(),
+                                                 q.data_ptr(), pe.data_ptr(), W, p + 1, out.data_ptr(), n,
+                                                 C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)),
+                       "mm_savgol_f64")
+    if was_f32:
+        out = out.float()
+    return out[0] if squeeze else out
+
+
 def _stencil_rows(x, st):
     import torch
     from .calc import apply_stencil
@@ -180,12 +337,13 @@ def _stencil_rows(x, st):
 
 def _apply_filter_device(x, sr, kind, *, filt, cutOff, filtLen, polyOrd, coeffs):
     """applyFilter for float64 CUDA(HIP) curves ([n] or [rows, n], along the last axis): 'iir' through
-    mm_sosfiltfilt_f64, 'sg' and 'fir' through the banded-operator kernel (mm_stencil_f64).  Windows / tap
-    counts beyond the C struct (Savitzky-Golay windows over 16 samples, FIR filters over 8 taps) make the round
-    trip through the host (the reference's own scipy calls)."""
+    mm_sosfiltfilt_f64, 'sg' and 'fir' through the banded-operator kernel (mm_stencil_f64) where the filter fits its C
+    struct (Savitzky-Golay windows up to 16 samples, FIR filters up to 8 taps: results unchanged), longer ones through
+    savgol_batch / fir_filtfilt_batch.  Only what scipy itself rejects (a single FIR tap) still goes to the reference's
+    own scipy call on the host, for its exception."""
     import torch
     was_f32 = x.dtype == torch.float32
-    x_in = x                                # (the host round trip below hands scipy the caller's own type)
+    x_in = x                                # (the float32 entry points and scipy below get the caller's own type)
     if filt == "iir" and was_f32:
         pass                                # float32 curves keep their type up to the kernel (odd extension in float32)
     elif x.dtype != torch.float64:
@@ -201,12 +359,9 @@ def _apply_filter_device(x, sr, kind, *, filt, cutOff, filtLen, polyOrd, coeffs)
         if len(cutOff) != 1:
             raise Exception(_MSG_SG)
         from .calc import velocity_batch
-        try:
-            y = velocity_batch(x, 1.0, 0, "sg", filtLen, 2, polyOrd)
-            # scipy.signal.savgol_filter keeps a float32 curve float32 (it correlates in double and rounds once): so here
-            return y.float() if was_f32 else y
-        except NotImplementedError:
-            pass
+        y = velocity_batch(x, 1.0, 0, "sg", filtLen, 2, polyOrd)       # (any window: the stencil, beyond it savgol_batch)
+        # scipy.signal.savgol_filter keeps a float32 curve float32 (it correlates in double and rounds once): so here
+        return y.float() if was_f32 else y
     if filt == "fir":
         taps = np.asarray(coeffs) if coeffs is not None else \
             _sig.firwin(filtLen, _band_edges(cutOff, sr, kind), window=("kaiser", 7.4), pass_zero=kind)
@@ -228,7 +383,9 @@ def _apply_filter_device(x, sr, kind, *, filt, cutOff, filtLen, polyOrd, coeffs)
                 y = _stencil_rows(ext.double(), st)[:, pad:pad + n]
                 return y[0] if x_in.dim() == 1 else y
             return _stencil_rows(x, st)
-    if filt in ("fir", "sg"):
+        if np.size(taps) >= 2:                 # more than 8 taps: the long kernel (float32 rows through _f32_f64)
+            return fir_filtfilt_batch(x_in if was_f32 else x, taps)
+        # a single tap: scipy's own call, for scipy's own exception
         y = applyFilter(x_in.cpu().numpy(), sr, filt=filt, cutOff=cutOff, filtLen=filtLen,
                         filtType=kind[:-4], polyOrd=polyOrd, coeffs=coeffs)
         return torch.from_numpy(np.ascontiguousarray(y)).to(x.device)
