@@ -14,6 +14,8 @@
  *                             "% HBM roofline (rFFT)" metric of BASELINE.json)
  *   mm_modspec_f32         <- row A8: rFFT over every coefficient's time trajectory
  *                             (build-defined; no reference site)
+ *   mm_mfcc_ragged_f32     <- the same MFCC (and row A8) for a padded batch with one length per clip, each clip as if
+ *                             it were called alone (build-defined; no reference site)
  *   mm_mfcc_change_f64     <- script/mfcc.py:392-427 (drop c0, Butterworth sosfiltfilt,
  *                             gradient or Savitzky-Golay derivative, norm, output filter) -- row N1
  *   mm_sosfiltfilt_f64     <- applyFilter(filt='iir') (script/mfcc.py:29-135): scipy sosfiltfilt on a batch
@@ -201,6 +203,27 @@ int mm_modspec_f32(mm_plan* plan, const float* d_mfcc, int64_t batch, int64_t n_
 int mm_mfcc_modspec_f32(mm_plan* plan, const float* d_audio, int64_t batch, int64_t n_samples,
                         int64_t audio_stride, float* d_mfcc, float* d_modspec, void* d_workspace,
                         size_t workspace_bytes, void* stream);
+
+/* Ragged batches (csrc/mm_ragged.hip; no reference site: the reference takes one clip per call): a padded batch
+ * d_audio [batch][audio_stride] with n_samples = the longest clip and d_lengths (DEVICE, int64 [batch]) the valid
+ * samples of every clip.  With T_b = mm_num_frames(lengths[b]) and T_max = mm_num_frames(n_samples):
+ *   d_mfcc [batch][n_mfcc][T_max]: columns [0, T_b) = the MFCC of clip b ALONE as mm_mfcc_f32 defines it (its own centre
+ *     padding at its own end, the top_db maximum over its own n_mels x T_b values), columns [T_b, T_max) = 0.0f;
+ *   d_modspec (may be NULL) complex64 [batch][n_mfcc][n_mod / 2 + 1], n_mod = mm_mod_fft_len(T_max): mm_modspec_f32 of
+ *     d_mfcc, i.e. the rFFT of every clip's own T_b columns zero-padded to the batch's n_mod.
+ * Samples at and beyond lengths[b] never enter a result, whatever they hold (NaN, Inf, another clip's audio); a row's
+ * result does not depend on the other rows (bit for bit, for one n_samples).  A length outside [1, n_samples] is clamped
+ * into it on the device: a wrong row, never an access out of bounds.  Every plan and kernel path; asynchronous on
+ * `stream`, no allocation, no synchronisation.  The launches: the plan's unclamped log-mel (mm_logmel_f32) over the
+ * batch as it lies, the same over one short patch row per clip that redoes the few frames reaching past the clip's end,
+ * a per-clip maximum, clamp + DCT-II, and the trajectory rFFT.  MM_ERR_UNSUPPORTED when d_modspec is
+ * given and n_mod > 8192 (pass NULL and transform d_mfcc with mm_hilbert_rfft_f32), and for a plan with |preemph| > 1 (the
+ * patch row continues a clip with preemph^k y[L - 1], which must not grow); MM_ERR_INVALID_ARG / MM_ERR_WORKSPACE
+ * as mm_mfcc_f32.  Workspace: mm_ragged_workspace_bytes() (0 for invalid arguments). */
+size_t mm_ragged_workspace_bytes(const mm_plan* plan, int64_t batch, int64_t n_samples);
+int mm_mfcc_ragged_f32(mm_plan* plan, const float* d_audio, int64_t batch, int64_t n_samples, int64_t audio_stride,
+                       const int64_t* d_lengths, float* d_mfcc, float* d_modspec, void* d_workspace, size_t ws_bytes,
+                       void* stream);
 
 /* MFCC-change tail (script/mfcc.py:392-427, outFilter 'iir' low-pass or None): d_mfcc [batch][n_mfcc]
  * [n_frames] f32 -> d_change [batch][n_frames] f64.  diff_method 0 = np.gradient (diffMethod='grad',

@@ -141,6 +141,8 @@ PROTOTYPES = {
     "mm_stft_power_f32": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     "mm_rfft_f32": (C.c_int, [_vp, _vp, _i64, _i64, _i64, C.c_int32, _vp, _vp]),
     "mm_modspec_f32": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp]),
+    "mm_ragged_workspace_bytes": (C.c_size_t, [_vp, _i64, _i64]),
+    "mm_mfcc_ragged_f32": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "mm_mfcc_change_f64": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int32, C.c_int32, _vp, C.c_int32, _vp,
                                      C.c_int32, _vp, _vp, C.c_size_t, _vp]),
     "mm_sosfiltfilt_f64": (C.c_int, [_vp, _i64, _i64, _i64, _vp, C.c_int32, _vp, _vp, C.c_size_t, _vp]),

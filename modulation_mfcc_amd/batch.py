@@ -23,6 +23,40 @@ def mfcc_modspec_batch(audio, cfg: MfccConfig, mfcc_out=None, mod_out=None):
     return get_plan(cfg).mfcc_modspec(audio, out=mfcc_out, out_mod=mod_out)     # one launch where the plan can
 
 
+def mfcc_ragged_batch(audio, lengths, cfg: MfccConfig, out=None):
+    """Padded batch [B, n_max] + one length per clip -> (MFCC [B, n_mfcc, T_max], frames [B]): every clip's MFCC as
+    mfcc_batch gives it for that clip alone in the columns [0, frames[b]), zeros behind them; what the padding holds
+    (zeros, NaN, another clip) never matters.  See MfccPlan.mfcc_ragged."""
+    return get_plan(cfg).mfcc_ragged(audio, lengths, out=out)
+
+
+def mfcc_modspec_ragged_batch(audio, lengths, cfg: MfccConfig, mfcc_out=None, mod_out=None):
+    """mfcc_ragged_batch and the modulation spectrum of every clip's own frames on the batch's one modulation-frequency
+    axis -> (MFCC, spectrum complex64 [B, n_mfcc, n_mod/2+1], frames)."""
+    return get_plan(cfg).mfcc_modspec_ragged(audio, lengths, out=mfcc_out, out_mod=mod_out)
+
+
+def pack_clips(clips):
+    """A list of 1-D float32 tensors (one device) -> (audio [B, n_max] on that device, lengths int64 [B] on the host) for
+    the ragged calls.  The padding behind each clip is left as allocated: the ragged calls never read it into a result."""
+    import torch
+    clips = list(clips)
+    if not clips:
+        raise ValueError("pack_clips: no clips")
+    for c in clips:
+        if not (isinstance(c, torch.Tensor) and c.dtype == torch.float32 and c.dim() == 1):
+            raise TypeError("pack_clips: every clip must be a 1-D float32 tensor")
+        if c.device != clips[0].device:
+            raise ValueError(f"pack_clips: clips on {clips[0].device} and {c.device}")
+        if c.shape[0] < 1:
+            raise ValueError("pack_clips: empty clip")
+    lengths = torch.tensor([c.shape[0] for c in clips], dtype=torch.int64)
+    audio = torch.empty((len(clips), int(lengths.max())), dtype=torch.float32, device=clips[0].device)
+    for b, c in enumerate(clips):
+        audio[b, :c.shape[0]].copy_(c, non_blocking=True)
+    return audio, lengths
+
+
 def rfft_batch(rows, n: int, cfg: MfccConfig = None, out=None):
     """Stage-isolated batched rFFT (the kernel the '% HBM roofline (rFFT)' metric is quoted on)."""
     return get_plan(cfg or MfccConfig()).rfft(rows, n, out=out)

@@ -9,3 +9,4 @@
 #include "mm_peaks.hip"
 #include "mm_interp.hip"
 #include "mm_longfilt.hip"
+#include "mm_ragged.hip"

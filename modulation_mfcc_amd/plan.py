@@ -134,6 +134,31 @@ def _torch():
     return torch
 
 
+def check_lengths(lengths, batch, n_samples, device=None):
+    """The `lengths` argument of the ragged calls: one valid sample count per clip of a padded [batch, n_samples] batch.
+
+    A host sequence, numpy array or CPU tensor of integers is validated here -- shape [batch], every value in
+    [1, n_samples], ValueError otherwise -- and returned as an int64 numpy array.  An int64 tensor on `device` (a
+    CUDA(HIP) device) is returned as it is, with no read-back: the kernels clamp its values into [1, n_samples]."""
+    torch = _torch()
+    if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+        if lengths.dtype != torch.int64:
+            raise TypeError(f"lengths on the device must be int64, got {lengths.dtype}")
+        if tuple(lengths.shape) != (int(batch),):
+            raise ValueError(f"lengths must have shape ({int(batch)},), got {tuple(lengths.shape)}")
+        if device is not None and lengths.device != torch.device(device):
+            raise ValueError(f"lengths is on {lengths.device}, the plan on {device}")
+        return lengths.contiguous()
+    arr = lengths.numpy() if isinstance(lengths, torch.Tensor) else np.asarray(lengths)
+    if arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer):
+        raise TypeError(f"lengths must be integers, got {arr.dtype}")
+    if arr.shape != (int(batch),):
+        raise ValueError(f"lengths must have shape ({int(batch)},), got {arr.shape}")
+    if int(arr.min()) < 1 or int(arr.max()) > int(n_samples):
+        raise ValueError(f"lengths must lie in [1, {int(n_samples)}], got {int(arr.min())} .. {int(arr.max())}")
+    return np.ascontiguousarray(arr, dtype=np.int64)
+
+
 class MfccPlan:
     """Owns one ``mm_plan`` on the current CUDA(HIP) device.  Raises when no GPU is present.
 
@@ -294,6 +319,70 @@ class MfccPlan:
                                                      out_mod.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
                        "mm_mfcc_modspec_f32")
         return out, out_mod
+
+    # ---- ragged batches: a padded batch and a length per clip -----------------------------------
+    def ragged_workspace(self, batch, n_samples):
+        """The plan's workspace, grown to what mm_mfcc_ragged_f32 needs (the buffer workspace() hands out)."""
+        torch = _torch()
+        need = int(self._lib.mm_ragged_workspace_bytes(self._h, batch, n_samples))
+        if need == 0:
+            raise ValueError("mm_ragged_workspace_bytes: invalid arguments")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def _ragged_lengths(self, lengths, B, n):
+        """(int64 device tensor [B] for the kernels, frames [B] int64 on the device) -- no synchronisation: host lengths
+        are validated on the host and uploaded on the current stream, device lengths go through untouched."""
+        torch = _torch()
+        lens = check_lengths(lengths, B, n, self.device)
+        hop, odd = self.cfg.hop_length, self.cfg.n_fft - 2 * (self.cfg.n_fft // 2)      # frames = 1 + (L - odd) // hop
+        if not isinstance(lens, torch.Tensor):
+            both = torch.from_numpy(np.stack([lens, 1 + (lens - odd) // hop])).to(self.device, non_blocking=True)   # one copy
+            return both[0], both[1]
+        return lens, torch.div(lens.clamp(1, n).add_(hop - odd), hop, rounding_mode="floor")
+
+    def _ragged(self, audio, lengths, out, out_mod, want_mod):
+        torch = _torch()
+        audio = self._check_audio(audio)
+        B, n = audio.shape
+        T = self.cfg.num_frames(n)
+        lens, frames = self._ragged_lengths(lengths, B, n)
+        if out is None:
+            out = torch.empty((B, self.cfg.n_mfcc, T), dtype=torch.float32, device=self.device)
+        else:
+            self._check_out(out, (B, self.cfg.n_mfcc, T), torch.float32, "mfcc")
+        nm = self.cfg.mod_fft_len(T) if want_mod else 0
+        if want_mod:
+            if out_mod is None:
+                out_mod = torch.empty((B, self.cfg.n_mfcc, nm // 2 + 1), dtype=torch.complex64, device=self.device)
+            else:
+                self._check_out(out_mod, (B, self.cfg.n_mfcc, nm // 2 + 1), torch.complex64, "modspec")
+        fused_mod = want_mod and nm <= 8192
+        ws = self.ragged_workspace(B, n)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.mm_mfcc_ragged_f32(self._h, audio.data_ptr(), B, n, audio.stride(0), lens.data_ptr(),
+                                                    out.data_ptr(), out_mod.data_ptr() if fused_mod else None,
+                                                    ws.data_ptr(), ws.numel(), self._stream()),
+                       "mm_mfcc_ragged_f32")
+        if want_mod and not fused_mod:
+            self.modspec(out, out=out_mod)      # more than 8192 frames per clip: the transform in global memory
+        return out, out_mod, frames
+
+    def mfcc_ragged(self, audio, lengths, out=None):
+        """Padded batch [B, n_max] float32 on the device + `lengths` [B] -> (MFCC [B, n_mfcc, T_max], frames [B] int64 on the
+        device).  mfcc[b, :, :frames[b]] is the MFCC of audio[b, :lengths[b]] as mfcc() gives it for that clip alone (its
+        own centre padding, its own top_db maximum), mfcc[b, :, frames[b]:] is 0.  The samples at and beyond lengths[b]
+        never enter a result, whatever they hold.  lengths: a host sequence / numpy array / CPU tensor of integers
+        (validated here: ValueError outside [1, n_max]) or an int64 device tensor (passed through with no read-back)."""
+        out, _, frames = self._ragged(audio, lengths, out, None, False)
+        return out, frames
+
+    def mfcc_modspec_ragged(self, audio, lengths, out=None, out_mod=None):
+        """mfcc_ragged() and the modulation spectrum of its result -> (MFCC, complex64 [B, n_mfcc, n_mod/2+1], frames): the
+        rFFT of every clip's own frames zero-padded to n_mod = mod_fft_len(T_max), one modulation-frequency axis per
+        batch; bit for bit modspec() of the ragged MFCC."""
+        return self._ragged(audio, lengths, out, out_mod, True)
 
     def logmel(self, audio):
         """Unclamped 10*log10(max(amin, mel)) [B, n_mels, T] and the per-clip max [B]."""

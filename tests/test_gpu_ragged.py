@@ -1,0 +1,338 @@
+"""GPU (-m gpu): ragged batches -- a padded batch [B, n_max] and a length per clip (mm_mfcc_ragged_f32, MfccPlan.mfcc_ragged /
+mfcc_modspec_ragged, mfcc_ragged_batch, pack_clips).
+
+The expected value is always the numpy reference on the clip ALONE: O.mfcc(y[:L_b], cfg) under conftest.mfcc_close (the
+project's tolerance), O.modspec of it at the batch's n_mod within 1e-4 of its maximum (as test_modspec_matches_oracle).
+Inputs are O.synth_clip; what lies behind a clip's end is filled with NaN unless a test says otherwise."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+import mfcc_oracle as O
+from conftest import mfcc_close
+
+pytestmark = pytest.mark.gpu
+
+C1 = dict(sr=16000, n_fft=512, win_length=400, hop_length=160, n_mels=40, n_mfcc=13, fmin=100.0, fmax=8000.0)
+C3 = dict(sr=48000, n_fft=2048, win_length=1200, hop_length=480, n_mels=80, n_mfcc=40, fmin=100.0, fmax=10000.0)
+REF_DEFAULT = dict(sr=10000, n_fft=512, win_length=250, hop_length=50, n_mels=128, n_mfcc=13, fmin=100.0, fmax=10000.0)
+N_MAX_1 = 12001
+LENGTHS_1 = (1, 3, 159, 160, 161, 255, 256, 257, 511, 512, 513, 4097, 10239, 10240, 10241, 12001)
+
+
+def _key(kw):
+    return tuple(sorted(kw.items()))
+
+
+def _ocfg(kw):
+    return O.OracleConfig(**{**kw, "top_db": None if kw.get("top_db", 80.0) < 0 else kw.get("top_db", 80.0)})
+
+
+@functools.lru_cache(maxsize=None)
+def _clip(seed, n_max, sr, kind="am"):
+    y = O.synth_clip(seed, n_max, sr, kind)
+    y.setflags(write=False)
+    return y
+
+
+@functools.lru_cache(maxsize=None)
+def _want(key, seed, n_max, L):
+    """The reference MFCC of clip `seed` cut to L samples, alone (computed once, shared, read-only)."""
+    kw = dict(key)
+    m = O.mfcc(_clip(seed, n_max, kw["sr"])[:L], _ocfg(kw))
+    m.setflags(write=False)
+    return m
+
+
+def _batch(kw, n_max, lengths, fill=np.nan):
+    """Rows: clip b = synth_clip(seed b) cut to lengths[b], everything behind it = fill."""
+    a = np.stack([_clip(b, n_max, kw["sr"]) for b in range(len(lengths))]).copy()
+    for b, L in enumerate(lengths):
+        a[b, L:] = fill
+    return a
+
+
+def _plan(kw):
+    from modulation_mfcc_amd import MfccConfig, get_plan
+    return get_plan(MfccConfig(**kw))
+
+
+def _dev(x, gpu):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(x)).to(gpu)
+
+
+def _check_rows(kw, n_max, lengths, out, frames, what):
+    """Every clip against the reference on the clip alone, exact zeros behind its frames, frames == num_frames(L)."""
+    from modulation_mfcc_amd import MfccConfig
+    cfg = MfccConfig(**kw)
+    got, fr = out.cpu().numpy(), frames.cpu().numpy()
+    assert got.shape == (len(lengths), kw["n_mfcc"], cfg.num_frames(n_max))
+    assert fr.dtype == np.int64 and fr.tolist() == [cfg.num_frames(L) for L in lengths]
+    for b, L in enumerate(lengths):
+        want = _want(_key(kw), b, n_max, L)
+        T_b = want.shape[1]
+        assert T_b == fr[b]
+        assert not np.isnan(got[b]).any(), f"{what} L={L}: NaN in the result"
+        mfcc_close(got[b, :, :T_b], want, f"{what} L={L}")
+        tail = got[b, :, T_b:]
+        assert (tail == 0.0).all() and not np.signbit(tail).any(), f"{what} L={L}: columns behind T_b are not +0.0"
+
+
+def test_lengths_at_every_edge_staged_kernel(gpu):
+    """Clips shorter than a hop, than n_fft / 2 and than n_fft, both sides of the 64-frame tile boundary (10240 = 64 x 160)
+    and the full row, in one batch, NaN behind every clip."""
+    plan = _plan(C1)
+    assert plan.kernel_path == "radix16-w16s"
+    out, frames = plan.mfcc_ragged(_dev(_batch(C1, N_MAX_1, LENGTHS_1), gpu), list(LENGTHS_1))
+    _check_rows(C1, N_MAX_1, LENGTHS_1, out, frames, "edges")
+
+
+def test_garbage_behind_the_clip_never_matters(gpu):
+    """Zeros, NaN and 1e30 behind the clips: bit-equal outputs."""
+    import torch
+    plan = _plan(C1)
+    outs = [plan.mfcc_ragged(_dev(_batch(C1, N_MAX_1, LENGTHS_1, fill), gpu), list(LENGTHS_1))[0].clone()
+            for fill in (0.0, np.nan, 1e30)]
+    assert not torch.isnan(outs[0]).any()
+    assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
+
+
+def test_rows_do_not_depend_on_each_other(gpu):
+    """Each row alone in a [1, n_max] batch == its row in the batch, bit for bit."""
+    import torch
+    plan = _plan(C1)
+    audio = _dev(_batch(C1, N_MAX_1, LENGTHS_1), gpu)
+    out = plan.mfcc_ragged(audio, list(LENGTHS_1))[0].clone()
+    for b, L in enumerate(LENGTHS_1):
+        alone, fr = plan.mfcc_ragged(audio[b:b + 1].clone(), [L])
+        assert torch.equal(alone[0], out[b]), f"row {b} (L={L}) differs from the row computed alone"
+        assert fr.tolist() == [plan.cfg.num_frames(L)]
+
+
+def test_the_clamp_is_per_clip(gpu):
+    """Row 0: amplitude 1e-3, second half digital silence (its own top_db clamp is active), full-scale noise behind it; row 1:
+    a full-scale clip.  First, with the reference alone: clamping row 0 against the maximum of the PADDED row gives another
+    answer than mfcc_close allows -- so the device result can only match when its maximum is the clip's own.
+    (top_db 40: at amplitude 1e-3 the clip's loudest band lies at -50 dB, 50 dB over the amin floor of -100 dB, so the default
+    80 dB would leave row 0's own clamp idle.)"""
+    kw = dict(C1, top_db=40.0)
+    cfg = _ocfg(kw)
+    n_max, L0 = 8000, 4800
+    y0 = np.zeros(L0, np.float32)
+    y0[:L0 // 2] = 1e-3 * O.synth_clip(100, L0 // 2, C1["sr"], "noise")
+    y1 = O.synth_clip(101, n_max, C1["sr"], "noise")
+    row0 = np.concatenate([y0, O.synth_clip(102, n_max - L0, C1["sr"], "noise")])
+    want0, want1 = O.mfcc(y0, cfg), O.mfcc(y1, cfg)
+    lm0 = O.logmel_unclamped(y0, cfg)
+    assert lm0.min() < lm0.max() - 40.0, "row 0's own clamp is not active"
+    assert not np.array_equal(want0, O.mfcc_from_logmel(lm0, kw["n_mfcc"]))
+    padded_max = O.logmel_unclamped(row0, cfg).max()
+    wrong0 = O.mfcc_from_logmel(np.maximum(lm0, padded_max - np.float32(40.0)), kw["n_mfcc"])
+    with pytest.raises(AssertionError):
+        mfcc_close(wrong0, want0, "maximum over the padded row")
+    plan = _plan(kw)
+    out, frames = plan.mfcc_ragged(_dev(np.stack([row0, y1]), gpu), [L0, n_max])
+    got = out.cpu().numpy()
+    T0 = want0.shape[1]
+    assert frames.tolist() == [T0, want1.shape[1]]
+    mfcc_close(got[0, :, :T0], want0, "quiet clip with a loud padding")
+    assert (got[0, :, T0:] == 0.0).all()
+    mfcc_close(got[1], want1, "full-scale clip")
+
+
+def _around(n_fft, n_max):
+    return (1, n_fft // 2 - 1, n_fft // 2, n_fft // 2 + 1, n_fft - 1, n_fft, n_fft + 1, n_max - 1, n_max)
+
+
+PATHS = [
+    ("c3_wpf_2048", C3, {}),
+    ("reference_default_empty_filters", REF_DEFAULT, {}),
+    ("n_fft_400_any_length", dict(C1, n_fft=400), {}),
+    ("odd_hop_161", dict(C1, hop_length=161), {}),
+    ("preemph_0.97", dict(C1, preemph=0.97), {}),
+    ("top_db_off", dict(C1, top_db=-1.0), {}),
+    ("force_generic", C1, dict(generic=True)),
+    ("unaligned_row_stride", C1, dict(slice_of_wider=True)),
+    # beyond the issue's list: the two plans whose frame geometry the patch treats specially -- n_fft 256 transformed as 512
+    # points (the frame's span is the 512), and an odd n_fft (one sample less padded than consumed) with pre-emphasis
+    ("n_fft_256_in_512_points", dict(C1, n_fft=256, win_length=200, hop_length=80), {}),
+    ("odd_n_fft_441_preemph", dict(sr=44100, n_fft=441, win_length=441, hop_length=147, n_mels=30, n_mfcc=12, fmin=50.0,
+                                   fmax=20000.0, preemph=0.5), {}),
+]
+
+
+@pytest.mark.parametrize("name,kw,how", PATHS, ids=[p[0] for p in PATHS])
+def test_other_kernel_paths(name, kw, how, gpu):
+    import torch
+    from modulation_mfcc_amd import MfccConfig, MfccPlan
+    n_max = 3 * kw["n_fft"] + 7
+    lengths = _around(kw["n_fft"], n_max)
+    audio = _dev(_batch(kw, n_max, lengths), gpu)
+    if how.get("slice_of_wider"):
+        wide = torch.full((len(lengths), n_max + 6), float("nan"), dtype=torch.float32, device=gpu)
+        wide[:, 1:1 + n_max] = audio
+        audio = wide[:, 1:1 + n_max]
+        assert audio.stride(0) == n_max + 6 and audio.data_ptr() % 16 == 4
+    plan = MfccPlan(MfccConfig(**kw))       # (its own plan: force_generic is a switch of the plan)
+    try:
+        if how.get("generic"):
+            plan.force_generic(True)
+            assert plan.kernel_path == "generic"
+        if name == "n_fft_400_any_length":
+            assert plan.kernel_path == "any-length"
+        out, frames = plan.mfcc_ragged(audio, np.array(lengths))
+        _check_rows(kw, n_max, lengths, out, frames, name)
+    finally:
+        plan.close()
+
+
+@pytest.mark.parametrize("kw,n_max,lengths", [(C1, N_MAX_1, LENGTHS_1), (C3, 3 * 2048 + 7, _around(2048, 3 * 2048 + 7))],
+                         ids=["c1_edges", "c3_wpf_2048"])
+def test_modulation_spectrum(kw, n_max, lengths, gpu):
+    """rFFT of every clip's own frames on the batch's axis: against the reference per clip, and bit for bit modspec() of the
+    ragged MFCC."""
+    import torch
+    plan = _plan(kw)
+    out, mod, frames = plan.mfcc_modspec_ragged(_dev(_batch(kw, n_max, lengths), gpu), list(lengths))
+    _check_rows(kw, n_max, lengths, out, frames, "modspec")
+    n_mod = plan.cfg.mod_fft_len(plan.cfg.num_frames(n_max))
+    assert tuple(mod.shape) == (len(lengths), kw["n_mfcc"], n_mod // 2 + 1) and mod.dtype == torch.complex64
+    assert torch.equal(torch.view_as_real(mod), torch.view_as_real(plan.modspec(out)))
+    got = mod.cpu().numpy()
+    for b, L in enumerate(lengths):
+        want = O.modspec(_want(_key(kw), b, n_max, L), n_mod)
+        assert np.abs(got[b] - want).max() <= 1e-4 * np.abs(want).max(), f"L={L}"
+
+
+def test_all_lengths_equal_n_max(gpu):
+    """The ragged path on a batch without padding against mfcc() (two device paths: mfcc_close, not bit-equality)."""
+    plan = _plan(C1)
+    audio = _dev(np.stack([_clip(b, N_MAX_1, C1["sr"]) for b in range(4)]), gpu)
+    ref = plan.mfcc(audio).cpu().numpy()
+    out, frames = plan.mfcc_ragged(audio, [N_MAX_1] * 4)
+    assert frames.tolist() == [ref.shape[2]] * 4
+    got = out.cpu().numpy()
+    for b in range(4):
+        mfcc_close(got[b], ref[b], f"full-length row {b}")
+
+
+def test_device_lengths_and_argument_checks(gpu):
+    import torch
+    from modulation_mfcc_amd import mfcc_ragged_batch, mfcc_modspec_ragged_batch, MfccConfig
+    plan = _plan(C1)
+    audio = _dev(_batch(C1, N_MAX_1, LENGTHS_1), gpu)
+    host, fr_host = plan.mfcc_ragged(audio, list(LENGTHS_1))
+    host = host.clone()
+    dl = torch.tensor(LENGTHS_1, dtype=torch.int64, device=gpu)
+    devr, fr_dev = plan.mfcc_ragged(audio, dl)
+    assert torch.equal(host, devr) and torch.equal(fr_host, fr_dev) and fr_dev.device == audio.device
+    cpu_t, _ = plan.mfcc_ragged(audio, torch.tensor(LENGTHS_1, dtype=torch.int32))       # CPU tensor, any integer type
+    assert torch.equal(host, cpu_t)
+    # the batch functions reach the same entry
+    bt, bf = mfcc_ragged_batch(audio, np.array(LENGTHS_1), MfccConfig(**C1))
+    assert torch.equal(host, bt) and torch.equal(bf, fr_host)
+    bm = mfcc_modspec_ragged_batch(audio, LENGTHS_1, MfccConfig(**C1))
+    assert torch.equal(host, bm[0]) and len(bm) == 3
+    # a caller's output buffer
+    mine = torch.empty_like(host)
+    assert plan.mfcc_ragged(audio, dl, out=mine)[0] is mine and torch.equal(mine, host)
+    with pytest.raises(TypeError):
+        plan.mfcc_ragged(audio, dl.to(torch.int32))
+    with pytest.raises(ValueError):
+        plan.mfcc_ragged(audio, dl[:-1])
+    with pytest.raises(ValueError):
+        plan.mfcc_ragged(audio, dl.reshape(4, 4))
+    with pytest.raises(ValueError):
+        plan.mfcc_ragged(audio, [0] + list(LENGTHS_1[1:]))
+    with pytest.raises(ValueError):
+        plan.mfcc_ragged(audio, list(LENGTHS_1[:-1]) + [N_MAX_1 + 1])
+    with pytest.raises(TypeError):
+        plan.mfcc_ragged(audio, [float(v) for v in LENGTHS_1])
+    with pytest.raises(ValueError):
+        plan.mfcc_ragged(audio, dl, out=torch.empty((16, 13, 5), dtype=torch.float32, device=gpu))
+    with pytest.raises(TypeError):
+        plan.mfcc_ragged(audio.double(), dl)
+    # device lengths outside [1, n_max] are clamped by the kernels: rows as for 1 and n_max, no fault
+    wild = dl.clone()
+    wild[0], wild[15] = -5, 1 << 40
+    clamped, fr = plan.mfcc_ragged(audio, wild)
+    assert torch.equal(clamped, host) and torch.equal(fr, fr_host)
+
+
+def test_c_entry_codes_and_workspace(gpu):
+    """Null pointers, batch < 1 and a short workspace return the usual codes before anything is launched; the workspace
+    query is monotone in batch and in n_samples; n_mod > 8192 with a spectrum buffer is MM_ERR_UNSUPPORTED."""
+    import torch
+    from modulation_mfcc_amd import _lib
+    plan = _plan(C1)
+    lib, h = plan._lib, plan._h
+    B, n = 3, 4000
+    audio = torch.zeros((B, n), dtype=torch.float32, device=gpu)
+    lens = torch.full((B,), n, dtype=torch.int64, device=gpu)
+    out = torch.empty((B, 13, plan.cfg.num_frames(n)), dtype=torch.float32, device=gpu)
+    need = lib.mm_ragged_workspace_bytes(h, B, n)
+    assert need >= lib.mm_workspace_bytes(h, B, n) > 0
+    ws = torch.empty(need, dtype=torch.uint8, device=gpu)
+    st = plan._stream()
+    a, l, o, w = audio.data_ptr(), lens.data_ptr(), out.data_ptr(), ws.data_ptr()
+    f = lib.mm_mfcc_ragged_f32
+    assert f(h, a, B, n, n, l, o, None, w, need, st) == _lib.MM_OK
+    assert f(None, a, B, n, n, l, o, None, w, need, st) == _lib.MM_ERR_INVALID_ARG
+    assert f(h, None, B, n, n, l, o, None, w, need, st) == _lib.MM_ERR_INVALID_ARG
+    assert f(h, a, B, n, n, None, o, None, w, need, st) == _lib.MM_ERR_INVALID_ARG
+    assert f(h, a, B, n, n, l, None, None, w, need, st) == _lib.MM_ERR_INVALID_ARG
+    assert f(h, a, B, n, n, l, o, None, None, need, st) == _lib.MM_ERR_INVALID_ARG
+    assert f(h, a, 0, n, n, l, o, None, w, need, st) == _lib.MM_ERR_INVALID_ARG
+    assert f(h, a, B, 0, n, l, o, None, w, need, st) == _lib.MM_ERR_INVALID_ARG
+    assert f(h, a, B, n, n - 1, l, o, None, w, need, st) == _lib.MM_ERR_INVALID_ARG
+    assert f(h, a, B, n, n, l, o, None, w, need - 1, st) == _lib.MM_ERR_WORKSPACE
+    assert lib.mm_ragged_workspace_bytes(h, 0, n) == 0 and lib.mm_ragged_workspace_bytes(h, B, 0) == 0
+    sizes = [[lib.mm_ragged_workspace_bytes(h, b, m) for m in (1, 100, 4000, 160000)] for b in (1, 2, 64, 1024)]
+    for row in sizes:
+        assert all(x <= y for x, y in zip(row, row[1:]))
+    for lo, hi in zip(sizes, sizes[1:]):
+        assert all(x < y for x, y in zip(lo, hi))
+    torch.cuda.synchronize()
+
+
+def test_long_trajectories_take_the_global_transform(gpu):
+    """More than 8192 frames per clip: the C entry refuses the spectrum buffer, the Python call transforms the ragged MFCC with
+    modspec()'s long transform instead."""
+    import torch
+    from modulation_mfcc_amd import _lib
+    kw = dict(C1, hop_length=1, n_mels=8, n_mfcc=4)
+    plan = _plan(kw)
+    n_max, lengths = 8300, (700, 8300)
+    audio = _dev(_batch(kw, n_max, lengths), gpu)
+    T = plan.cfg.num_frames(n_max)
+    assert plan.cfg.mod_fft_len(T) == 16384
+    lens = torch.tensor(lengths, dtype=torch.int64, device=gpu)
+    out = torch.empty((2, 4, T), dtype=torch.float32, device=gpu)
+    mod = torch.empty((2, 4, 8193), dtype=torch.complex64, device=gpu)
+    ws = plan.ragged_workspace(2, n_max)
+    assert plan._lib.mm_mfcc_ragged_f32(plan._h, audio.data_ptr(), 2, n_max, n_max, lens.data_ptr(), out.data_ptr(),
+                                        mod.data_ptr(), ws.data_ptr(), ws.numel(), plan._stream()) == _lib.MM_ERR_UNSUPPORTED
+    m, ms, frames = plan.mfcc_modspec_ragged(audio, lens)
+    _check_rows(kw, n_max, lengths, m, frames, "hop 1")
+    want = plan.modspec(m)
+    assert torch.equal(torch.view_as_real(ms), torch.view_as_real(want))
+
+
+def test_pack_clips(gpu):
+    import torch
+    from modulation_mfcc_amd import pack_clips, mfcc_ragged_batch, MfccConfig
+    lengths = (513, 3, 4097, 160)
+    clips = [_dev(_clip(b, N_MAX_1, C1["sr"])[:L].copy(), gpu) for b, L in enumerate(lengths)]
+    audio, lens = pack_clips(clips)
+    assert tuple(audio.shape) == (4, 4097) and audio.device == clips[0].device and lens.tolist() == list(lengths)
+    for b, L in enumerate(lengths):
+        assert torch.equal(audio[b, :L], clips[b])
+    out, frames = mfcc_ragged_batch(audio, lens, MfccConfig(**C1))
+    got = out.cpu().numpy()
+    for b, L in enumerate(lengths):
+        want = _want(_key(C1), b, N_MAX_1, L)
+        mfcc_close(got[b, :, :want.shape[1]], want, f"packed clip {b}")
+        assert (got[b, :, want.shape[1]:] == 0.0).all() and frames[b].item() == want.shape[1]
