@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import mfcc_oracle as O
+import modspec_oracle as MS
 from conftest import FORNBERG, GOLDEN_NAMES, XCHECK_NAMES, fornberg_apply, load_golden, load_xcheck, mfcc_close
 
 pytestmark = pytest.mark.gpu
@@ -507,6 +508,7 @@ def test_modspec_matches_oracle(gpu):
     want = exp["modspec"]
     assert ms.shape == want.shape == (13, 65)
     assert np.abs(ms - want).max() <= 1e-4 * np.abs(want).max()
+    MS.check(ms, m[0].cpu().numpy(), 128, "golden clip")      # bin by bin, against the transform of the MFCC it was given
     # 10 s clip: T = 1001 -> n_mod 1024
     y10 = O.synth_clip(11, 160000, 16000, "am")
     m10 = plan.mfcc(_dev(y10, gpu)[None, :])
@@ -514,6 +516,7 @@ def test_modspec_matches_oracle(gpu):
     want10 = O.modspec(O.mfcc(y10, O.OracleConfig(**kw)))
     assert ms10.shape == (13, 513)
     assert np.abs(ms10 - want10).max() <= 1e-4 * np.abs(want10).max()
+    MS.check(ms10, m10[0].cpu().numpy(), 1024, "10 s clip")
 
 
 def test_full_size_properties(gpu):
@@ -593,6 +596,10 @@ def test_fused_tail_matches_separate_launches(extra, n, batches, gpu):
         ocfg = O.OracleConfig(**dict(kw, top_db=None if kw.get("top_db", 80.0) < 0 else kw.get("top_db", 80.0)))
         for i in (0, 1, B - 1):
             mfcc_close(m1[i].cpu().numpy(), O.mfcc(audio[i].cpu().numpy(), ocfg), f"B={B} clip {i}")
+            # bin by bin, against the transform of the MFCC the same call returned (== m0, asserted above)
+            n_mod = plan.cfg.mod_fft_len(m1.shape[2])
+            MS.check(s1[i].cpu().numpy(), m1[i].cpu().numpy(), n_mod, f"B={B} clip {i}: one call")
+            MS.check(s0[i].cpu().numpy(), m1[i].cpu().numpy(), n_mod, f"B={B} clip {i}: separate launches")
     if kw.get("top_db", 80.0) >= 0:
         # the clamp did bite in the quiet-tail clips (otherwise this test would not cover the fix-up)
         lm, mx = plan.logmel(audio[:1])
@@ -764,6 +771,7 @@ def test_headline_config_through_the_headline_entry_point(gpu):
         mfcc_close(m1[i].cpu().numpy(), want, f"headline clip {i}")
         wm = O.modspec(want)
         assert np.abs(s1[i].cpu().numpy() - wm).max() <= 1e-4 * np.abs(wm).max(), f"modspec clip {i}"
+        MS.check(s1[i].cpu().numpy(), m1[i].cpu().numpy(), 1024, f"headline clip {i}")     # bin by bin, of the returned MFCC
     e_time = (m1.double() ** 2).sum(-1)
     w = torch.full((513,), 2.0, device=gpu, dtype=torch.float64)
     w[0] = w[-1] = 1.0
@@ -811,6 +819,7 @@ def test_clip_mode_with_a_2048_point_trajectory(n, B, gpu):
             mfcc_close(m1[i].cpu().numpy(), want, f"clip {i}")
             wm = O.modspec(want)
             assert np.abs(s1[i].cpu().numpy() - wm).max() <= 1e-4 * max(np.abs(wm).max(), 1e-30), f"modspec clip {i}"
+            MS.check(s1[i].cpu().numpy(), m1[i].cpu().numpy(), 2048, f"clip {i}")      # bin by bin, of the returned MFCC
     e_time = (m1.double() ** 2).sum(-1)
     w = torch.full((1025,), 2.0, device=gpu, dtype=torch.float64)
     w[0] = w[-1] = 1.0
@@ -865,6 +874,7 @@ def test_half_band_wave_per_frame_kernels(kw, what, gpu):
     np.testing.assert_array_equal(m2.cpu().numpy(), got)
     wm = O.modspec(got[0])
     assert np.abs(s2[0].cpu().numpy() - wm).max() <= 1e-4 * max(np.abs(wm).max(), 1e-30)
+    MS.check(s2.cpu().numpy(), got, plan.cfg.mod_fft_len(got.shape[2]), what)      # bin by bin, every clip and row
 
 
 def test_modulation_spectrum_of_long_trajectories(gpu):

@@ -2,7 +2,8 @@
 mfcc_modspec_ragged, mfcc_ragged_batch, pack_clips).
 
 The expected value is always the numpy reference on the clip ALONE: O.mfcc(y[:L_b], cfg) under conftest.mfcc_close (the
-project's tolerance), O.modspec of it at the batch's n_mod within 1e-4 of its maximum (as test_modspec_matches_oracle).
+project's tolerance), O.modspec of it at the batch's n_mod within 1e-4 of its maximum (as test_modspec_matches_oracle) and,
+bin by bin, modspec_oracle.check against the float64 transform of the frames the call returned.
 Inputs are O.synth_clip; what lies behind a clip's end is filled with NaN unless a test says otherwise."""
 import ctypes as C
 import functools
@@ -11,6 +12,7 @@ import numpy as np
 import pytest
 
 import mfcc_oracle as O
+import modspec_oracle as MS
 from conftest import mfcc_close
 
 pytestmark = pytest.mark.gpu
@@ -201,10 +203,12 @@ def test_modulation_spectrum(kw, n_max, lengths, gpu):
     n_mod = plan.cfg.mod_fft_len(plan.cfg.num_frames(n_max))
     assert tuple(mod.shape) == (len(lengths), kw["n_mfcc"], n_mod // 2 + 1) and mod.dtype == torch.complex64
     assert torch.equal(torch.view_as_real(mod), torch.view_as_real(plan.modspec(out)))
-    got = mod.cpu().numpy()
+    got, mh, fr = mod.cpu().numpy(), out.cpu().numpy(), frames.cpu().numpy()
     for b, L in enumerate(lengths):
         want = O.modspec(_want(_key(kw), b, n_max, L), n_mod)
         assert np.abs(got[b] - want).max() <= 1e-4 * np.abs(want).max(), f"L={L}"
+        # bin by bin, against the transform of the clip's own frames as the call returned them
+        MS.check(got[b], np.ascontiguousarray(mh[b, :, :fr[b]]), n_mod, f"L={L}")
 
 
 def test_all_lengths_equal_n_max(gpu):
