@@ -18,6 +18,8 @@
  *                             it were called alone (build-defined; no reference site)
  *   mm_mfcc_change_f64     <- script/mfcc.py:392-427 (drop c0, Butterworth sosfiltfilt,
  *                             gradient or Savitzky-Golay derivative, norm, output filter) -- row N1
+ *   mm_mfcc_change_ragged_f64 <- the same tail for the result of mm_mfcc_ragged_f32: one frame count per clip, each
+ *                             clip's curve as if it were called alone (build-defined; no reference site)
  *   mm_sosfiltfilt_f64     <- applyFilter(filt='iir') (script/mfcc.py:29-135): scipy sosfiltfilt on a batch
  *   mm_stencil_f64         <- get_velocity (script/calc.py:593-650): np.gradient / savgol_filter /
  *                             findiff derivative of a curve -- row N2
@@ -253,6 +255,30 @@ int mm_mfcc_change_f64(mm_plan* plan, const float* d_mfcc, int64_t batch, int64_
 size_t mm_change_workspace_bytes(const mm_plan* plan, int64_t batch, int64_t n_frames);
 size_t mm_change_workspace_bytes_for(const mm_plan* plan, int64_t batch, int64_t n_frames, int32_t remove_first,
                                      const double* sos1, int32_t n_sec1, const double* sos2, int32_t n_sec2);
+
+/* The same tail for a ragged batch (no reference site: the reference takes one clip per call): d_mfcc [batch][n_mfcc]
+ * [n_frames_max] f32 and d_frames (DEVICE, int64 [batch]) as mm_mfcc_ragged_f32 writes / its caller derives them ->
+ * d_change [batch][n_frames_max] f64.  With T_b = d_frames[b]:
+ *   columns [0, T_b) = mm_mfcc_change_f64 on d_mfcc[b][:][0 .. T_b) ALONE: both odd extensions formed about frame T_b - 1
+ *     (the MFCC rows' in float32), the one-sided derivative at T_b - 1, the norm, the second filter;
+ *   columns [T_b, n_frames_max) = +0.0.
+ * MFCC columns at and behind T_b never enter a result, whatever they hold (NaN, Inf): the kernel loads T_b columns of a row.
+ * A row's result depends on its own data, T_b and n_frames_max only (bit for bit reproducible for one n_frames_max; against
+ * the single-length call it differs by rounding, ~1e-13 relative: the filters' chunk length follows n_frames_max).
+ * d_frames[b] outside [1, n_frames_max] is clamped into it on the device.  A clip scipy refuses, T_b <= the larger padding
+ * length, comes out NaN in [0, T_b): never an access out of bounds.  One launch of the clip-resident kernel (plus the
+ * table uploads), a workgroup per clip, shaped on the host for n_frames_max; no allocation, no synchronisation,
+ * asynchronous on `stream`.  mm_plan_set_fuse_tail() does not affect it.
+ * MM_ERR_UNSUPPORTED, before any launch, where the clip-resident form does not reach: a filter of more than 4 sections, or
+ * n_frames_max so long that one row and the curve do not fit LDS (about 10 000 frames) -- run mm_mfcc_change_f64 per
+ * distinct length then.  MM_ERR_INVALID_ARG as mm_mfcc_change_f64 (checked against n_frames_max) and for d_frames == NULL;
+ * MM_ERR_WORKSPACE below mm_change_ragged_workspace_bytes_for() (the filter tables, a few KB; 0 for invalid arguments). */
+size_t mm_change_ragged_workspace_bytes_for(const mm_plan* plan, int64_t batch, int64_t n_frames_max, int32_t remove_first,
+                                            const double* sos1, int32_t n_sec1, const double* sos2, int32_t n_sec2);
+int mm_mfcc_change_ragged_f64(mm_plan* plan, const float* d_mfcc, int64_t batch, int64_t n_frames_max,
+                              const int64_t* d_frames, int32_t remove_first, int32_t diff_method,
+                              const double* sos1, int32_t n_sec1, const double* sos2, int32_t n_sec2,
+                              double* d_change, void* d_workspace, size_t ws_bytes, void* stream);
 
 /* Zero-phase IIR filter of float64 curves: scipy.signal.sosfiltfilt(sos, x) with its defaults (odd
  * extension by 3 * ntaps samples, sosfilt_zi initial state), i.e. the 'iir' branch of applyFilter

@@ -6,8 +6,8 @@ include/modmfcc.h).  torch is used for device buffers, streams and torch.distrib
 """
 from .plan import MfccConfig, MfccPlan, get_plan, butter_sos  # noqa: F401
 from .batch import mfcc_batch, modspec_batch, mfcc_modspec_batch, rfft_batch, rms_batch  # noqa: F401
-from .batch import mfcc_ragged_batch, mfcc_modspec_ragged_batch, pack_clips  # noqa: F401
-from .mfcc import get_MFCCS_change, load_channel, applyFilter, get_amplitude  # noqa: F401
+from .batch import mfcc_ragged_batch, mfcc_modspec_ragged_batch, mfcc_change_ragged_batch, pack_clips  # noqa: F401
+from .mfcc import get_MFCCS_change, get_MFCCS_change_batch, load_channel, applyFilter, get_amplitude  # noqa: F401
 from .calc import (get_velocity, calculate_amplitude_envelope, velocity_batch, amplitude_envelope_batch,  # noqa: F401
                    hilbert_envelope_batch, find_peaks_batch, find_peaks_ex_batch,
                    peaks_to_list, MinMaxFinder)

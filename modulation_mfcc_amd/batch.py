@@ -36,6 +36,27 @@ def mfcc_modspec_ragged_batch(audio, lengths, cfg: MfccConfig, mfcc_out=None, mo
     return get_plan(cfg).mfcc_modspec_ragged(audio, lengths, out=mfcc_out, out_mod=mod_out)
 
 
+def mfcc_change_ragged_batch(audio, lengths, cfg: MfccConfig, *, tStep=None, **tail):
+    """Padded batch [B, n_max] + one length per clip -> (change [B, T_max] float64, frames [B] int64 on the device): the
+    amount-of-change curve of every clip as get_MFCCS_change computes it for that clip alone, in the columns
+    [0, frames[b]), zeros behind them.  mfcc_ragged_batch followed by the ragged change tail
+    (tail.mfcc_change_ragged_device, whose keywords -- removeFirst, filtCutoff, filtOrd, diffMethod, outFilter, ... -- pass
+    through; tStep defaults to the configuration's hop_length / sr); nothing leaves the device.  Host `lengths` are
+    validated on the host: a clip with too few frames for the filters raises scipy's ValueError (device lengths: NaN)."""
+    import numpy as np
+    import torch
+    from . import tail as _tail
+    plan = get_plan(cfg)
+    if tStep is None:
+        tStep = cfg.hop_length / cfg.sr
+    mfcc, frames = plan.mfcc_ragged(audio, lengths)
+    fr = frames
+    if not (isinstance(lengths, torch.Tensor) and lengths.is_cuda):      # host lengths: host frame counts, validated by the tail
+        lens = lengths.numpy() if isinstance(lengths, torch.Tensor) else np.asarray(lengths)
+        fr = 1 + (lens.astype(np.int64) - (cfg.n_fft - 2 * (cfg.n_fft // 2))) // cfg.hop_length
+    return _tail.mfcc_change_ragged_device(plan, mfcc, fr, tStep=tStep, **tail), frames
+
+
 def pack_clips(clips):
     """A list of 1-D float32 tensors (one device) -> (audio [B, n_max] on that device, lengths int64 [B] on the host) for
     the ragged calls.  The padding behind each clip is left as allocated: the ragged calls never read it into a result."""

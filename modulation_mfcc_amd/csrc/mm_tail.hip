@@ -163,6 +163,61 @@ int mm_mfcc_change_f64(mm_plan* p, const float* d_mfcc, int64_t batch, int64_t n
   return MM_OK;
 }
 
+// ---- ragged batches: one frame count per clip (include/modmfcc.h) ----
+// The clip-resident kernel alone, shaped for the longest clip: chunk tables, K1 / K2, row groups and LDS follow from
+// n_frames_max, a workgroup reads its own length.  No other form: more than MM_CLIP_NS sections or a clip whose single row
+// does not fit LDS is MM_ERR_UNSUPPORTED, whatever mm_plan_set_fuse_tail() says.
+static bool change_ragged_shape(int n_rows, int64_t n_frames_max, const SosFilt& f1, const SosFilt& f2, ClipShape* cs) {
+  const int64_t p1 = f1.padlen, p2 = f2.n_sec > 0 ? f2.padlen : 0;
+  *cs = clip_shape(n_rows, n_frames_max + 2 * p1, n_frames_max + 2 * p2);
+  return f1.n_sec <= MM_CLIP_NS && f2.n_sec <= MM_CLIP_NS && cs->G >= 1;
+}
+
+size_t mm_change_ragged_workspace_bytes_for(const mm_plan* p, int64_t batch, int64_t n_frames_max, int32_t remove_first,
+                                            const double* sos1, int32_t n_sec1, const double* sos2, int32_t n_sec2) {
+  if (!p || batch < 1 || n_frames_max < 1 || n_frames_max > 0x7FFFFFFF || remove_first < 0 || remove_first >= p->cfg.n_mfcc)
+    return 0;
+  SosFilt f1, f2;
+  if (change_pads(n_sec1, sos1, n_sec2, sos2, &f1, &f2)) return 0;
+  ClipShape cs;
+  // (a call the ragged entry answers with MM_ERR_UNSUPPORTED needs nothing: one double, so that a caller has a buffer to pass)
+  const bool ok = change_ragged_shape(p->cfg.n_mfcc - (remove_first ? 1 : 0), n_frames_max, f1, f2, &cs);
+  return std::max<size_t>(ok ? (size_t)cs.tab_n : 0, 1) * sizeof(double);
+}
+
+int mm_mfcc_change_ragged_f64(mm_plan* p, const float* d_mfcc, int64_t batch, int64_t n_frames_max, const int64_t* d_frames,
+                              int32_t remove_first, int32_t diff_method, const double* sos1, int32_t n_sec1,
+                              const double* sos2, int32_t n_sec2, double* d_change, void* d_ws, size_t ws_bytes, void* stream) {
+  if (!p || !d_mfcc || !d_frames || !d_change || !d_ws || batch < 1 || n_frames_max < 1) return MM_ERR_INVALID_ARG;
+  if (diff_method < 0 || diff_method > 1 || (diff_method == 1 && n_frames_max < 3)) return MM_ERR_INVALID_ARG;
+  if (remove_first < 0 || remove_first >= p->cfg.n_mfcc) return MM_ERR_INVALID_ARG;
+  if (batch > 0x7FFFFFFF || n_frames_max > 0x7FFFFFFF) return MM_ERR_INVALID_ARG;
+  SosFilt f1, f2;
+  int rc = change_pads(n_sec1, sos1, n_sec2, sos2, &f1, &f2);
+  if (rc) return rc;
+  // what the host can know: not even the longest clip is one scipy takes (a shorter one comes out NaN, on the device)
+  if (n_frames_max <= f1.padlen || n_frames_max <= f2.padlen) return MM_ERR_INVALID_ARG;
+  ChangeParams q;
+  q.mfcc = d_mfcc; q.n_frames = n_frames_max; q.batch = batch; q.n_mfcc = p->cfg.n_mfcc;
+  q.first_row = remove_first ? 1 : 0; q.n_rows = q.n_mfcc - q.first_row;
+  q.p1 = f1.padlen; q.p2 = f2.n_sec > 0 ? f2.padlen : 0; q.sg = diff_method;
+  q.R = batch * q.n_rows; q.Rp = round64(q.R); q.Bp = round64(batch);
+  q.ws1 = (double*)d_ws; q.ws2 = nullptr; q.out = d_change;
+  ClipShape cs;
+  if (!change_ragged_shape(q.n_rows, n_frames_max, f1, f2, &cs)) return MM_ERR_UNSUPPORTED;
+  if (ws_bytes < (size_t)cs.tab_n * sizeof(double)) return MM_ERR_WORKSPACE;
+  const int64_t n1 = n_frames_max + 2 * q.p1, n2 = n_frames_max + 2 * q.p2;
+  hipStream_t st = (hipStream_t)stream;
+  StageTimer tm(p, MM_STAGE_CHANGE, st);
+  const int ns = std::max(f1.n_sec, f2.n_sec);
+  rc = ns <= 2 ? launch_chg_clip<2, true>(q, f1, f2, cs, n1, n2, q.ws1, st, d_frames)
+     : ns == 3 ? launch_chg_clip<3, true>(q, f1, f2, cs, n1, n2, q.ws1, st, d_frames)
+               : launch_chg_clip<4, true>(q, f1, f2, cs, n1, n2, q.ws1, st, d_frames);
+  if (rc) return rc;
+  HIP_TRY(hipGetLastError());
+  return MM_OK;
+}
+
 size_t mm_sosfiltfilt_workspace_bytes(int64_t rows, int64_t n) {
   if (rows < 1 || n < 1) return 0;
   // the larger of the two device forms: time-major [n + 2 pad][rows padded to 64] | segmented rows (mm_sos_rows.hip.inc)

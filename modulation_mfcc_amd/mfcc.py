@@ -18,7 +18,7 @@ from . import filters as _filters
 from . import tail as _tail
 from .plan import MfccConfig, get_plan
 
-__all__ = ["applyFilter", "get_amplitude", "load_channel", "get_MFCCS_change", "mfcc_array"]
+__all__ = ["applyFilter", "get_amplitude", "load_channel", "get_MFCCS_change", "get_MFCCS_change_batch", "mfcc_array"]
 
 applyFilter = _filters.applyFilter
 
@@ -108,3 +108,50 @@ def get_MFCCS_change(audioIn, sigSr, /, *, channelN: int = 0, tStep: float = 0.0
                                outFiltType=outFiltType, outFiltCutOff=outFiltCutOff,
                                outFiltLen=outFiltLen, outFiltPolyOrd=outFiltPolyOrd)
     return change, anchors
+
+
+def get_MFCCS_change_batch(clips, sigSr, /, *, channelN: int = 0, tStep: float = 0.001,
+                           winLen: float = 0.025, n_mfcc: int = 13, n_fft: int = 512, minFreq: int = 100,
+                           maxFreq: int = 10000, removeFirst: int = 1, filtCutoff: int = 12,
+                           filtOrd: int = 6, diffMethod: str = "grad", outFilter: str = "iir",
+                           outFiltType: str = "low", outFiltCutOff=[None], outFiltLen: int = 6,
+                           outFiltPolyOrd: int = 3):
+    """``get_MFCCS_change`` for a list of clips of any lengths -> a list of ``(totChange, T)`` numpy pairs, one per clip,
+    each what ``get_MFCCS_change`` returns for that clip alone (its own last frame, its own time anchors).
+
+    ``clips``: paths, arrays or device tensors ([n] or [channels, n]; ``channelN`` picks as in the single call).  The
+    clips are packed into one padded batch (``pack_clips``) and run through the ragged MFCC and the ragged change tail in
+    a few launches (``mfcc_change_ragged_batch``); one copy brings the curves back.  A clip with too few frames for the
+    filters raises scipy's ValueError, as the single call does, with the clip's index in the message.
+    """
+    kw = dict(channelN=channelN, tStep=tStep, winLen=winLen, n_mfcc=n_mfcc, n_fft=n_fft, minFreq=minFreq, maxFreq=maxFreq,
+              removeFirst=removeFirst, filtCutoff=filtCutoff, filtOrd=filtOrd, diffMethod=diffMethod, outFilter=outFilter,
+              outFiltType=outFiltType, outFiltCutOff=outFiltCutOff, outFiltLen=outFiltLen, outFiltPolyOrd=outFiltPolyOrd)
+    clips = list(clips)
+    if not _tail.device_path_applies(diffMethod, outFilter) or not clips:
+        return [get_MFCCS_change(c, sigSr, **kw) for c in clips]       # (an output filter applyFilter refuses: its own error)
+    import torch
+    from .batch import mfcc_change_ragged_batch, pack_clips
+    cfg = MfccConfig.from_reference_call(sigSr, tStep=tStep, winLen=winLen, n_mfcc=n_mfcc,
+                                         n_fft=n_fft, minFreq=minFreq, maxFreq=maxFreq)
+    plan = get_plan(cfg)
+    rows = []
+    for c in clips:
+        signal = _load_audio_device(c, sigSr) if isinstance(c, str) else c
+        if signal.ndim > 1:
+            signal = signal[channelN, :]
+        if isinstance(signal, torch.Tensor):
+            y = signal.to(device=plan.device, dtype=torch.float32)
+        else:
+            y = torch.from_numpy(np.ascontiguousarray(np.asarray(signal), dtype=np.float32)).to(plan.device)
+        if y.dim() != 1:
+            raise ValueError("expected a 1-D signal")
+        rows.append(y)
+    audio, lengths = pack_clips(rows)
+    change, _ = mfcc_change_ragged_batch(audio, lengths, cfg, tStep=tStep, removeFirst=removeFirst, filtCutoff=filtCutoff,
+                                         filtOrd=filtOrd, diffMethod=diffMethod, outFilter=outFilter,
+                                         outFiltType=outFiltType, outFiltCutOff=outFiltCutOff, outFiltLen=outFiltLen,
+                                         outFiltPolyOrd=outFiltPolyOrd)
+    change = change.cpu().numpy()
+    frames = [cfg.num_frames(int(n)) for n in lengths]
+    return [(change[b, :T].copy(), _tail.time_anchors(T, tStep, winLen)) for b, T in enumerate(frames)]

@@ -134,29 +134,63 @@ def _torch():
     return torch
 
 
+def _check_counts(x, batch, hi, device, what):
+    """One integer count per clip, in [1, hi]: host values validated -> int64 numpy array; an int64 tensor on `device`
+    as it is (shape and type checked only: no read-back)."""
+    torch = _torch()
+    if isinstance(x, torch.Tensor) and x.is_cuda:
+        if x.dtype != torch.int64:
+            raise TypeError(f"{what} on the device must be int64, got {x.dtype}")
+        if tuple(x.shape) != (int(batch),):
+            raise ValueError(f"{what} must have shape ({int(batch)},), got {tuple(x.shape)}")
+        if device is not None and x.device != torch.device(device):
+            raise ValueError(f"{what} is on {x.device}, the plan on {device}")
+        return x.contiguous()
+    arr = x.numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    if arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer):
+        raise TypeError(f"{what} must be integers, got {arr.dtype}")
+    if arr.shape != (int(batch),):
+        raise ValueError(f"{what} must have shape ({int(batch)},), got {arr.shape}")
+    if int(arr.min()) < 1 or int(arr.max()) > int(hi):
+        raise ValueError(f"{what} must lie in [1, {int(hi)}], got {int(arr.min())} .. {int(arr.max())}")
+    return np.ascontiguousarray(arr, dtype=np.int64)
+
+
 def check_lengths(lengths, batch, n_samples, device=None):
     """The `lengths` argument of the ragged calls: one valid sample count per clip of a padded [batch, n_samples] batch.
 
     A host sequence, numpy array or CPU tensor of integers is validated here -- shape [batch], every value in
     [1, n_samples], ValueError otherwise -- and returned as an int64 numpy array.  An int64 tensor on `device` (a
     CUDA(HIP) device) is returned as it is, with no read-back: the kernels clamp its values into [1, n_samples]."""
-    torch = _torch()
-    if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
-        if lengths.dtype != torch.int64:
-            raise TypeError(f"lengths on the device must be int64, got {lengths.dtype}")
-        if tuple(lengths.shape) != (int(batch),):
-            raise ValueError(f"lengths must have shape ({int(batch)},), got {tuple(lengths.shape)}")
-        if device is not None and lengths.device != torch.device(device):
-            raise ValueError(f"lengths is on {lengths.device}, the plan on {device}")
-        return lengths.contiguous()
-    arr = lengths.numpy() if isinstance(lengths, torch.Tensor) else np.asarray(lengths)
-    if arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer):
-        raise TypeError(f"lengths must be integers, got {arr.dtype}")
-    if arr.shape != (int(batch),):
-        raise ValueError(f"lengths must have shape ({int(batch)},), got {arr.shape}")
-    if int(arr.min()) < 1 or int(arr.max()) > int(n_samples):
-        raise ValueError(f"lengths must lie in [1, {int(n_samples)}], got {int(arr.min())} .. {int(arr.max())}")
-    return np.ascontiguousarray(arr, dtype=np.int64)
+    return _check_counts(lengths, batch, n_samples, device, "lengths")
+
+
+_PADLEN_TEXT = "The length of the input vector x must be greater than padlen, which is {}."    # scipy.signal.sosfiltfilt's
+
+
+def sos_padlen(sos):
+    """scipy.signal.sosfiltfilt's default padlen for [n_sec, 6] sections: 3 * ntaps."""
+    return 3 * (2 * sos.shape[0] + 1 - min(int((sos[:, 2] == 0).sum()), int((sos[:, 5] == 0).sum())))
+
+
+def check_frames(frames, batch, n_frames_max, padlen=0, device=None):
+    """The `frames` argument of the ragged change tail: one valid frame count per clip of a [batch, n_mfcc, n_frames_max]
+    batch, checked as check_lengths checks sample counts.  Host values must also exceed `padlen`: scipy's own ValueError
+    text for a clip that sosfiltfilt refuses, with the first such clip named.  An int64 tensor on `device` is returned as
+    it is, with no read-back: the kernel clamps its values and writes NaN for a clip that is too short."""
+    arr = _check_counts(frames, batch, n_frames_max, device, "frames")
+    if isinstance(arr, np.ndarray):
+        short = np.flatnonzero(arr <= int(padlen))
+        if short.size:
+            raise ValueError(_PADLEN_TEXT.format(int(padlen)) + f" (clip {int(short[0])} has {int(arr[short[0]])} frames)")
+    return arr
+
+
+def by_length(frames):
+    """Host frame counts [B] -> [(T, int64 index array of the clips with T frames)], ascending T: the grouping behind
+    every per-length route of the ragged change tail."""
+    frames = np.asarray(frames)
+    return [(int(T), np.flatnonzero(frames == T).astype(np.int64)) for T in np.unique(frames)]
 
 
 class MfccPlan:
@@ -489,6 +523,64 @@ class MfccPlan:
                                                 s1.ctypes.data, s1.shape[0], s2.ctypes.data, s2.shape[0] if out_filter else 0,
                                                 out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
                    "mm_mfcc_change_f64")
+        return out
+
+    def mfcc_change_ragged(self, mfcc, frames, sos1, sos2=None, remove_first=True, diff_method="grad", out_filter=True):
+        """mfcc_change() for a ragged batch: [B, n_mfcc, T_max] float32 (what mfcc_ragged() returns) + `frames` [B] ->
+        [B, T_max] float64.  out[b, :frames[b]] is mfcc_change() of mfcc[b, :, :frames[b]] alone (both odd extensions and
+        the one-sided derivative at the clip's own last frame; equal to the single call up to rounding, ~1e-13),
+        out[b, frames[b]:] is 0; the MFCC columns at and behind frames[b] never enter a result.  One launch
+        (mm_mfcc_change_ragged_f64), no synchronisation.
+
+        frames: a host sequence / numpy array / CPU tensor (validated here: ValueError outside [1, T_max], and scipy's
+        ValueError naming the first clip that is not longer than a filter's padding) or an int64 device tensor (passed
+        through with no read-back: values are clamped into [1, T_max] and a clip that is too short comes out NaN).
+
+        Filters of more than 4 sections and batches of more than about 10 000 frames (MM_ERR_UNSUPPORTED from the C
+        entry) fall back to one mfcc_change() per distinct frame count, scattered into the zeroed output: correct,
+        slower, and the one place this method synchronises (it reads `frames` back when they live on the device)."""
+        torch = _torch()
+        if not (isinstance(mfcc, torch.Tensor) and mfcc.is_cuda and mfcc.dtype == torch.float32
+                and mfcc.dim() == 3 and mfcc.shape[1] == self.cfg.n_mfcc):
+            raise TypeError("mfcc must be a float32 CUDA(HIP) tensor [B, n_mfcc, T]")
+        if mfcc.device != self.device:
+            raise ValueError(f"mfcc is on {mfcc.device}, the plan on {self.device}")
+        mfcc = mfcc.contiguous()
+        B, _, Tm = mfcc.shape
+        from .filters import sos_sections
+        s1 = sos_sections(sos1)
+        s2 = s1 if sos2 is None else sos_sections(sos2)
+        padlen = max(sos_padlen(s) for s in ((s1, s2) if out_filter else (s1,)))
+        if Tm <= padlen:
+            raise ValueError(_PADLEN_TEXT.format(padlen))
+        sg = 0 if diff_method == "grad" else 1
+        fr = check_frames(frames, B, Tm, padlen, self.device)
+        on_host = not isinstance(fr, torch.Tensor)
+        fr_dev = torch.from_numpy(fr).to(self.device, non_blocking=True) if on_host else fr
+        rf, n2 = 1 if remove_first else 0, s2.shape[0] if out_filter else 0
+        out = torch.empty((B, Tm), dtype=torch.float64, device=self.device)
+        need = int(self._lib.mm_change_ragged_workspace_bytes_for(self._h, B, Tm, rf, s1.ctypes.data, s1.shape[0],
+                                                                  s2.ctypes.data, n2))
+        if need == 0:
+            raise ValueError("mm_change_ragged_workspace_bytes_for: invalid arguments")
+        ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self._lib.mm_mfcc_change_ragged_f64(self._h, mfcc.data_ptr(), B, Tm, fr_dev.data_ptr(), rf, sg,
+                                                     s1.ctypes.data, s1.shape[0], s2.ctypes.data, n2, out.data_ptr(),
+                                                     ws.data_ptr(), ws.numel(), self._stream())
+        if rc != _lib.MM_ERR_UNSUPPORTED:
+            _lib.check(rc, "mm_mfcc_change_ragged_f64")
+            return out
+        # no ragged kernel for this call: one single-length call per distinct frame count (reads device lengths back)
+        fr_host = fr if on_host else fr_dev.clamp(1, Tm).cpu().numpy()
+        out.zero_()
+        for T, idx in by_length(fr_host):
+            ii = torch.from_numpy(idx).to(self.device)
+            if T <= padlen:                 # device lengths only: what the kernel writes for a clip scipy refuses
+                out[ii, :T] = float("nan")
+                continue
+            out[ii, :T] = self.mfcc_change(mfcc[ii, :, :T], s1, s2, remove_first=remove_first, diff_method=diff_method,
+                                           out_filter=out_filter)
         return out
 
     # ---- per-kernel device timing -------------------------------------------------------
