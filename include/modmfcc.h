@@ -485,6 +485,22 @@ int mm_pyin_f32(const mm_pyin_params* p, const mm_pyin_tables* t, const float* d
 int mm_pyin_f64(const mm_pyin_params* p, const mm_pyin_tables* t, const double* d_x, int64_t rows, int64_t n,
                 int64_t x_stride, double* d_f0, uint8_t* d_voiced, double* d_voiced_prob, int32_t* d_states, void* d_ws,
                 size_t ws_bytes, void* stream);
+/* The whole path for clips of different lengths in one padded batch d_x [rows][x_stride >= n_max].  d_lengths: DEVICE
+ * int64 [rows], the valid samples of each row, clamped by the kernels into [1, n_max] (as mm_mfcc_ragged_f32 does).  Row b
+ * is computed as the clip of its first n_b samples alone: its own centre padding, its own last frame; the samples at and
+ * behind n_b never enter a result, whatever they hold.  The outputs keep the padded frame space [rows][T_max], T_max =
+ * mm_pyin_num_frames(p, n_max): row b holds T_b = mm_pyin_num_frames(p, n_b) frames (0 when center is off and n_b <
+ * frame_length) and zeros in [T_b, T_max) of all four outputs.  d_frames: DEVICE int64 [rows], receives T_b; may be NULL.
+ * The workspace follows T_max, not sum T_b: mm_pyin_ragged_workspace_bytes equals mm_pyin_workspace_bytes at n_max.
+ * Nothing is allocated, nothing synchronises.  MM_ERR_INVALID_ARG: NULL d_lengths, and every case of mm_pyin_f32
+ * (T_max < 1 among them); MM_ERR_WORKSPACE before any launch. */
+size_t mm_pyin_ragged_workspace_bytes(const mm_pyin_params* p, int64_t rows, int64_t n_max);
+int mm_pyin_ragged_f32(const mm_pyin_params* p, const mm_pyin_tables* t, const float* d_x, int64_t rows, int64_t n_max,
+                       int64_t x_stride, const int64_t* d_lengths, double* d_f0, uint8_t* d_voiced, double* d_voiced_prob,
+                       int32_t* d_states, int64_t* d_frames, void* d_ws, size_t ws_bytes, void* stream);
+int mm_pyin_ragged_f64(const mm_pyin_params* p, const mm_pyin_tables* t, const double* d_x, int64_t rows, int64_t n_max,
+                       int64_t x_stride, const int64_t* d_lengths, double* d_f0, uint8_t* d_voiced, double* d_voiced_prob,
+                       int32_t* d_states, int64_t* d_frames, void* d_ws, size_t ws_bytes, void* stream);
 /* interp_NAN(method='linear') (script/calc.py:345-385) of float64 rows: NaN samples get scipy interp1d's linear
  * interpolation between their valid neighbours, extrapolated from the first / last two valid samples at the ends.
  * Rows with fewer than two valid samples are copied unchanged (scipy raises; the host checks). d_y may equal d_x
@@ -511,6 +527,17 @@ enum {
 size_t mm_interp_nan_workspace_bytes(int32_t kind, int64_t rows, int64_t n);
 int mm_interp_nan_f64(int32_t kind, const double* d_x, int64_t rows, int64_t n, int64_t x_stride, double* d_y,
                       int64_t y_stride, void* d_ws, size_t ws_bytes, void* stream);
+/* Both interp_NAN entries with a count per row: d_counts, DEVICE int64 [rows], clamped by the kernels into [1, n_max].
+ * Row b is the curve of its first c_b samples: a sample is valid when it is not NaN and its index is below c_b, "the last
+ * sample" (the pchip end fix, the extrapolation from the last two valid samples, NEXT behind the last valid one) is
+ * c_b - 1, and columns [c_b, n_max) of d_y are written as 0.  A row with too few valid samples below c_b is copied
+ * unchanged in [0, c_b).  Workspace of the second: mm_interp_nan_workspace_bytes(kind, rows, n_max).  MM_ERR_INVALID_ARG
+ * for NULL d_counts and the cases of the entries above; MM_ERR_WORKSPACE before any launch. */
+int mm_interp_nan_linear_ragged_f64(const double* d_x, int64_t rows, int64_t n_max, int64_t x_stride,
+                                    const int64_t* d_counts, double* d_y, int64_t y_stride, void* stream);
+int mm_interp_nan_ragged_f64(int32_t kind, const double* d_x, int64_t rows, int64_t n_max, int64_t x_stride,
+                             const int64_t* d_counts, double* d_y, int64_t y_stride, void* d_ws, size_t ws_bytes,
+                             void* stream);
 /* The regrid of read_AG50x (script/calc.py:173-219): d_out[j][c] = scipy interp1d(t_in, y[:, c], 'linear')(t_out[j]) for
  * the float32 samples d_y [n][y_stride] (time-major, cols <= y_stride interleaved columns) -> float64 d_out [m][out_stride].
  * Per output time the index is scipy's: the first i with t_in[i] >= t (binary search of d_t_in, ascending), clipped to

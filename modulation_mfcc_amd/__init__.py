@@ -14,6 +14,7 @@ from .calc import (get_velocity, calculate_amplitude_envelope, velocity_batch, a
 from .filters import sosfiltfilt_batch, fir_filtfilt_batch, savgol_batch  # noqa: F401
 from .audio_io import load_audio, load_wav, resample_batch  # noqa: F401
 from .pitch import pyin_batch, pyin, interp_NAN, interp_nan_batch, get_f0  # noqa: F401
+from .pitch import pyin_ragged_batch, pyin_ragged_frames, interp_nan_ragged_batch, get_f0_batch  # noqa: F401
 from .ema import read_AG50x, read_AG50x_arrays, read_pos_header  # noqa: F401
 
 __version__ = "0.2.0"

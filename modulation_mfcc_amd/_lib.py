@@ -180,6 +180,11 @@ PROTOTYPES = {
     "mm_pyin_workspace_bytes": (C.c_size_t, [_pyp, _i64, _i64]),
     "mm_pyin_f32": (C.c_int, [_pyp, _pyt, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "mm_pyin_f64": (C.c_int, [_pyp, _pyt, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "mm_pyin_ragged_workspace_bytes": (C.c_size_t, [_pyp, _i64, _i64]),
+    "mm_pyin_ragged_f32": (C.c_int, [_pyp, _pyt, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "mm_pyin_ragged_f64": (C.c_int, [_pyp, _pyt, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "mm_interp_nan_linear_ragged_f64": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "mm_interp_nan_ragged_f64": (C.c_int, [C.c_int32, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, C.c_size_t, _vp]),
     "mm_interp_nan_linear_f64": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp]),
     "mm_interp_nan_workspace_bytes": (C.c_size_t, [C.c_int32, _i64, _i64]),
     "mm_interp_nan_f64": (C.c_int, [C.c_int32, _vp, _i64, _i64, _i64, _vp, _i64, _vp, C.c_size_t, _vp]),

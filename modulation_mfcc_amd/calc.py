@@ -15,10 +15,11 @@ import numpy as np
 from scipy.signal import savgol_filter
 
 from .filters import applyFilter
-from .pitch import get_f0, interp_NAN, interp_nan_batch  # noqa: F401
+from .pitch import get_f0, get_f0_batch, interp_NAN, interp_nan_batch, interp_nan_ragged_batch  # noqa: F401
 from .ema import read_AG50x, read_AG50x_arrays, read_pos_header  # noqa: F401
 
-__all__ = ["applyFilter", "get_f0", "interp_NAN", "interp_nan_batch", "read_AG50x", "read_AG50x_arrays", "read_pos_header",
+__all__ = ["applyFilter", "get_f0", "get_f0_batch", "interp_NAN", "interp_nan_batch", "interp_nan_ragged_batch",
+           "read_AG50x", "read_AG50x_arrays", "read_pos_header",
            "get_velocity", "calculate_amplitude_envelope", "velocity_stencil", "velocity_batch", "apply_stencil",
            "hilbert_envelope_batch", "amplitude_envelope_batch", "find_peaks_batch", "find_peaks_ex_batch",
            "peaks_to_list", "MinMaxFinder"]

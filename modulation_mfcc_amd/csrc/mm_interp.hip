@@ -45,6 +45,12 @@ __device__ __forceinline__ void ip_load_segment(const double* __restrict__ xr, i
   __syncthreads();
 }
 
+// The samples of a row: all n_max of it, or its first clamp(counts[row], 1, n_max) (the ragged entry point).  What lies
+// behind the count is no sample: never valid, never an end of the curve, and written as 0.
+__device__ __forceinline__ int64_t ip_row_count(const int64_t* __restrict__ counts, int64_t row, int64_t n_max) {
+  return counts ? min<int64_t>(max<int64_t>(counts[row], 1), n_max) : n_max;
+}
+
 // last valid sample of the segment before local index j / first one after it; -1 when there is none
 __device__ __forceinline__ int ip_seg_prev(const uint64_t* s_m, int j) {
   int w = j >> 6;
@@ -60,11 +66,13 @@ __device__ __forceinline__ int ip_seg_next(const uint64_t* s_m, int j) {
   return bits ? (w << 6) + __ffsll((unsigned long long)bits) - 1 : -1;
 }
 
-__global__ __launch_bounds__(kIpThreads) void ip_summary_kernel(const double* __restrict__ x, int64_t n, int64_t x_stride,
+__global__ __launch_bounds__(kIpThreads) void ip_summary_kernel(const double* __restrict__ x, int64_t n_max,
+                                                                int64_t x_stride, const int64_t* __restrict__ counts,
                                                                 int32_t nseg, int4* __restrict__ summary) {
   __shared__ uint64_t s_m[kIpWords];
   const int64_t row = blockIdx.x / nseg, seg = blockIdx.x % nseg;
   const int64_t base = seg * kIpSeg;
+  const int64_t n = ip_row_count(counts, row, n_max);
   double v[kIpPer];
   ip_load_segment(x + row * x_stride, n, base, v, s_m);
   if (threadIdx.x == 0) {
@@ -147,14 +155,16 @@ __device__ __forceinline__ double ip_pchip_inner(double hl, double hr, double ml
 enum { IP_PCHIP = 0, IP_NEAREST, IP_NEAREST_UP, IP_PREVIOUS, IP_NEXT, IP_ZERO, IP_SLINEAR, IP_KINDS };
 
 template <int KIND>
-__global__ __launch_bounds__(kIpThreads) void ip_eval_kernel(const double* __restrict__ x, int64_t n, int64_t x_stride,
-                                                             double* __restrict__ y, int64_t y_stride, int32_t nseg,
+__global__ __launch_bounds__(kIpThreads) void ip_eval_kernel(const double* __restrict__ x, int64_t n_max, int64_t x_stride,
+                                                             const int64_t* __restrict__ counts, double* __restrict__ y,
+                                                             int64_t y_stride, int32_t nseg,
                                                              const int4* __restrict__ carry,
                                                              const int4* __restrict__ rowinfo) {
 #pragma clang fp contract(off)
   __shared__ uint64_t s_m[kIpWords];
   const int64_t row = blockIdx.x / nseg, seg = blockIdx.x % nseg;
   const int64_t base = seg * kIpSeg;
+  const int64_t n = ip_row_count(counts, row, n_max);         // "the last sample" below is n - 1 of this row
   const double* xr = x + row * x_stride;
   double* yr = y + row * y_stride;
   double v[kIpPer];
@@ -179,7 +189,10 @@ __global__ __launch_bounds__(kIpThreads) void ip_eval_kernel(const double* __res
 #pragma unroll
   for (int k = 0; k < kIpPer; ++k) {
     const int64_t i = base + k * kIpThreads + threadIdx.x;
-    if (i >= n) continue;
+    if (i >= n) {
+      if (i < n_max) yr[i] = 0.0;                             // behind the row's count
+      continue;
+    }
     if (v[k] == v[k] || need2 < 0) { yr[i] = v[k]; continue; }
     const int64_t k1 = prev_valid(i), k2 = next_valid(i);
     double r;
@@ -269,10 +282,44 @@ size_t ip_align(size_t v) { return (v + 255) / 256 * 256; }
 int64_t ip_nseg(int64_t n) { return (n + kIpSeg - 1) / kIpSeg; }
 
 template <int KIND>
-void ip_launch_eval(unsigned blocks, hipStream_t st, const double* d_x, int64_t n, int64_t x_stride, double* d_y,
-                    int64_t y_stride, int32_t nseg, const int4* carry, const int4* rowinfo) {
-  hipLaunchKernelGGL(ip_eval_kernel<KIND>, dim3(blocks), dim3(kIpThreads), 0, st, d_x, n, x_stride, d_y, y_stride, nseg,
-                     carry, rowinfo);
+void ip_launch_eval(unsigned blocks, hipStream_t st, const double* d_x, int64_t n, int64_t x_stride, const int64_t* d_counts,
+                    double* d_y, int64_t y_stride, int32_t nseg, const int4* carry, const int4* rowinfo) {
+  hipLaunchKernelGGL(ip_eval_kernel<KIND>, dim3(blocks), dim3(kIpThreads), 0, st, d_x, n, x_stride, d_counts, d_y, y_stride,
+                     nseg, carry, rowinfo);
+}
+
+int ip_run(int32_t kind, const double* d_x, int64_t rows, int64_t n, int64_t x_stride, const int64_t* d_counts, double* d_y,
+           int64_t y_stride, void* d_ws, size_t ws_bytes, void* stream) {
+  if (kind < 0 || kind >= IP_KINDS || !d_x || !d_y || !d_ws || rows < 1 || rows > 0x7fffffff || n < 1 || n > kIpMaxN ||
+      x_stride < n || y_stride < n)
+    return MM_ERR_INVALID_ARG;
+  const int64_t nseg = ip_nseg(n);
+  if (rows * nseg > 0x7fffffff) return MM_ERR_INVALID_ARG;
+  if (ws_bytes < mm_interp_nan_workspace_bytes(kind, rows, n)) return MM_ERR_WORKSPACE;
+  char* w = (char*)d_ws;
+  int4* summary = (int4*)w;  w += ip_align((size_t)rows * nseg * sizeof(int4));
+  int4* carry = (int4*)w;    w += ip_align((size_t)rows * nseg * sizeof(int4));
+  int4* rowinfo = (int4*)w;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned blocks = (unsigned)(rows * nseg);
+  hipLaunchKernelGGL(ip_summary_kernel, dim3(blocks), dim3(kIpThreads), 0, st, d_x, n, x_stride, d_counts, (int32_t)nseg,
+                     summary);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(ip_scan_kernel, dim3((unsigned)rows), dim3(64), 0, st, summary, (int32_t)nseg, carry, rowinfo);
+  HIP_TRY(hipGetLastError());
+#define IP_EVAL(K) ip_launch_eval<K>(blocks, st, d_x, n, x_stride, d_counts, d_y, y_stride, (int32_t)nseg, carry, rowinfo)
+  switch (kind) {
+    case IP_PCHIP:      IP_EVAL(IP_PCHIP); break;
+    case IP_NEAREST:    IP_EVAL(IP_NEAREST); break;
+    case IP_NEAREST_UP: IP_EVAL(IP_NEAREST_UP); break;
+    case IP_PREVIOUS:   IP_EVAL(IP_PREVIOUS); break;
+    case IP_NEXT:       IP_EVAL(IP_NEXT); break;
+    case IP_ZERO:       IP_EVAL(IP_ZERO); break;
+    default:            IP_EVAL(IP_SLINEAR); break;
+  }
+#undef IP_EVAL
+  HIP_TRY(hipGetLastError());
+  return MM_OK;
 }
 
 }  // namespace
@@ -288,33 +335,14 @@ size_t mm_interp_nan_workspace_bytes(int32_t kind, int64_t rows, int64_t n) {
 
 int mm_interp_nan_f64(int32_t kind, const double* d_x, int64_t rows, int64_t n, int64_t x_stride, double* d_y,
                       int64_t y_stride, void* d_ws, size_t ws_bytes, void* stream) {
-  if (kind < 0 || kind >= IP_KINDS || !d_x || !d_y || !d_ws || rows < 1 || rows > 0x7fffffff || n < 1 || n > kIpMaxN ||
-      x_stride < n || y_stride < n)
-    return MM_ERR_INVALID_ARG;
-  const int64_t nseg = ip_nseg(n);
-  if (rows * nseg > 0x7fffffff) return MM_ERR_INVALID_ARG;
-  if (ws_bytes < mm_interp_nan_workspace_bytes(kind, rows, n)) return MM_ERR_WORKSPACE;
-  char* w = (char*)d_ws;
-  int4* summary = (int4*)w;  w += ip_align((size_t)rows * nseg * sizeof(int4));
-  int4* carry = (int4*)w;    w += ip_align((size_t)rows * nseg * sizeof(int4));
-  int4* rowinfo = (int4*)w;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned blocks = (unsigned)(rows * nseg);
-  hipLaunchKernelGGL(ip_summary_kernel, dim3(blocks), dim3(kIpThreads), 0, st, d_x, n, x_stride, (int32_t)nseg, summary);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(ip_scan_kernel, dim3((unsigned)rows), dim3(64), 0, st, summary, (int32_t)nseg, carry, rowinfo);
-  HIP_TRY(hipGetLastError());
-  switch (kind) {
-    case IP_PCHIP:      ip_launch_eval<IP_PCHIP>(blocks, st, d_x, n, x_stride, d_y, y_stride, (int32_t)nseg, carry, rowinfo); break;
-    case IP_NEAREST:    ip_launch_eval<IP_NEAREST>(blocks, st, d_x, n, x_stride, d_y, y_stride, (int32_t)nseg, carry, rowinfo); break;
-    case IP_NEAREST_UP: ip_launch_eval<IP_NEAREST_UP>(blocks, st, d_x, n, x_stride, d_y, y_stride, (int32_t)nseg, carry, rowinfo); break;
-    case IP_PREVIOUS:   ip_launch_eval<IP_PREVIOUS>(blocks, st, d_x, n, x_stride, d_y, y_stride, (int32_t)nseg, carry, rowinfo); break;
-    case IP_NEXT:       ip_launch_eval<IP_NEXT>(blocks, st, d_x, n, x_stride, d_y, y_stride, (int32_t)nseg, carry, rowinfo); break;
-    case IP_ZERO:       ip_launch_eval<IP_ZERO>(blocks, st, d_x, n, x_stride, d_y, y_stride, (int32_t)nseg, carry, rowinfo); break;
-    default:            ip_launch_eval<IP_SLINEAR>(blocks, st, d_x, n, x_stride, d_y, y_stride, (int32_t)nseg, carry, rowinfo); break;
-  }
-  HIP_TRY(hipGetLastError());
-  return MM_OK;
+  return ip_run(kind, d_x, rows, n, x_stride, nullptr, d_y, y_stride, d_ws, ws_bytes, stream);
+}
+
+int mm_interp_nan_ragged_f64(int32_t kind, const double* d_x, int64_t rows, int64_t n_max, int64_t x_stride,
+                             const int64_t* d_counts, double* d_y, int64_t y_stride, void* d_ws, size_t ws_bytes,
+                             void* stream) {
+  if (!d_counts) return MM_ERR_INVALID_ARG;
+  return ip_run(kind, d_x, rows, n_max, x_stride, d_counts, d_y, y_stride, d_ws, ws_bytes, stream);
 }
 
 int mm_regrid_linear_f32_f64(const float* d_y, int64_t n, int64_t cols, int64_t y_stride, const double* d_t_in,

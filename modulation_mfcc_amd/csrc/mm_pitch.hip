@@ -28,6 +28,19 @@ __device__ __forceinline__ uint64_t lanemask_lt() {
   return lane == 0 ? 0ull : (~0ull >> (64 - lane));
 }
 
+// A length per row (the ragged entry points).  Row b has n_b = clamp(lens[b], 1, n_max) samples and T_b =
+// mm_pyin_num_frames(p, n_b) frames inside the padded [rows][T_max] frame space; T_b is 0 when an uncentred row is shorter
+// than a frame.  lens == nullptr: every row has n_max samples (every other entry point).
+struct RowLens { const int64_t* lens; int64_t n_max; int frame_length; int hop; int pad2; };
+
+__device__ __forceinline__ int64_t row_samples(const RowLens& r, int64_t row) {
+  return min<int64_t>(max<int64_t>(r.lens[row], 1), r.n_max);
+}
+__device__ __forceinline__ int64_t row_frames(const RowLens& r, int64_t row) {
+  const int64_t padded = row_samples(r, row) + r.pad2;
+  return padded < r.frame_length ? 0 : 1 + (padded - r.frame_length) / r.hop;
+}
+
 template <class T> __device__ __forceinline__ T small_cut();
 template <> __device__ __forceinline__ float small_cut<float>() { return 1e-6f; }
 template <> __device__ __forceinline__ double small_cut<double>() { return 1e-6; }
@@ -44,7 +57,7 @@ __global__ __launch_bounds__(kCmndThreads) void pyin_cmnd_kernel(const T* __rest
                                                                  int64_t n_frames, int64_t tiles_per_row, int64_t tile0,
                                                                  int64_t frame0, int64_t frame_end, int F, int hop,
                                                                  int pad, int win, int min_p, int max_p, int span,
-                                                                 double* __restrict__ out) {
+                                                                 RowLens rl, double* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) double pyin_lds[];
   const int P1 = max_p + 1;
   double* ys = pyin_lds;                         // [span + kAcfLags]
@@ -52,12 +65,18 @@ __global__ __launch_bounds__(kCmndThreads) void pyin_cmnd_kernel(const T* __rest
   const int64_t tile = tile0 + blockIdx.x;
   const int64_t row = tile / tiles_per_row;
   const int64_t t0 = (tile - row * tiles_per_row) * F;
-  const int nf = (int)min<int64_t>((int64_t)F, n_frames - t0);
+  int64_t nv = n, Tv = n_frames;                 // valid samples and frames of this row
+  if (rl.lens) {
+    nv = row_samples(rl, row);
+    Tv = row_frames(rl, row);
+    if (t0 >= Tv) return;                        // a tile of dead frames: uniform over the workgroup, ahead of every barrier
+  }
+  const int nf = (int)min<int64_t>((int64_t)F, Tv - t0);
   const T* xr = x + row * x_stride;
   const int64_t g0 = t0 * hop - pad;
   for (int i = threadIdx.x; i < span + kAcfLags; i += blockDim.x) {
     const int64_t g = g0 + i;
-    ys[i] = (i < span && g >= 0 && g < n) ? (double)xr[g] : 0.0;
+    ys[i] = (i < span && g >= 0 && g < nv) ? (double)xr[g] : 0.0;
   }
   __syncthreads();
   const int f = threadIdx.x;
@@ -138,6 +157,7 @@ struct CandArgs {
   double sr, fmin, ntp;
   const double* thr; const double* beta; const double* beta_cum; const double* boltz;
   int32_t* count; int32_t* bins; double* probs; double* vp;
+  RowLens rl; int64_t frame0, T_max;             // ragged: this launch starts at flat frame frame0 of [rows][T_max]
 };
 
 __global__ __launch_bounds__(64 * kCandWaves) void pyin_cand_kernel(CandArgs a) {
@@ -150,11 +170,17 @@ __global__ __launch_bounds__(64 * kCandWaves) void pyin_cand_kernel(CandArgs a) 
   int* s_b = s_i + R;
   const int64_t fr = (int64_t)blockIdx.x * kCandWaves + wv;
   const bool live = fr < a.frames;
+  // a frame behind its row's T_b has no CMND row (the scratch keeps whatever an earlier chunk left): count 0, voiced_prob 0
+  bool rd = live;
+  if (rd && a.rl.lens) {
+    const int64_t gf = a.frame0 + fr, row = gf / a.T_max;
+    rd = gf - row * a.T_max < row_frames(a.rl, row);
+  }
   const int P = a.P;
-  const double* x = a.cmnd + (live ? fr : 0) * P;
+  const double* x = a.cmnd + (rd ? fr : 0) * P;
   // 1. troughs (util.localmin with is_trough[0] = x[0] < x[1])
   int nt = 0;
-  if (live) {
+  if (rd) {
     for (int base = 0; base < P; base += 64) {
       const int i = base + lane;
       bool tr = false;
@@ -319,6 +345,7 @@ struct VitArgs {
   double LT; double lp_voiced; double lp_unvoiced; double fill_na;
   const double* same; const double* cross; const double* freqs;
   int16_t* ptr; int32_t* states; double* f0; uint8_t* voiced;
+  RowLens rl; double* vp_tail; int64_t* frames;  // ragged: T is T_max, the row runs its own T_b; frames[row] = T_b (or NULL)
 };
 
 __device__ __forceinline__ void vit_reduce(double& v, int& i) {
@@ -339,6 +366,16 @@ __device__ __forceinline__ void vit_obs_cands(const VitArgs& a, double* lo, int6
   for (int q = threadIdx.x; q < nk; q += blockDim.x) lo[a.bins[fr * a.R + q]] = log(a.probs[fr * a.R + q] + kTiny);
 }
 
+// ragged rows: zeros in [T, TM) of every output
+__device__ __forceinline__ void vit_zero_tail(const VitArgs& a, int64_t f0i, int64_t T, int64_t TM) {
+  for (int64_t t = T + threadIdx.x; t < TM; t += blockDim.x) {
+    a.f0[f0i + t] = 0.0;
+    a.voiced[f0i + t] = 0;
+    a.vp_tail[f0i + t] = 0.0;
+    a.states[f0i + t] = 0;
+  }
+}
+
 __global__ __launch_bounds__(kVitThreads) void pyin_viterbi_kernel(VitArgs a) {
   extern __shared__ __attribute__((aligned(16))) double pyin_lds[];
   const int nb = a.n_bins, S = 2 * nb, H = a.H, W = 2 * H + 1;
@@ -346,9 +383,15 @@ __global__ __launch_bounds__(kVitThreads) void pyin_viterbi_kernel(VitArgs a) {
   double* lob = pyin_lds + 2 * S;           // [3][S]
   double* red_v = lob + 3 * S;              // [2][16]
   int* red_i = (int*)(red_v + 32);          // [2][16]
-  const int64_t row = blockIdx.x, T = a.T;
-  const int64_t f0i = row * T;
-  int16_t* ptr = a.ptr + row * T * S;
+  const int64_t row = blockIdx.x, TM = a.T;
+  const int64_t T = a.rl.lens ? row_frames(a.rl, row) : TM;     // every prefetch below stops at T: a dead frame's record
+  const int64_t f0i = row * TM;                                 // may hold any bin index
+  int16_t* ptr = a.ptr + row * TM * S;
+  if (a.rl.lens) {
+    if (a.frames && threadIdx.x == 0) a.frames[row] = T;
+    vit_zero_tail(a, f0i, T, TM);
+    if (T == 0) return;                                         // uniform over the workgroup, ahead of every barrier
+  }
   const int wv = threadIdx.x >> 6, nw = blockDim.x >> 6, lane = threadIdx.x & 63;
   // frame 0 (and the candidates of frame 1, defaults of frame 1)
   vit_obs_defaults(a, lob, f0i, S);
@@ -446,14 +489,18 @@ __global__ __launch_bounds__(kVitThreads) void pyin_viterbi_kernel(VitArgs a) {
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int kInterpThreads = 256;
 
-__global__ __launch_bounds__(kInterpThreads) void interp_linear_kernel(const double* __restrict__ x, int64_t n,
-                                                                       int64_t stride, double* __restrict__ y,
-                                                                       int64_t y_stride) {
+// counts (or nullptr): row b is the curve of its first c_b = clamp(counts[b], 1, n_max) samples -- whatever lies behind
+// is no sample of it, and columns [c_b, n_max) of the output are 0.
+__global__ __launch_bounds__(kInterpThreads) void interp_linear_kernel(const double* __restrict__ x, int64_t n_max,
+                                                                       int64_t stride, const int64_t* __restrict__ counts,
+                                                                       double* __restrict__ y, int64_t y_stride) {
   __shared__ int64_t s_first[kInterpThreads][2], s_last[kInterpThreads][2];
   __shared__ int64_t s_ends[4];
   const double* xr = x + blockIdx.x * stride;
   double* yr = y + blockIdx.x * y_stride;
   const int t = threadIdx.x;
+  const int64_t n = counts ? min<int64_t>(max<int64_t>(counts[blockIdx.x], 1), n_max) : n_max;
+  for (int64_t i = n + t; i < n_max; i += kInterpThreads) yr[i] = 0.0;
   const int64_t L = (n + kInterpThreads - 1) / kInterpThreads;
   const int64_t b = min<int64_t>(n, t * L), e = min<int64_t>(n, b + L);
   int64_t f1 = -1, f2 = -1, l1 = -1, l2 = -1;     // first two / last two valid samples of the segment
@@ -532,9 +579,13 @@ size_t records_bytes(const mm_pyin_params* p, int64_t frames) {
 
 size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
+RowLens row_lens(const mm_pyin_params* p, const int64_t* d_lens, int64_t n_max) {
+  return RowLens{d_lens, n_max, p->frame_length, p->hop_length, p->center ? 2 * (p->frame_length / 2) : 0};
+}
+
 template <class T>
-int launch_cmnd(const mm_pyin_params* p, const T* d_x, int64_t rows, int64_t n, int64_t x_stride, int64_t frame0,
-                int64_t frame_end, double* d_out, hipStream_t st) {
+int launch_cmnd(const mm_pyin_params* p, const T* d_x, int64_t rows, int64_t n, int64_t x_stride, const int64_t* d_lens,
+                int64_t frame0, int64_t frame_end, double* d_out, hipStream_t st) {
   int span = 0;
   size_t lds = 0;
   const int F = cmnd_tile_frames(p, &span, &lds);
@@ -554,15 +605,17 @@ int launch_cmnd(const mm_pyin_params* p, const T* d_x, int64_t rows, int64_t n, 
     const int64_t nt = std::min<int64_t>(tile1 - tb, 1 << 30);
     hipLaunchKernelGGL(pyin_cmnd_kernel<T>, dim3((unsigned)nt), dim3(kCmndThreads), lds, st, d_x, n, x_stride, nT, tpr, tb,
                        frame0, frame_end, F, p->hop_length, p->center ? p->frame_length / 2 : 0, p->win_length,
-                       p->min_period, p->max_period, span, d_out);
+                       p->min_period, p->max_period, span, row_lens(p, d_lens, n), d_out);
     HIP_TRY(hipGetLastError());
   }
   return MM_OK;
 }
 
 int launch_cand(const mm_pyin_params* p, const mm_pyin_tables* tb, const double* d_cmnd, int64_t frames, int32_t* d_count,
-                int32_t* d_bins, double* d_probs, double* d_vp, hipStream_t st) {
+                int32_t* d_bins, double* d_probs, double* d_vp, const int64_t* d_lens, int64_t n_max, int64_t frame0,
+                hipStream_t st) {
   CandArgs a;
+  a.rl = row_lens(p, d_lens, n_max); a.frame0 = frame0; a.T_max = d_lens ? mm_pyin_num_frames(p, n_max) : 1;
   a.cmnd = d_cmnd; a.frames = frames; a.P = (int)n_lags(p); a.min_p = p->min_period; a.n_thr = p->n_thresholds;
   a.R = p->max_troughs; a.n_bins = p->n_bins; a.nbps = p->nbps; a.sr = p->sr; a.fmin = p->fmin; a.ntp = p->no_trough_prob;
   a.thr = tb->thresholds; a.beta = tb->beta_probs; a.beta_cum = tb->beta_cum; a.boltz = tb->boltzmann;
@@ -581,9 +634,10 @@ int launch_cand(const mm_pyin_params* p, const mm_pyin_tables* tb, const double*
 }
 
 int launch_vit(const mm_pyin_params* p, const mm_pyin_tables* tb, const int32_t* d_count, const int32_t* d_bins,
-               const double* d_probs, const double* d_vp, int64_t rows, int64_t T, int32_t* d_states, double* d_f0,
-               uint8_t* d_voiced, int16_t* d_ptr, hipStream_t st) {
+               const double* d_probs, double* d_vp, int64_t rows, int64_t T, int32_t* d_states, double* d_f0,
+               uint8_t* d_voiced, int16_t* d_ptr, const int64_t* d_lens, int64_t n_max, int64_t* d_frames, hipStream_t st) {
   VitArgs a;
+  a.rl = row_lens(p, d_lens, n_max); a.vp_tail = d_vp; a.frames = d_frames;
   a.count = d_count; a.bins = d_bins; a.probs = d_probs; a.vp = d_vp; a.T = T; a.R = p->max_troughs; a.n_bins = p->n_bins;
   a.H = p->band_h; a.LT = p->log_tiny; a.lp_voiced = p->log_p_init[0]; a.lp_unvoiced = p->log_p_init[1];
   a.fill_na = p->fill_na; a.same = tb->log_same; a.cross = tb->log_cross; a.freqs = tb->freqs;
@@ -606,9 +660,11 @@ bool tables_ok(const mm_pyin_tables* t) {
 
 template <class T>
 int pyin_whole(const mm_pyin_params* p, const mm_pyin_tables* tb, const T* d_x, int64_t rows, int64_t n, int64_t x_stride,
-               double* d_f0, uint8_t* d_voiced, double* d_vp, int32_t* d_states, void* d_ws, size_t ws_bytes, void* stream) {
+               bool ragged, const int64_t* d_lens, int64_t* d_frames, double* d_f0, uint8_t* d_voiced, double* d_vp,
+               int32_t* d_states, void* d_ws, size_t ws_bytes, void* stream) {
   int rc = mm_pyin_check(p);
   if (rc) return rc;
+  if (ragged && !d_lens) return MM_ERR_INVALID_ARG;
   if (!tables_ok(tb) || !d_x || !d_f0 || !d_voiced || !d_vp || !d_states || !d_ws || rows < 1 || rows > 0x7fffffff ||
       n < 1 || x_stride < n)
     return MM_ERR_INVALID_ARG;
@@ -626,12 +682,12 @@ int pyin_whole(const mm_pyin_params* p, const mm_pyin_tables* tb, const T* d_x, 
   const int64_t chunk = std::min<int64_t>(frames, kCmndChunkFrames);
   for (int64_t f0 = 0; f0 < frames; f0 += chunk) {
     const int64_t f1 = std::min(frames, f0 + chunk);
-    rc = launch_cmnd<T>(p, d_x, rows, n, x_stride, f0, f1, cmnd, st);
+    rc = launch_cmnd<T>(p, d_x, rows, n, x_stride, d_lens, f0, f1, cmnd, st);
     if (rc) return rc;
-    rc = launch_cand(p, tb, cmnd, f1 - f0, count + f0, bins + f0 * R, probs + f0 * R, d_vp + f0, st);
+    rc = launch_cand(p, tb, cmnd, f1 - f0, count + f0, bins + f0 * R, probs + f0 * R, d_vp + f0, d_lens, n, f0, st);
     if (rc) return rc;
   }
-  return launch_vit(p, tb, count, bins, probs, d_vp, rows, nT, d_states, d_f0, d_voiced, ptr, st);
+  return launch_vit(p, tb, count, bins, probs, d_vp, rows, nT, d_states, d_f0, d_voiced, ptr, d_lens, n, d_frames, st);
 }
 
 }  // namespace
@@ -683,8 +739,8 @@ int mm_pyin_cmnd(const mm_pyin_params* p, const void* d_x, int32_t dtype, int64_
   const int64_t T = mm_pyin_num_frames(p, n);
   if (T < 1) return MM_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == 0) return launch_cmnd<float>(p, (const float*)d_x, rows, n, x_stride, 0, rows * T, d_cmnd, st);
-  return launch_cmnd<double>(p, (const double*)d_x, rows, n, x_stride, 0, rows * T, d_cmnd, st);
+  if (dtype == 0) return launch_cmnd<float>(p, (const float*)d_x, rows, n, x_stride, nullptr, 0, rows * T, d_cmnd, st);
+  return launch_cmnd<double>(p, (const double*)d_x, rows, n, x_stride, nullptr, 0, rows * T, d_cmnd, st);
 }
 
 int mm_pyin_candidates(const mm_pyin_params* p, const mm_pyin_tables* t, const double* d_cmnd, int64_t frames,
@@ -692,7 +748,7 @@ int mm_pyin_candidates(const mm_pyin_params* p, const mm_pyin_tables* t, const d
   int rc = mm_pyin_check(p);
   if (rc) return rc;
   if (!tables_ok(t) || !d_cmnd || frames < 1 || !d_count || !d_bins || !d_probs || !d_voiced_prob) return MM_ERR_INVALID_ARG;
-  return launch_cand(p, t, d_cmnd, frames, d_count, d_bins, d_probs, d_voiced_prob, (hipStream_t)stream);
+  return launch_cand(p, t, d_cmnd, frames, d_count, d_bins, d_probs, d_voiced_prob, nullptr, 0, 0, (hipStream_t)stream);
 }
 
 size_t mm_pyin_decode_workspace_bytes(const mm_pyin_params* p, int64_t rows, int64_t n_frames) {
@@ -709,27 +765,57 @@ int mm_pyin_decode(const mm_pyin_params* p, const mm_pyin_tables* t, const int32
       !d_states || !d_f0 || !d_voiced || !d_ws)
     return MM_ERR_INVALID_ARG;
   if (ws_bytes < mm_pyin_decode_workspace_bytes(p, rows, n_frames)) return MM_ERR_WORKSPACE;
-  return launch_vit(p, t, d_count, d_bins, d_probs, d_voiced_prob, rows, n_frames, d_states, d_f0, d_voiced,
-                    (int16_t*)d_ws, (hipStream_t)stream);
+  return launch_vit(p, t, d_count, d_bins, d_probs, const_cast<double*>(d_voiced_prob), rows, n_frames, d_states, d_f0,
+                    d_voiced, (int16_t*)d_ws, nullptr, 0, nullptr, (hipStream_t)stream);
 }
 
 int mm_pyin_f32(const mm_pyin_params* p, const mm_pyin_tables* t, const float* d_x, int64_t rows, int64_t n,
                 int64_t x_stride, double* d_f0, uint8_t* d_voiced, double* d_voiced_prob, int32_t* d_states, void* d_ws,
                 size_t ws_bytes, void* stream) {
-  return pyin_whole<float>(p, t, d_x, rows, n, x_stride, d_f0, d_voiced, d_voiced_prob, d_states, d_ws, ws_bytes, stream);
+  return pyin_whole<float>(p, t, d_x, rows, n, x_stride, false, nullptr, nullptr, d_f0, d_voiced, d_voiced_prob, d_states,
+                           d_ws, ws_bytes, stream);
 }
 
 int mm_pyin_f64(const mm_pyin_params* p, const mm_pyin_tables* t, const double* d_x, int64_t rows, int64_t n,
                 int64_t x_stride, double* d_f0, uint8_t* d_voiced, double* d_voiced_prob, int32_t* d_states, void* d_ws,
                 size_t ws_bytes, void* stream) {
-  return pyin_whole<double>(p, t, d_x, rows, n, x_stride, d_f0, d_voiced, d_voiced_prob, d_states, d_ws, ws_bytes, stream);
+  return pyin_whole<double>(p, t, d_x, rows, n, x_stride, false, nullptr, nullptr, d_f0, d_voiced, d_voiced_prob, d_states,
+                            d_ws, ws_bytes, stream);
+}
+
+size_t mm_pyin_ragged_workspace_bytes(const mm_pyin_params* p, int64_t rows, int64_t n_max) {
+  return mm_pyin_workspace_bytes(p, rows, n_max);           // the frame space is [rows][T_max]
+}
+
+int mm_pyin_ragged_f32(const mm_pyin_params* p, const mm_pyin_tables* t, const float* d_x, int64_t rows, int64_t n_max,
+                       int64_t x_stride, const int64_t* d_lengths, double* d_f0, uint8_t* d_voiced, double* d_voiced_prob,
+                       int32_t* d_states, int64_t* d_frames, void* d_ws, size_t ws_bytes, void* stream) {
+  return pyin_whole<float>(p, t, d_x, rows, n_max, x_stride, true, d_lengths, d_frames, d_f0, d_voiced, d_voiced_prob,
+                           d_states, d_ws, ws_bytes, stream);
+}
+
+int mm_pyin_ragged_f64(const mm_pyin_params* p, const mm_pyin_tables* t, const double* d_x, int64_t rows, int64_t n_max,
+                       int64_t x_stride, const int64_t* d_lengths, double* d_f0, uint8_t* d_voiced, double* d_voiced_prob,
+                       int32_t* d_states, int64_t* d_frames, void* d_ws, size_t ws_bytes, void* stream) {
+  return pyin_whole<double>(p, t, d_x, rows, n_max, x_stride, true, d_lengths, d_frames, d_f0, d_voiced, d_voiced_prob,
+                            d_states, d_ws, ws_bytes, stream);
 }
 
 int mm_interp_nan_linear_f64(const double* d_x, int64_t rows, int64_t n, int64_t x_stride, double* d_y, int64_t y_stride,
                              void* stream) {
   if (!d_x || !d_y || rows < 1 || rows > 0x7fffffff || n < 1 || x_stride < n || y_stride < n) return MM_ERR_INVALID_ARG;
   hipLaunchKernelGGL(interp_linear_kernel, dim3((unsigned)rows), dim3(kInterpThreads), 0, (hipStream_t)stream, d_x, n,
-                     x_stride, d_y, y_stride);
+                     x_stride, (const int64_t*)nullptr, d_y, y_stride);
+  HIP_TRY(hipGetLastError());
+  return MM_OK;
+}
+
+int mm_interp_nan_linear_ragged_f64(const double* d_x, int64_t rows, int64_t n_max, int64_t x_stride,
+                                    const int64_t* d_counts, double* d_y, int64_t y_stride, void* stream) {
+  if (!d_x || !d_y || !d_counts || rows < 1 || rows > 0x7fffffff || n_max < 1 || x_stride < n_max || y_stride < n_max)
+    return MM_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(interp_linear_kernel, dim3((unsigned)rows), dim3(kInterpThreads), 0, (hipStream_t)stream, d_x, n_max,
+                     x_stride, d_counts, d_y, y_stride);
   HIP_TRY(hipGetLastError());
   return MM_OK;
 }

@@ -2,6 +2,8 @@
 (script/calc.py:386-592), and its ``interp_NAN`` (:345-385).
 
     pyin_batch(audio [B, n] | [n] device tensor, sr, fmin=, fmax=, ...)  -> (f0, voiced_flag, voiced_prob) on the device
+    pyin_ragged_batch(audio [B, n_max], lengths [B], sr, ...)             -> the same with a length per clip (+ frames [B])
+    get_f0_batch(clips, sr, method='pyin', ...)                           -> [(f0, f0t), ...]: get_f0 of a list of clips
     pyin(y, fmin=, fmax=, sr=22050, ...)                                  -> librosa.pyin's signature: numpy in, numpy out
     interp_NAN(X, method='linear')                                        -> 'linear' on the device, other kinds via scipy
     get_f0(x, sr, method='pyin', ...)                                     -> (f0, f0t), the reference's signature
@@ -25,7 +27,8 @@ from scipy import interpolate
 
 from .filters import applyFilter
 
-__all__ = ["pyin_batch", "pyin", "interp_NAN", "get_f0", "pyin_sizes", "beta_tables", "boltzmann_table",
+__all__ = ["pyin_batch", "pyin_ragged_batch", "pyin_ragged_frames", "pyin", "interp_NAN", "interp_nan_batch",
+           "interp_nan_ragged_batch", "get_f0", "get_f0_batch", "pyin_sizes", "beta_tables", "boltzmann_table",
            "transition_matrix", "banded_log_transitions", "pitch_freqs", "pyin_params", "pyin_cmnd", "pyin_records"]
 
 TINY = np.finfo(np.float64).tiny
@@ -295,6 +298,91 @@ def pyin_batch(audio, sr, *, fmin, fmax, frame_length=2048, win_length=None, hop
     return tuple(o[0] for o in out) if squeeze else out
 
 
+def pyin_ragged_frames(lengths, frame_length, hop_length, center=True):
+    """Frames of clips of ``lengths`` samples (host integers) -> int64 numpy array: mm_pyin_num_frames per clip, 0 for a
+    clip too short for one frame (only without centring).  No GPU needed."""
+    n = np.asarray(lengths, dtype=np.int64)
+    padded = n + (2 * (int(frame_length) // 2) if center else 0)
+    return np.where((n >= 1) & (padded >= frame_length), 1 + (padded - int(frame_length)) // int(hop_length), 0).astype(np.int64)
+
+
+_MSG_SHORT = "pyin: a signal of {} samples is shorter than frame_length={}"
+
+
+def pyin_ragged_batch(audio, lengths, sr, *, fmin, fmax, frame_length=2048, win_length=None, hop_length=None,
+                      n_thresholds=100, beta_parameters=(2, 18), boltzmann_parameter=2, resolution=0.1,
+                      max_transition_rate=35.92, switch_prob=0.01, no_trough_prob=0.01, fill_na=np.nan, center=True,
+                      pad_mode="constant", return_states=False):
+    """pyin_batch for clips of different lengths in one padded batch: ``audio`` [B, n_max] (float32 or float64 on the
+    device, any row pitch >= n_max) and one valid sample count per clip -> (f0, voiced_flag, voiced_prob, frames), each
+    [B, T_max] but ``frames`` (int64 [B] on the device), and the states under ``return_states``.  Row b holds, in the
+    columns [0, frames[b]), exactly what pyin_batch returns for audio[b, :lengths[b]] alone -- its own centre padding, its
+    own last frame, its own decode -- and zeros behind them; what the padding of ``audio`` holds never matters.
+
+    ``lengths``: host integers (validated: ValueError outside [1, n_max], and pyin_batch's ValueError with the clip's index
+    for a clip without a frame) or an int64 device tensor (no read-back; the kernels clamp it, and a clip without a frame
+    gets an all-zero row and frames[b] == 0).  ``center=True`` with another ``pad_mode`` than 'constant' needs host
+    lengths: every clip is padded alone and the batch is packed again.  The scratch follows T_max, not the sum of the
+    clips' frames; batches are cut to PYIN_WS_BYTES as in pyin_batch."""
+    import torch
+    from . import _lib
+    from .plan import check_lengths
+    x, _ = _as_signal(audio)
+    if audio.dim() != 2:
+        raise ValueError("audio must be [B, n_max]")
+    B, n = x.shape
+    lens = check_lengths(lengths, B, n, x.device)
+    on_host = isinstance(lens, np.ndarray)
+    if center and pad_mode != "constant":
+        if not on_host:
+            raise ValueError(f"pad_mode={pad_mode!r} pads every clip on its own: lengths must be host values")
+        h = frame_length // 2
+        padded = torch.empty((B, n + 2 * h), dtype=x.dtype, device=x.device)
+        for b in range(B):
+            padded[b, :int(lens[b]) + 2 * h] = _pad_center(x[b:b + 1, :int(lens[b])], frame_length, pad_mode)[0]
+        x, n, lens, center = padded, n + 2 * h, lens + 2 * h, False
+    p, z = pyin_params(n, sr, fmin=fmin, fmax=fmax, frame_length=frame_length, win_length=win_length,
+                       hop_length=hop_length, n_thresholds=n_thresholds, resolution=resolution,
+                       max_transition_rate=max_transition_rate, switch_prob=switch_prob, no_trough_prob=no_trough_prob,
+                       fill_na=fill_na, center=center)
+    T = z["n_frames"]
+    if T < 1:
+        raise ValueError(_MSG_SHORT.format(n, frame_length))
+    if on_host:
+        none = np.flatnonzero(pyin_ragged_frames(lens, frame_length, z["hop_length"], center) < 1)
+        if none.size:
+            raise ValueError(_MSG_SHORT.format(int(lens[none[0]]), frame_length) + f" (clip {int(none[0])})")
+    lib = _lib.load()
+    dev = x.device
+    tabs = _tables(p, z, switch_prob, beta_parameters, boltzmann_parameter, dev)
+    p.band_h = tabs.H
+    f0 = torch.empty((B, T), dtype=torch.float64, device=dev)
+    voiced = torch.empty((B, T), dtype=torch.uint8, device=dev)
+    vprob = torch.empty((B, T), dtype=torch.float64, device=dev)
+    states = torch.empty((B, T), dtype=torch.int32, device=dev)
+    frames = torch.empty(B, dtype=torch.int64, device=dev)
+    need = lib.mm_pyin_ragged_workspace_bytes
+    rows = B
+    while rows > 1 and need(C.byref(p), rows, n) > PYIN_WS_BYTES:
+        rows = max(1, min(rows - 1, rows * PYIN_WS_BYTES // need(C.byref(p), rows, n)))
+    ws = torch.empty(int(need(C.byref(p), rows, n)), dtype=torch.uint8, device=dev)
+    f32 = x.dtype == torch.float32
+    name = "mm_pyin_ragged_f32" if f32 else "mm_pyin_ragged_f64"
+    with torch.cuda.device(dev):
+        lens_dev = torch.from_numpy(lens).to(dev, non_blocking=True) if on_host else lens      # (on the current stream)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        for r0 in range(0, B, rows):
+            r = min(rows, B - r0)
+            fn = lib.mm_pyin_ragged_f32 if f32 else lib.mm_pyin_ragged_f64
+            _lib.check(fn(C.byref(p), C.byref(tabs.c), x[r0].data_ptr(), r, n, _row_pitch(x), lens_dev[r0:].data_ptr(),
+                          f0[r0].data_ptr(), voiced[r0].data_ptr(), vprob[r0].data_ptr(), states[r0].data_ptr(),
+                          frames[r0:].data_ptr(), ws.data_ptr(), ws.numel(), stream), name)
+    if fill_na is None:                 # librosa keeps the decoded bin's frequency on unvoiced frames: of real frames only
+        live = torch.arange(T, device=dev)[None, :] < frames[:, None]
+        f0 = tabs.dev["freqs"][(states % z["n_bins"]).long()] * live
+    return (f0, voiced.bool(), vprob, frames) + ((states,) if return_states else ())
+
+
 def pyin_cmnd(audio, sr, *, fmin, fmax, frame_length=2048, win_length=None, hop_length=None, center=True):
     """Stage: the cumulative-mean-normalised difference rows [B, n_frames, max_period - min_period + 1] (float64) of
     a device batch (mm_pyin_cmnd; zero padding when centred)."""
@@ -476,6 +564,63 @@ def interp_nan_batch(x, method: str = "linear"):
     raise ValueError(f"interp_nan_batch: unknown method {method!r}")
 
 
+def interp_nan_ragged_batch(x, counts, method: str = "linear"):
+    """interp_nan_batch with a count per row: ``x`` [rows, n_max] on the device, ``counts`` [rows] (host integers,
+    validated: ValueError outside [1, n_max]; or an int64 device tensor, clamped by the kernels) -> [rows, n_max] of x's
+    dtype.  Row b holds interp_nan_batch(x[b, :counts[b]], method) in the columns [0, counts[b]) and zeros behind them;
+    what x holds behind a row's count never matters.  The methods and the errors are interp_nan_batch's, the errors taken
+    from the smallest number of valid samples below a row's count, in one read-back."""
+    import torch
+    from . import _lib
+    from .plan import _check_counts
+    if not _is_device_tensor(x):
+        raise TypeError("interp_nan_ragged_batch takes a CUDA(HIP) tensor")
+    if method != "linear" and method not in _INTERP_KINDS:
+        if method in _INTERP_HOST_KINDS:
+            raise NotImplementedError(f"method={method!r} needs a banded solve over all knots; not on the device")
+        raise ValueError(f"interp_nan_ragged_batch: unknown method {method!r}")
+    if x.dim() != 2:
+        raise ValueError("x must be [rows, n_max]")
+    if not x.is_floating_point():
+        raise TypeError("x must be a floating-point tensor")
+    rows, n = x.shape
+    if rows == 0 or n == 0:
+        return x.clone()
+    dev = x.device
+    cnt = _check_counts(counts, rows, n, dev, "counts")
+    xd = x.to(torch.float64)
+    if xd.stride(1) != 1 or (rows > 1 and xd.stride(0) < n):
+        xd = xd.contiguous()
+    pitch_ = xd.stride(0) if rows > 1 else n
+    with torch.cuda.device(dev):
+        cd = torch.from_numpy(cnt).to(dev, non_blocking=True) if isinstance(cnt, np.ndarray) else cnt
+        c = cd.clamp(1, n)
+        valid = ((~torch.isnan(xd)) & (torch.arange(n, device=dev)[None, :] < c[:, None])).sum(dim=1)
+        if method == "linear":                              # scipy.interpolate.interp1d needs two points, NaN or not
+            if int(valid.min()) < 2:
+                raise ValueError("x and y arrays must have at least 2 entries")
+        else:                                               # a row without a NaN below its count is returned as it is
+            fewest = int(torch.where(valid < c, valid, torch.full_like(valid, 2)).min())
+            if method == "slinear" and fewest < 2:
+                raise ValueError("x and y arrays must have at least 2 entries")
+            if fewest < 1:
+                if method == "pchip":
+                    raise IndexError("index 0 is out of bounds for axis 0 with size 0")
+                raise ValueError("cannot reshape array of size 0 into shape (0,newaxis)")
+        y = torch.empty((rows, n), dtype=torch.float64, device=dev)
+        lib = _lib.load()
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        if method == "linear":
+            _lib.check(lib.mm_interp_nan_linear_ragged_f64(xd.data_ptr(), rows, n, pitch_, cd.data_ptr(), y.data_ptr(), n,
+                                                           stream), "mm_interp_nan_linear_ragged_f64")
+        else:
+            kind = _INTERP_KINDS[method]
+            ws = torch.empty(int(lib.mm_interp_nan_workspace_bytes(kind, rows, n)), dtype=torch.uint8, device=dev)
+            _lib.check(lib.mm_interp_nan_ragged_f64(kind, xd.data_ptr(), rows, n, pitch_, cd.data_ptr(), y.data_ptr(), n,
+                                                    ws.data_ptr(), ws.numel(), stream), "mm_interp_nan_ragged_f64")
+    return y.to(x.dtype)
+
+
 def interp_NAN(X, method: str = "linear"):
     """script/calc.py:345-385: NaN samples of a curve filled by interpolation.  'linear' (scipy interp1d, extrapolated at
     the ends) runs on the device (mm_interp_nan_linear_f64) for numpy curves and CUDA(HIP) tensors ([n] or [rows, n]).
@@ -553,3 +698,107 @@ def get_f0(x, sr: float, method: str = "praatac", hopSize: float = 0.01, minPitc
     if not on_device:
         f0 = f0.cpu().numpy()
     return f0, f0t
+
+
+def get_f0_batch(clips, sr: float, method: str = "praatac", hopSize: float = 0.01, minPitch: float = 75,
+                 maxPitch: float = 600, interpUnvoiced="linear", outFilter="iir", outFiltType: str = "low",
+                 outFiltCutOff=[None], outFiltLen: int = 6, outFiltPolyOrd: int = 3, minMaxQuant=None, maxCandNum: int = 15,
+                 veryAccurate: bool = False, silenceThresh: float = 0.03, voicingThresh: float = 0.45,
+                 octaveCost: float = 0.01, octaveJumpCost: float = 0.35, voicedUnvoicedCost: float = 0.14,
+                 pyinframe_length: int = 2048, pyinwin_length: int = None, n_thresholds: int = 100,
+                 beta_parameters: tuple = (2, 18), boltzmann_parameter: int = 2, resolution: float = 0.1,
+                 max_transition_rate: float = 35.92, switch_prob: float = 0.01, no_trough_prob: float = 0.01,
+                 pyinfill_na: float = np.nan, pyincenter: bool = True, pyinpad_mode: str = "constant"):
+    """``get_f0`` for a list of clips of any lengths -> a list of ``(f0, f0t)``, one per clip, each what ``get_f0`` returns
+    for that clip alone: a numpy pair for a numpy clip, a device tensor and a numpy ``f0t`` for a CUDA(HIP) clip [n].
+
+    The float32 clips and the others (float64; integer PCM becomes float64) form one padded batch each, so every clip keeps
+    the precision it has alone, and run through pyin_ragged_batch.  ``interpUnvoiced`` runs ragged on the device
+    (interp_nan_ragged_batch; 'quadratic' and 'cubic' per clip through scipy, as interp_NAN does).  ``outFilter`` is
+    applied per group of clips with the same frame count, through applyFilter on [g, T].  ``minMaxQuant``: the first pass
+    is ragged; the second has its own fmin / fmax, and with them its own pitch bins and transition band, per clip, so it
+    runs pyin_batch clip by clip.  The errors are get_f0's, with the clip's index appended where one clip is at fault."""
+    if (interpUnvoiced is None) & (outFilter is not None):
+        raise Exception(_MSG_GAPS)
+    if method in ("praatac", "praatcc"):
+        raise NotImplementedError(f"method={method!r} calls Praat through parselmouth; not part of this build")
+    if method != "pyin":
+        raise UnboundLocalError(f"get_f0: unknown method {method!r}")     # reference: f0 unbound
+    import torch
+    from .plan import by_length
+    clips = list(clips)
+    on_device = [_is_device_tensor(c) for c in clips]
+    sigs = [c if d else _to_device_signal(c) for c, d in zip(clips, on_device)]
+    hop_length = int(hopSize * sr)
+    kw = dict(sr=sr, frame_length=pyinframe_length, win_length=pyinwin_length, hop_length=hop_length,
+              n_thresholds=n_thresholds, beta_parameters=beta_parameters, boltzmann_parameter=boltzmann_parameter,
+              resolution=resolution, max_transition_rate=max_transition_rate, switch_prob=switch_prob,
+              no_trough_prob=no_trough_prob, fill_na=pyinfill_na, center=pyincenter, pad_mode=pyinpad_mode)
+    for i, s in enumerate(sigs):
+        if s.dim() != 1:
+            raise ValueError(f"audio must be [n] (clip {i})")
+        if s.shape[0] < 1 or pyin_ragged_frames([s.shape[0]], pyinframe_length, max(hop_length, 1), pyincenter)[0] < 1:
+            raise ValueError(_MSG_SHORT.format(s.shape[0], pyinframe_length) + f" (clip {i})")
+    out = [None] * len(clips)
+    groups = ([i for i, s in enumerate(sigs) if s.dtype == torch.float32],
+              [i for i, s in enumerate(sigs) if s.dtype != torch.float32])
+    for idx in groups:
+        if not idx:
+            continue
+        dev = sigs[idx[0]].device
+        dtype = torch.float32 if sigs[idx[0]].dtype == torch.float32 else torch.float64
+        lengths = np.array([sigs[i].shape[0] for i in idx], dtype=np.int64)
+        audio = torch.empty((len(idx), int(lengths.max())), dtype=dtype, device=dev)
+        for b, i in enumerate(idx):
+            audio[b, :lengths[b]].copy_(sigs[i], non_blocking=True)       # (integer PCM: converted to float64 here)
+        f0 = pyin_ragged_batch(audio, lengths, fmin=minPitch, fmax=maxPitch, **kw)[0]
+        frames = pyin_ragged_frames(lengths, pyinframe_length, hop_length, pyincenter)
+        if minMaxQuant is not None:
+            first = f0.cpu().numpy()
+            for b, i in enumerate(idx):
+                h = first[b, :frames[b]]
+                h = h[np.isnan(h) == 0]
+                try:
+                    quants = np.quantile(h, [minMaxQuant[0], minMaxQuant[1]])
+                    f0[b, :frames[b]] = pyin_batch(audio[b, :lengths[b]], fmin=quants[0], fmax=quants[1], **kw)[0]
+                except (ValueError, IndexError, NotImplementedError) as e:
+                    raise type(e)(f"{e} (clip {i})") from e
+        if interpUnvoiced is not None:
+            if interpUnvoiced == "linear" or interpUnvoiced in _INTERP_KINDS:
+                try:
+                    f0 = interp_nan_ragged_batch(f0, frames, interpUnvoiced)
+                except (ValueError, IndexError) as e:
+                    _blame_clip(e, lambda b: interp_NAN(f0[b, :frames[b]], interpUnvoiced), idx)
+            else:
+                for b, i in enumerate(idx):
+                    try:
+                        f0[b, :frames[b]] = interp_NAN(f0[b, :frames[b]], interpUnvoiced)
+                    except (ValueError, IndexError) as e:
+                        raise type(e)(f"{e} (clip {i})") from e
+        curves = [None] * len(idx)
+        if outFilter is not None:
+            for T, g in by_length(frames):
+                rows = f0[torch.from_numpy(g).to(dev), :T]
+                try:
+                    y = applyFilter(rows, 1 / hopSize, filt=outFilter, cutOff=outFiltCutOff, filtLen=outFiltLen,
+                                    filtType=outFiltType, polyOrd=outFiltPolyOrd)
+                except ValueError as e:                                   # (too few frames for the filter)
+                    raise ValueError(f"{e} (clip {idx[int(g[0])]})") from e
+                for k, b in enumerate(g):
+                    curves[int(b)] = y[k]
+        else:
+            curves = [f0[b, :frames[b]] for b in range(len(idx))]
+        for b, i in enumerate(idx):
+            f = curves[b].clone() if on_device[i] else curves[b].cpu().numpy()
+            out[i] = (f, np.arange(int(frames[b])) * hopSize)
+    return out
+
+
+def _blame_clip(err, one, idx):
+    """A batched call raised ``err``: run ``one(b)`` clip by clip and raise the first clip's own error with its index."""
+    for b, i in enumerate(idx):
+        try:
+            one(b)
+        except type(err) as e:
+            raise type(e)(f"{e} (clip {i})") from e
+    raise err
