@@ -26,6 +26,10 @@
  *   mm_fir_filtfilt_f64,
  *   mm_savgol_f64          <- applyFilter(filt='fir' | 'sg') and get_velocity(method='sg') with filters of any length:
  *                             scipy filtfilt(b, 1, x) / savgol_filter(mode='interp') on a batch
+ *   mm_sosfiltfilt_ragged_f64, mm_stencil_ragged_f64,
+ *   mm_fir_filtfilt_ragged_f64,
+ *   mm_savgol_ragged_f64   <- the four filters above on a padded batch with one length per curve, each curve filtered as
+ *                             if it were called alone, bit for bit (build-defined; no reference site)
  *   mm_rms_f32,
  *   mm_hilbert_envelope    <- calculate_amplitude_envelope (script/calc.py:284-343): librosa.feature.rms /
  *                             |scipy.signal.hilbert| -- row N3
@@ -348,6 +352,46 @@ int mm_fir_filtfilt_f32_f64(const float* d_x, int64_t rows, int64_t n, int64_t x
                             double* d_y, int64_t y_stride, void* stream);
 int mm_savgol_f64(const double* d_x, int64_t rows, int64_t n, int64_t x_stride, const double* d_c, const double* d_q,
                   const double* d_p, int32_t window, int32_t n_basis, double* d_y, int64_t y_stride, void* stream);
+
+/* The filters above for a ragged batch (no reference site: the reference filters one curve per call): the arguments of
+ * the single-length entry point with n read as n_max, the longest row, and d_lens (DEVICE, int64 [rows]), one length per
+ * row, the convention of d_frames of mm_mfcc_change_ragged_f64.  d_y is [rows][n_max] ([rows][y_stride] for the FIR and
+ * Savitzky-Golay entries).  With n_b = d_lens[b], clamped on the device into [1, n_max]:
+ *   columns [0, n_b) of row b = BIT FOR BIT what the single-length entry point writes for d_x[b][0 .. n_b) alone (rows = 1,
+ *     n = n_b): both odd extensions about the row's own first and last sample (in float32 for the _f32_f64 entries), the
+ *     backward IIR pass from the row's own end, the Savitzky-Golay edge fits on the row's own first and last window, the
+ *     stencil's right edge rows at n_b;
+ *   columns [n_b, n_max) = +0.0.
+ * Nothing at or behind n_b is loaded, whatever it holds (NaN, Inf, another row's data), and nothing outside
+ * [rows][x_stride] is touched.  A row scipy would refuse -- n_b <= padlen (sosfiltfilt), n_b <= 3 n_taps (FIR), window > n_b
+ * (Savitzky-Golay), n_b < max(2 n_edge, edge_w) (stencil) -- comes out NaN in [0, n_b) and zero behind it; its neighbours
+ * are not affected.  The launches are those of the single-length call at n_max, shaped on the host: no allocation, no
+ * synchronisation, no read-back of the lengths, asynchronous on `stream`.
+ * mm_sosfiltfilt_ragged_*: up to 4 sections (more: MM_ERR_UNSUPPORTED before any launch -- filter per distinct length with
+ * mm_sosfiltfilt_f64 then), on the segmented rows: segments anchored at the row's own start (forward) and end (backward),
+ * segments behind the row's extended length exit.  A row alone runs a wave per segment; so does the ragged call, except
+ * from 128 rows on when n_max + 2 padlen <= 16 x 1088, where a workgroup walks each row in ONE round of sixteen segments,
+ * which is the same arithmetic operation for operation (a second round would carry a differently rounded state).
+ * mm_stencil_ragged_f64 reads st->reserved as the shortest row the CALLER takes where that exceeds the operator's own
+ * minimum (filtfilt as a banded operator: 3 n_taps + 1); shorter rows come out NaN.  mm_stencil_f64 ignores the field.
+ * Workspace: mm_sosfiltfilt_ragged_workspace_bytes(rows, n_max) (0 for invalid arguments); MM_ERR_WORKSPACE below it.
+ * MM_ERR_INVALID_ARG as the single-length entries (checked against n_max), and for d_lens == NULL. */
+size_t mm_sosfiltfilt_ragged_workspace_bytes(int64_t rows, int64_t n_max);
+int mm_sosfiltfilt_ragged_f64(const double* d_x, int64_t rows, int64_t n_max, int64_t x_stride, const int64_t* d_lens,
+                              const double* sos, int32_t n_sec, double* d_y, void* d_workspace, size_t ws_bytes,
+                              void* stream);
+int mm_sosfiltfilt_ragged_f32_f64(const float* d_x, int64_t rows, int64_t n_max, int64_t x_stride, const int64_t* d_lens,
+                                  const double* sos, int32_t n_sec, double* d_y, void* d_workspace, size_t ws_bytes,
+                                  void* stream);
+int mm_stencil_ragged_f64(const mm_stencil* st, const double* d_x, int64_t rows, int64_t n_max, int64_t x_stride,
+                          const int64_t* d_lens, double* d_y, void* stream);
+int mm_fir_filtfilt_ragged_f64(const double* d_x, int64_t rows, int64_t n_max, int64_t x_stride, const int64_t* d_lens,
+                               const double* d_h, int32_t n_taps, double* d_y, int64_t y_stride, void* stream);
+int mm_fir_filtfilt_ragged_f32_f64(const float* d_x, int64_t rows, int64_t n_max, int64_t x_stride, const int64_t* d_lens,
+                                   const double* d_h, int32_t n_taps, double* d_y, int64_t y_stride, void* stream);
+int mm_savgol_ragged_f64(const double* d_x, int64_t rows, int64_t n_max, int64_t x_stride, const int64_t* d_lens,
+                         const double* d_c, const double* d_q, const double* d_p, int32_t window, int32_t n_basis,
+                         double* d_y, int64_t y_stride, void* stream);
 
 /* Framewise RMS (row N3): librosa.feature.rms(y, frame_length, hop_length, center, pad_mode=
  * 'constant') as called at script/calc.py:331 / script/mfcc.py:247.  d_audio [batch][audio_stride]

@@ -12,6 +12,8 @@ from .calc import (get_velocity, calculate_amplitude_envelope, velocity_batch, a
                    hilbert_envelope_batch, find_peaks_batch, find_peaks_ex_batch,
                    peaks_to_list, MinMaxFinder)
 from .filters import sosfiltfilt_batch, fir_filtfilt_batch, savgol_batch  # noqa: F401
+from .filters import (sosfiltfilt_ragged_batch, fir_filtfilt_ragged_batch, savgol_ragged_batch,  # noqa: F401
+                      apply_filter_ragged_batch, applyFilter_batch)
 from .audio_io import load_audio, load_wav, resample_batch  # noqa: F401
 from .pitch import pyin_batch, pyin, interp_NAN, interp_nan_batch, get_f0  # noqa: F401
 from .pitch import pyin_ragged_batch, pyin_ragged_frames, interp_nan_ragged_batch, get_f0_batch  # noqa: F401

@@ -94,6 +94,7 @@ class mm_peaks_out(C.Structure):
 
 
 MM_MAX_SEC = 16            # sections per SOS filter (mm_change.hip.inc)
+MM_RAGGED_MAX_SEC = 4      # sections the ragged IIR entries take (the segmented rows; mm_sos_rows.hip.inc)
 
 
 class MMError(RuntimeError):
@@ -152,6 +153,13 @@ PROTOTYPES = {
     "mm_fir_filtfilt_f64": (C.c_int, [_vp, _i64, _i64, _i64, _vp, C.c_int32, _vp, _i64, _vp]),
     "mm_fir_filtfilt_f32_f64": (C.c_int, [_vp, _i64, _i64, _i64, _vp, C.c_int32, _vp, _i64, _vp]),
     "mm_savgol_f64": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _i64, _vp]),
+    "mm_sosfiltfilt_ragged_workspace_bytes": (C.c_size_t, [_i64, _i64]),
+    "mm_sosfiltfilt_ragged_f64": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, C.c_int32, _vp, _vp, C.c_size_t, _vp]),
+    "mm_sosfiltfilt_ragged_f32_f64": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, C.c_int32, _vp, _vp, C.c_size_t, _vp]),
+    "mm_stencil_ragged_f64": (C.c_int, [C.POINTER(mm_stencil), _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "mm_fir_filtfilt_ragged_f64": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, C.c_int32, _vp, _i64, _vp]),
+    "mm_fir_filtfilt_ragged_f32_f64": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, C.c_int32, _vp, _i64, _vp]),
+    "mm_savgol_ragged_f64": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _i64, _vp]),
     "mm_change_workspace_bytes": (C.c_size_t, [_vp, _i64, _i64]),
     "mm_change_workspace_bytes_for": (C.c_size_t, [_vp, _i64, _i64, C.c_int32, _vp, C.c_int32, _vp, C.c_int32]),
     "mm_change_ragged_workspace_bytes_for": (C.c_size_t, [_vp, _i64, _i64, C.c_int32, _vp, C.c_int32, _vp, C.c_int32]),

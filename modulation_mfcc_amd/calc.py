@@ -308,6 +308,41 @@ def velocity_stencil(sr: float, difference: int = 1, method: str = "gradient", w
     raise ValueError("Méthode inconnue. Utilisez 'gradient', 'sg' ou 'finDiff'.")
 
 
+def _c_stencil(st, n_min: int = 0):
+    """The C struct mm_stencil of a stencil dict; ``n_min`` (the ragged entry only) is the shortest row the caller takes."""
+    from . import _lib
+    cs = _lib.mm_stencil()
+    if len(st["off"]) != len(st["c"]):
+        raise ValueError("stencil: one offset per tap")
+    cs.n_c, cs.n_edge, cs.edge_w, cs.reserved = len(st["c"]), st["n_edge"], st["edge_w"], int(n_min)
+    for k, (o, c) in enumerate(zip(st["off"], st["c"])):
+        cs.off[k], cs.c[k] = o, c
+    for i in range(st["n_edge"]):
+        for j in range(st["edge_w"]):
+            cs.el[i][j], cs.er[i][j] = st["el"][i][j], st["er"][i][j]
+    cs.den_c, cs.den_e = st["den_c"], st["den_e"]
+    return cs
+
+
+def apply_stencil_ragged(x2, lens_dev, st, n_min: int = 0):
+    """The banded operator ``st`` once along the last axis of a float64 CUDA(HIP) tensor [rows, n_max] with unit inner
+    stride, a length per row (``lens_dev``: int64 device tensor [rows]; mm_stencil_ragged_f64): row b equals
+    apply_stencil on x2[b:b+1, :n_b] bit for bit in its first n_b columns and is +0.0 behind them; nothing at or behind n_b
+    is read.  A row shorter than the operator takes (or than ``n_min``) comes out NaN."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    rows, n = x2.shape
+    cs = _c_stencil(st, n_min)
+    out = torch.empty((rows, n), dtype=torch.float64, device=x2.device)
+    with torch.cuda.device(x2.device):
+        _lib.check(_lib.load().mm_stencil_ragged_f64(C.byref(cs), x2.data_ptr(), rows, n, x2.stride(0) if rows > 1 else n,
+                                                     lens_dev.data_ptr(), out.data_ptr(),
+                                                     C.c_void_p(torch.cuda.current_stream(x2.device).cuda_stream)),
+                   "mm_stencil_ragged_f64")
+    return out
+
+
 def apply_stencil(x2, st, passes: int = 1):
     """Run the banded operator ``st`` (dict: off, c, den_c, n_edge, edge_w, el, er, den_e -- the fields of the C
     struct mm_stencil) ``passes`` times along the last axis of a float64 CUDA(HIP) tensor [rows, n] with unit
@@ -316,16 +351,7 @@ def apply_stencil(x2, st, passes: int = 1):
     import torch
     from . import _lib
     rows, n = x2.shape
-    cs = _lib.mm_stencil()
-    if len(st["off"]) != len(st["c"]):
-        raise ValueError("stencil: one offset per tap")
-    cs.n_c, cs.n_edge, cs.edge_w = len(st["c"]), st["n_edge"], st["edge_w"]
-    for k, (o, c) in enumerate(zip(st["off"], st["c"])):
-        cs.off[k], cs.c[k] = o, c
-    for i in range(st["n_edge"]):
-        for j in range(st["edge_w"]):
-            cs.el[i][j], cs.er[i][j] = st["el"][i][j], st["er"][i][j]
-    cs.den_c, cs.den_e = st["den_c"], st["den_e"]
+    cs = _c_stencil(st)
     lib = _lib.load()
     stream = C.c_void_p(torch.cuda.current_stream(x2.device).cuda_stream)
     with torch.cuda.device(x2.device):

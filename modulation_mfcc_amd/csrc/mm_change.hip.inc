@@ -432,11 +432,23 @@ static void launch_sos_any(const SosFilt& f, double* ws, int64_t n, int64_t W, h
 // den_c, and for the n_edge first / last outputs a dense row over the first / last edge_w inputs.
 // One thread per output sample; the taps travel in the kernel argument.
 // ------------------------------------------------------------------------------------------
+// RAGGED: a length per row (lens, DEVICE int64 [rows], clamped into [1, n_max]); the right edge rows sit at the row's own
+// end, nothing at or behind it is loaded, the columns behind it become +0.0, and a row too short for the operator NaN.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void stencil_kernel(mm_stencil st, const double* __restrict__ x, int64_t rows,
-                                                      int64_t n, int64_t in_stride, double* __restrict__ y) {
+                                                      int64_t n_max, int64_t in_stride, const int64_t* __restrict__ lens,
+                                                      double* __restrict__ y) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= rows * n) return;
-  const int64_t r = idx / n, i = idx - r * n;
+  if (idx >= rows * n_max) return;
+  const int64_t r = idx / n_max, i = idx - r * n_max;
+  int64_t n = n_max;
+  if constexpr (RAGGED) {
+    const int64_t nb = lens[r];
+    n = nb < 1 ? 1 : (nb > n_max ? n_max : nb);
+    if (i >= n) { y[idx] = 0.0; return; }
+    // (st.reserved: the caller's own minimum, e.g. filtfilt's 3 n_taps + 1, where it exceeds the operator's)
+    if (n < 2 * (int64_t)st.n_edge || n < st.edge_w || n < st.reserved) { y[idx] = __builtin_nan(""); return; }
+  }
   const double* xr = x + r * in_stride;
   double acc = 0.0, den;
   if (i < st.n_edge) {
@@ -450,5 +462,5 @@ __global__ __launch_bounds__(256) void stencil_kernel(mm_stencil st, const doubl
     for (int k = 0; k < st.n_c; ++k) acc = fma(st.c[k], xr[i + st.off[k]], acc);
     den = st.den_c;
   }
-  y[r * n + i] = acc / den;
+  y[idx] = acc / den;
 }

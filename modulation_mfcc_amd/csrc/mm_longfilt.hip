@@ -48,16 +48,43 @@ __device__ __forceinline__ double lf_sample(const T* __restrict__ xr, int64_t n,
   return 0.0;
 }
 
-template <typename T, bool EXT>
+// RAGGED: a length per row (lens, DEVICE int64 [rows], clamped into [1, n]); n and i_hi are then those of the longest row,
+// which shape the grid, and a row's own outputs end n - i_hi before ITS end, as the longest row's do.  Outputs of the
+// tile at or behind the row's length become +0.0 (a tile without any output of the row's stages nothing), those of a row
+// shorter than n_min -- one scipy refuses -- NaN before its length; the outputs between the row's last one and its length
+// (the Savitzky-Golay edge) are sg_edge_kernel's.  Nothing at or behind the row's length is loaded: the staging reads
+// through lf_sample with the row's own length.  The tiles start at the row's start and the chunks do not depend on the
+// length: an output is summed in the order the row alone gives it.
+template <typename T, bool EXT, bool RAGGED>
 __global__ __launch_bounds__(kLfThreads) void longcorr_kernel(const T* __restrict__ x, int64_t n, int64_t x_stride,
                                                               const double* __restrict__ h, int32_t n_taps, int64_t off0,
                                                               int64_t i_lo, int64_t i_hi, int32_t tiles,
-                                                              double* __restrict__ y, int64_t y_stride) {
+                                                              double* __restrict__ y, int64_t y_stride,
+                                                              const int64_t* __restrict__ lens, int64_t n_min) {
   __shared__ double s[kLfSlots];
   const int64_t row = blockIdx.x / tiles, tile = blockIdx.x % tiles;
   const T* xr = x + row * x_stride;
   const int64_t i0 = i_lo + tile * kLfTile;             // first output of the tile
   const int lane = threadIdx.x;
+  const int64_t i_end = i_hi;                           // RAGGED: where the zeros behind a shorter row end
+  if constexpr (RAGGED) {
+    const int64_t nb = lens[row], back = n - i_hi;
+    n = nb < 1 ? 1 : (nb > n ? n : nb);                 // the row's own length from here on (uniform over the workgroup)
+    i_hi = n - back;
+    const bool bad = n < n_min;
+    if (bad || i0 >= i_hi) {                            // no output of the row's in this tile: before any barrier
+      double* yr = y + row * y_stride;
+      const int64_t i = i0 + (int64_t)kLfPer * lane;
+#pragma unroll
+      for (int j = 0; j < kLfPer; ++j) {
+        if (i + j < i_end) {
+          if (i + j >= n) yr[i + j] = 0.0;
+          else if (bad) yr[i + j] = __builtin_nan("");
+        }
+      }
+      return;
+    }
+  }
   const double* sp = s + (kLfPer + 1) * lane;           // slot of sample kLfPer * lane
   double total[kLfPer];
 #pragma unroll
@@ -107,18 +134,39 @@ __global__ __launch_bounds__(kLfThreads) void longcorr_kernel(const T* __restric
   double* yr = y + row * y_stride;
   const int64_t i = i0 + (int64_t)kLfPer * lane;
 #pragma unroll
-  for (int j = 0; j < kLfPer; ++j)
+  for (int j = 0; j < kLfPer; ++j) {
     if (i + j < i_hi) yr[i + j] = total[j];
+    else if constexpr (RAGGED) {
+      if (i + j >= n && i + j < i_end) yr[i + j] = 0.0;
+    }
+  }
 }
 
 // block = (row, side): side 0 the first W / 2 outputs from x[0 .. W), side 1 the last W / 2 from x[n - W .. n)
+// RAGGED: side 1 fits x[n_b - W .. n_b) of the row's own length n_b and writes the W / 2 outputs before it, then the zeros
+// that longcorr_kernel's range [W / 2, n - W / 2) leaves: [max(n_b, n - W / 2), n).  A row with n_b < W (scipy refuses it)
+// gets NaN before n_b and zeros behind it in the same two stretches, [0, W / 2) and [n - W / 2, n), and loads nothing.
+template <bool RAGGED>
 __global__ __launch_bounds__(kLfThreads) void sg_edge_kernel(const double* __restrict__ x, int64_t n, int64_t x_stride,
                                                              const double* __restrict__ q_tab, const double* __restrict__ p_tab,
-                                                             int32_t W, int32_t p1, double* __restrict__ y, int64_t y_stride) {
+                                                             int32_t W, int32_t p1, double* __restrict__ y, int64_t y_stride,
+                                                             const int64_t* __restrict__ lens) {
   __shared__ double s_a[kSgQ];
   const int64_t row = blockIdx.x >> 1;
   const int side = blockIdx.x & 1;
   const int half = W / 2;
+  if constexpr (RAGGED) {
+    const int64_t nb = lens[row], n_max = n;
+    n = nb < 1 ? 1 : (nb > n_max ? n_max : nb);         // the row's own length from here on (uniform over the workgroup)
+    double* yr = y + row * y_stride;
+    if (n < W) {                                        // before any barrier
+      const int64_t lo = side ? (n_max - half > half ? n_max - half : half) : 0, hi = side ? n_max : half;
+      for (int64_t i = lo + threadIdx.x; i < hi; i += kLfThreads) yr[i] = i < n ? __builtin_nan("") : 0.0;
+      return;
+    }
+    if (side)
+      for (int64_t i = (n > n_max - half ? n : n_max - half) + threadIdx.x; i < n_max; i += kLfThreads) yr[i] = 0.0;
+  }
   const double* xw = x + row * x_stride + (side ? n - W : 0);
   double* yo = y + row * y_stride + (side ? n - half : 0);
   const double* ps = p_tab + (int64_t)side * half * p1;
@@ -151,36 +199,29 @@ int64_t lf_tiles(int64_t rows, int64_t outputs) {
   return tiles > 0x7fffffff || rows * tiles > 0x7fffffff ? 0 : tiles;
 }
 
+// d_lens (DEVICE int64 [rows], or null): the ragged form, n the longest row's length
 template <typename T>
-int lf_fir_filtfilt(const T* d_x, int64_t rows, int64_t n, int64_t x_stride, const double* d_h, int32_t n_taps, double* d_y,
-                    int64_t y_stride, void* stream) {
+int lf_fir_filtfilt(const T* d_x, int64_t rows, int64_t n, int64_t x_stride, const int64_t* d_lens, const double* d_h,
+                    int32_t n_taps, double* d_y, int64_t y_stride, void* stream) {
   if (!d_x || !d_h || !d_y || rows < 1 || rows > 0x7fffffff || n_taps < 2 || n_taps > (1 << 29) || n <= 3 * (int64_t)n_taps ||
       x_stride < n || y_stride < n)
     return MM_ERR_INVALID_ARG;
   const int64_t tiles = lf_tiles(rows, n);
   if (!tiles) return MM_ERR_INVALID_ARG;
-  hipLaunchKernelGGL((longcorr_kernel<T, true>), dim3((unsigned)(rows * tiles)), dim3(kLfThreads), 0, (hipStream_t)stream,
-                     d_x, n, x_stride, d_h, 2 * n_taps - 1, -(int64_t)(n_taps - 1), (int64_t)0, n, (int32_t)tiles, d_y, y_stride);
+  if (d_lens)
+    hipLaunchKernelGGL((longcorr_kernel<T, true, true>), dim3((unsigned)(rows * tiles)), dim3(kLfThreads), 0, (hipStream_t)stream,
+                       d_x, n, x_stride, d_h, 2 * n_taps - 1, -(int64_t)(n_taps - 1), (int64_t)0, n, (int32_t)tiles, d_y, y_stride,
+                       d_lens, 3 * (int64_t)n_taps + 1);
+  else
+    hipLaunchKernelGGL((longcorr_kernel<T, true, false>), dim3((unsigned)(rows * tiles)), dim3(kLfThreads), 0, (hipStream_t)stream,
+                       d_x, n, x_stride, d_h, 2 * n_taps - 1, -(int64_t)(n_taps - 1), (int64_t)0, n, (int32_t)tiles, d_y, y_stride,
+                       d_lens, (int64_t)0);
   HIP_TRY(hipGetLastError());
   return MM_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int mm_fir_filtfilt_f64(const double* d_x, int64_t rows, int64_t n, int64_t x_stride, const double* d_h, int32_t n_taps,
-                        double* d_y, int64_t y_stride, void* stream) {
-  return lf_fir_filtfilt(d_x, rows, n, x_stride, d_h, n_taps, d_y, y_stride, stream);
-}
-
-int mm_fir_filtfilt_f32_f64(const float* d_x, int64_t rows, int64_t n, int64_t x_stride, const double* d_h, int32_t n_taps,
-                            double* d_y, int64_t y_stride, void* stream) {
-  return lf_fir_filtfilt(d_x, rows, n, x_stride, d_h, n_taps, d_y, y_stride, stream);
-}
-
-int mm_savgol_f64(const double* d_x, int64_t rows, int64_t n, int64_t x_stride, const double* d_c, const double* d_q,
-                  const double* d_p, int32_t window, int32_t n_basis, double* d_y, int64_t y_stride, void* stream) {
+int lf_savgol(const double* d_x, int64_t rows, int64_t n, int64_t x_stride, const int64_t* d_lens, const double* d_c,
+              const double* d_q, const double* d_p, int32_t window, int32_t n_basis, double* d_y, int64_t y_stride, void* stream) {
   if (!d_x || !d_c || !d_y || rows < 1 || rows > 0x3fffffff || window < 1 || window > n || n_basis < 1 || n_basis > window ||
       x_stride < n || y_stride < n)
     return MM_ERR_INVALID_ARG;
@@ -191,16 +232,64 @@ int mm_savgol_f64(const double* d_x, int64_t rows, int64_t n, int64_t x_stride, 
   if (i_hi > i_lo) {
     const int64_t tiles = lf_tiles(rows, i_hi - i_lo);
     if (!tiles) return MM_ERR_INVALID_ARG;
-    hipLaunchKernelGGL((longcorr_kernel<double, false>), dim3((unsigned)(rows * tiles)), dim3(kLfThreads), 0, st, d_x, n,
-                       x_stride, d_c, window, -(int64_t)((window - 1) / 2), i_lo, i_hi, (int32_t)tiles, d_y, y_stride);
+    if (d_lens)
+      hipLaunchKernelGGL((longcorr_kernel<double, false, true>), dim3((unsigned)(rows * tiles)), dim3(kLfThreads), 0, st, d_x, n,
+                         x_stride, d_c, window, -(int64_t)((window - 1) / 2), i_lo, i_hi, (int32_t)tiles, d_y, y_stride, d_lens,
+                         (int64_t)window);
+    else
+      hipLaunchKernelGGL((longcorr_kernel<double, false, false>), dim3((unsigned)(rows * tiles)), dim3(kLfThreads), 0, st, d_x, n,
+                         x_stride, d_c, window, -(int64_t)((window - 1) / 2), i_lo, i_hi, (int32_t)tiles, d_y, y_stride, d_lens,
+                         (int64_t)0);
     HIP_TRY(hipGetLastError());
   }
   if (half > 0) {
-    hipLaunchKernelGGL(sg_edge_kernel, dim3((unsigned)(2 * rows)), dim3(kLfThreads), 0, st, d_x, n, x_stride, d_q, d_p,
-                       window, n_basis, d_y, y_stride);
+    if (d_lens)
+      hipLaunchKernelGGL(sg_edge_kernel<true>, dim3((unsigned)(2 * rows)), dim3(kLfThreads), 0, st, d_x, n, x_stride, d_q, d_p,
+                         window, n_basis, d_y, y_stride, d_lens);
+    else
+      hipLaunchKernelGGL(sg_edge_kernel<false>, dim3((unsigned)(2 * rows)), dim3(kLfThreads), 0, st, d_x, n, x_stride, d_q, d_p,
+                         window, n_basis, d_y, y_stride, d_lens);
     HIP_TRY(hipGetLastError());
   }
   return MM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mm_fir_filtfilt_f64(const double* d_x, int64_t rows, int64_t n, int64_t x_stride, const double* d_h, int32_t n_taps,
+                        double* d_y, int64_t y_stride, void* stream) {
+  return lf_fir_filtfilt(d_x, rows, n, x_stride, nullptr, d_h, n_taps, d_y, y_stride, stream);
+}
+
+int mm_fir_filtfilt_f32_f64(const float* d_x, int64_t rows, int64_t n, int64_t x_stride, const double* d_h, int32_t n_taps,
+                            double* d_y, int64_t y_stride, void* stream) {
+  return lf_fir_filtfilt(d_x, rows, n, x_stride, nullptr, d_h, n_taps, d_y, y_stride, stream);
+}
+
+int mm_fir_filtfilt_ragged_f64(const double* d_x, int64_t rows, int64_t n_max, int64_t x_stride, const int64_t* d_lens,
+                               const double* d_h, int32_t n_taps, double* d_y, int64_t y_stride, void* stream) {
+  if (!d_lens) return MM_ERR_INVALID_ARG;
+  return lf_fir_filtfilt(d_x, rows, n_max, x_stride, d_lens, d_h, n_taps, d_y, y_stride, stream);
+}
+
+int mm_fir_filtfilt_ragged_f32_f64(const float* d_x, int64_t rows, int64_t n_max, int64_t x_stride, const int64_t* d_lens,
+                                   const double* d_h, int32_t n_taps, double* d_y, int64_t y_stride, void* stream) {
+  if (!d_lens) return MM_ERR_INVALID_ARG;
+  return lf_fir_filtfilt(d_x, rows, n_max, x_stride, d_lens, d_h, n_taps, d_y, y_stride, stream);
+}
+
+int mm_savgol_f64(const double* d_x, int64_t rows, int64_t n, int64_t x_stride, const double* d_c, const double* d_q,
+                  const double* d_p, int32_t window, int32_t n_basis, double* d_y, int64_t y_stride, void* stream) {
+  return lf_savgol(d_x, rows, n, x_stride, nullptr, d_c, d_q, d_p, window, n_basis, d_y, y_stride, stream);
+}
+
+int mm_savgol_ragged_f64(const double* d_x, int64_t rows, int64_t n_max, int64_t x_stride, const int64_t* d_lens,
+                         const double* d_c, const double* d_q, const double* d_p, int32_t window, int32_t n_basis, double* d_y,
+                         int64_t y_stride, void* stream) {
+  if (!d_lens) return MM_ERR_INVALID_ARG;
+  return lf_savgol(d_x, rows, n_max, x_stride, d_lens, d_c, d_q, d_p, window, n_basis, d_y, y_stride, stream);
 }
 
 }  // extern "C"

@@ -21,12 +21,19 @@
 // The forward direction reads x with scipy's odd extension formed on the fly and writes the padded row-major workspace;
 // the reverse direction reads that and writes y without the padding.  Traffic: 3 x 8 bytes per sample and direction.
 // Differs from scipy's sequential recursion by rounding only (the Phi products), like the other time-parallel forms.
-#define MM_SEG_CH 17              // samples per chunk (odd: the chunks of a segment start in different LDS banks)
+//
+// RG (mm_sosfiltfilt_ragged_*): a length per row.  SegSource reads the row's n_b once per wave and works on the row's own
+// n_ext_b = n_b + 2 pad and segment count: forward segments are anchored at the row's start, backward ones at its own end,
+// waves behind the row's segments exit (wave-uniform; these kernels have no workgroup barrier), and the backward pass's
+// waves share the +0.0 of the columns behind n_b.  The segments, the lanes and the scans are those of the row filtered
+// alone, so the result is too, bit for bit; a row scipy refuses (n_b <= pad) is not loaded at all and comes out NaN.
+// RG = false compiles to the single-length kernels as they were.
+#define MM_SEG_CH 17             // samples per chunk (odd: the chunks of a segment start in different LDS banks)
 #define MM_SEG_LEN (64 * MM_SEG_CH)
 #define MM_SEG_WAVES 4            // segments per workgroup (8.7 KB of LDS each)
 #define MM_SEG_JT 13              // powers Phi^(2^j), j < 13: 6 for the chunks of a segment, 6 for 64 segments, 1 carry
 
-template <int NS>
+template <int NS, bool RG>
 struct SegArgs {
   SosCoef<NS> f;
   const double* tab;             // W [MM_SEG_CH][2 NS] | P [MM_SEG_JT][packed lower block triangle, by columns]
@@ -43,23 +50,33 @@ struct SegArgs {
   double* seg_Z;                 // [rows][n_seg][2 NS]
   int64_t rows, n, n_ext;        // n_ext = n + 2 pad
   int n_seg, pad, reverse;
+  const int64_t* lens;           // ragged (not null): a length per row, DEVICE int64 [rows]; n, n_ext and n_seg are then
+                                 //     those of the longest row the launch is shaped for, y is [rows][n]
 };
 
 // sample p (pass order) of the extended row -- forward: scipy's odd extension of x; reverse: the workspace from its end
-template <int NS>
+template <int NS, bool RG>
 struct SegSource {
   const double* base;
   const float* basef;            // float32 source (forward pass of the change tail), else null
   double e0, e1;                 // x[0], x[n - 1] (forward)
-  int64_t n, n_ext;
+  int64_t n, n_ext;              // the row's own length and extended length
   int pad, reverse;
-  __device__ __forceinline__ SegSource(const SegArgs<NS>& a, int64_t row) {
-    n = a.n; n_ext = a.n_ext; pad = a.pad; reverse = a.reverse; basef = nullptr; base = nullptr;
+  int n_seg;                     // segments of the row; 0: a ragged row scipy refuses (n <= pad), nothing of it is loaded
+  __device__ __forceinline__ SegSource(const SegArgs<NS, RG>& a, int64_t row) {
+    n = a.n; n_ext = a.n_ext; n_seg = a.n_seg;
+    pad = a.pad; reverse = a.reverse; basef = nullptr; base = nullptr;
+    if constexpr (RG) {          // the row's own length, clamped: one scalar load per wave (the row is wave-uniform)
+      const int64_t nb = a.lens[row];
+      n = nb < 1 ? 1 : (nb > a.n ? a.n : nb);
+      n_ext = n + 2 * (int64_t)pad;
+      n_seg = n > pad ? (int)((n_ext + MM_SEG_LEN - 1) / MM_SEG_LEN) : 0;
+    }
     if (reverse) { base = a.ws + row * a.ws_stride; e0 = e1 = 0.0; }
     else if (a.xf) {
       if (a.n_mfcc > 0) {
         const int64_t clip = row / a.n_rows;
-        basef = a.xf + ((clip * a.n_mfcc + a.first_row + (row - clip * a.n_rows)) * n);
+        basef = a.xf + ((clip * a.n_mfcc + a.first_row + (row - clip * a.n_rows)) * a.n);
       } else basef = a.xf + row * a.x_stride;
       e0 = (double)basef[0]; e1 = (double)basef[n - 1];
     } else { base = a.x + row * a.x_stride; e0 = base[0]; e1 = base[n - 1]; }
@@ -85,8 +102,8 @@ struct SegSource {
   }
 };
 
-template <int NS>
-__device__ __forceinline__ void seg_load(const SegSource<NS>& src, int64_t p0, double* slab, int lane) {
+template <int NS, bool RG>
+__device__ __forceinline__ void seg_load(const SegSource<NS, RG>& src, int64_t p0, double* slab, int lane) {
   double v[MM_SEG_CH];
   // a segment that touches neither the extension nor the row's end (all but two or three per row): one address per
   // lane, the 17 loads at immediate offsets
@@ -121,8 +138,8 @@ __device__ __forceinline__ void seg_load(const SegSource<NS>& src, int64_t p0, d
 
 // seg_load in two halves for sos_row_stream_kernel: the loads of a segment issued into registers a round ahead
 // (seg_fetch: only a segment that touches neither the extension nor the row's end), the slab written when its turn comes
-template <int NS>
-__device__ __forceinline__ bool seg_fetch(const SegSource<NS>& src, int64_t p0, int lane, double (&v)[MM_SEG_CH]) {
+template <int NS, bool RG>
+__device__ __forceinline__ bool seg_fetch(const SegSource<NS, RG>& src, int64_t p0, int lane, double (&v)[MM_SEG_CH]) {
   const bool inner = src.reverse ? p0 + MM_SEG_LEN <= src.n_ext : (p0 >= src.pad && p0 + MM_SEG_LEN <= src.pad + src.n);
   if (!inner) return false;
   if (src.reverse) {
@@ -141,8 +158,8 @@ __device__ __forceinline__ bool seg_fetch(const SegSource<NS>& src, int64_t p0, 
   return true;
 }
 
-template <int NS>
-__device__ __forceinline__ void seg_put(const SegSource<NS>& src, int64_t p0, double* slab, int lane, const double (&v)[MM_SEG_CH],
+template <int NS, bool RG>
+__device__ __forceinline__ void seg_put(const SegSource<NS, RG>& src, int64_t p0, double* slab, int lane, const double (&v)[MM_SEG_CH],
                                         bool fetched) {
   if (fetched && src.reverse) {
 #pragma unroll
@@ -212,8 +229,8 @@ __device__ __forceinline__ void seg_matvec(double (&Z)[2 * NS], const MM_CONST d
   for (int a = 0; a < S2; ++a) Z[a] = o[a];
 }
 
-template <int NS>
-__global__ __launch_bounds__(64 * MM_SEG_WAVES) void sos_seg_state_kernel(SegArgs<NS> a) {
+template <int NS, bool RG>
+__global__ __launch_bounds__(64 * MM_SEG_WAVES) void sos_seg_state_kernel(SegArgs<NS, RG> a) {
   extern __shared__ double seg_lds[];
   constexpr int S2 = 2 * NS;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -225,8 +242,9 @@ __global__ __launch_bounds__(64 * MM_SEG_WAVES) void sos_seg_state_kernel(SegArg
   double* slab = seg_lds + wave * MM_SEG_LEN;
   const MM_CONST double* W = (const MM_CONST double*)a.tab;
   const MM_CONST double* P = W + MM_SEG_CH * S2;
-  const SegSource<NS> src(a, row);
-  seg_load<NS>(src, (int64_t)seg * MM_SEG_LEN, slab, lane);
+  const SegSource<NS, RG> src(a, row);
+  if (RG && seg >= src.n_seg - 1) return;                  // ragged: behind the row's own segments (wave-uniform)
+  seg_load<NS, RG>(src, (int64_t)seg * MM_SEG_LEN, slab, lane);
   wave_lds_sync();
   double Z[S2];
   seg_weighted_sum<NS>(slab + lane * MM_SEG_CH, W, Z);
@@ -238,14 +256,16 @@ __global__ __launch_bounds__(64 * MM_SEG_WAVES) void sos_seg_state_kernel(SegArg
   }
 }
 
-template <int NS>
-__global__ __launch_bounds__(64 * MM_SEG_WAVES) void sos_seg_scan_kernel(SegArgs<NS> a) {
+template <int NS, bool RG>
+__global__ __launch_bounds__(64 * MM_SEG_WAVES) void sos_seg_scan_kernel(SegArgs<NS, RG> a) {
   constexpr int S2 = 2 * NS, TRI = 2 * NS * (NS + 1);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * MM_SEG_WAVES + wave;
   if (row >= a.rows) return;
   const MM_CONST double* P = (const MM_CONST double*)a.tab + MM_SEG_CH * S2;
-  const SegSource<NS> src(a, row);
+  const SegSource<NS, RG> src(a, row);
+  const int n_seg = src.n_seg;                             // the row's own (ragged: at most a.n_seg, which strides S and Z)
+  if (RG && n_seg <= 1) return;                            // ragged: one segment starts from zi * first sample, as a row alone
   const double x0 = src.at(0);
   double carry[S2];                                        // start state of segment `base`
 #pragma unroll
@@ -253,19 +273,19 @@ __global__ __launch_bounds__(64 * MM_SEG_WAVES) void sos_seg_scan_kernel(SegArgs
   const double* S = a.seg_S + row * a.n_seg * S2;
   double* Zo = a.seg_Z + row * a.n_seg * S2;
 #pragma unroll 1
-  for (int base = 0; base < a.n_seg; base += 64) {
+  for (int base = 0; base < n_seg; base += 64) {
     const int s = base + lane;
     // u(0) = carry, u(i) = S(base + i - 1)
     double Z[S2];
-    const bool have = lane > 0 && s - 1 < a.n_seg - 1;
+    const bool have = lane > 0 && s - 1 < n_seg - 1;
 #pragma unroll
     for (int c = 0; c < S2; ++c) Z[c] = lane == 0 ? carry[c] : (have ? S[(int64_t)(s - 1) * S2 + c] : 0.0);
     seg_scan<NS>(Z, P, 6, lane);
-    if (s < a.n_seg) {
+    if (s < n_seg) {
 #pragma unroll
       for (int c = 0; c < S2; ++c) Zo[(int64_t)s * S2 + c] = Z[c];
     }
-    if (base + 64 < a.n_seg) {                             // next round: Z(base + 64) = Phi^64 Z(base + 63) + S(base + 63)
+    if (base + 64 < n_seg) {                               // next round: Z(base + 64) = Phi^64 Z(base + 63) + S(base + 63)
       double nx[S2];
 #pragma unroll
       for (int c = 0; c < S2; ++c) nx[c] = Z[c];
@@ -280,33 +300,48 @@ __global__ __launch_bounds__(64 * MM_SEG_WAVES) void sos_seg_scan_kernel(SegArgs
 }
 
 // the filtered segment, slab -> global memory along time: forward -> the padded workspace; reverse -> y without the padding
-template <int NS>
-__device__ __forceinline__ void seg_store(const SegArgs<NS>& a, int64_t row, int64_t p0, const double* slab, int lane) {
-  if (!a.reverse && p0 + MM_SEG_LEN <= a.n_ext) {
+template <int NS, bool RG>
+__device__ __forceinline__ void seg_store(const SegArgs<NS, RG>& a, const SegSource<NS, RG>& src, int64_t row, int64_t p0,
+                                          const double* slab, int lane) {
+  const int64_t n = RG ? src.n : a.n, n_ext = RG ? src.n_ext : a.n_ext;      // the row's own (y rows are a.n apart)
+  if (!a.reverse && p0 + MM_SEG_LEN <= n_ext) {
     double* o = a.ws + row * a.ws_stride + p0 + lane;
 #pragma unroll
     for (int m = 0; m < MM_SEG_CH; ++m) o[64 * m] = slab[lane + 64 * m];
-  } else if (a.reverse && a.n_ext - 1 - a.pad - p0 < a.n && a.n_ext - a.pad - p0 - MM_SEG_LEN >= 0) {
-    double* o = a.y + row * a.n + (a.n_ext - a.pad - p0 - MM_SEG_LEN + lane);        // ascending addresses over ascending lanes
+  } else if (a.reverse && n_ext - 1 - a.pad - p0 < n && n_ext - a.pad - p0 - MM_SEG_LEN >= 0) {
+    double* o = a.y + row * a.n + (n_ext - a.pad - p0 - MM_SEG_LEN + lane);          // ascending addresses over ascending lanes
 #pragma unroll
     for (int m = 0; m < MM_SEG_CH; ++m) o[64 * m] = slab[MM_SEG_LEN - 1 - lane - 64 * m];
   } else
 #pragma unroll
   for (int m = 0; m < MM_SEG_CH; ++m) {
     const int64_t p = p0 + lane + 64 * m;
-    if (p < a.n_ext) {
+    if (p < n_ext) {
       const double v = slab[lane + 64 * m];
       if (!a.reverse) a.ws[row * a.ws_stride + p] = v;
       else {
-        const int64_t t = a.n_ext - 1 - p - a.pad;
-        if (t >= 0 && t < a.n) a.y[row * a.n + t] = v;
+        const int64_t t = n_ext - 1 - p - a.pad;
+        if (t >= 0 && t < n) a.y[row * a.n + t] = v;
       }
     }
   }
 }
 
-template <int NS>
-__global__ __launch_bounds__(64 * MM_SEG_WAVES) void sos_seg_apply_kernel(SegArgs<NS> a) {
+// ragged, reverse pass: columns [first, first + count) of y's row that lie at or behind the row's own length become +0.0,
+// and NaN before it where scipy refuses the row (n <= pad: nothing of the row was loaded or filtered)
+template <int NS, bool RG>
+__device__ __forceinline__ void seg_fill(const SegArgs<NS, RG>& a, const SegSource<NS, RG>& src, int64_t row, int64_t first,
+                                         int64_t count, int lane, int stride) {
+  double* yr = a.y + row * a.n;
+  const int64_t end = first + count < a.n ? first + count : a.n;
+  for (int64_t j = first + lane; j < end; j += stride) {
+    if (j >= src.n) yr[j] = 0.0;
+    else if (src.n_seg == 0) yr[j] = __builtin_nan("");
+  }
+}
+
+template <int NS, bool RG>
+__global__ __launch_bounds__(64 * MM_SEG_WAVES) void sos_seg_apply_kernel(SegArgs<NS, RG> a) {
   extern __shared__ double seg_lds[];
   constexpr int S2 = 2 * NS;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -317,9 +352,12 @@ __global__ __launch_bounds__(64 * MM_SEG_WAVES) void sos_seg_apply_kernel(SegArg
   double* slab = seg_lds + wave * MM_SEG_LEN;
   const MM_CONST double* W = (const MM_CONST double*)a.tab;
   const MM_CONST double* P = W + MM_SEG_CH * S2;
-  const SegSource<NS> src(a, row);
+  const SegSource<NS, RG> src(a, row);
   const int64_t p0 = (int64_t)seg * MM_SEG_LEN;
-  seg_load<NS>(src, p0, slab, lane);
+  // ragged, reverse pass: the launch's segments share the zeros (and NaN) of the row between them, MM_SEG_LEN columns each
+  if (RG && a.reverse) seg_fill<NS, RG>(a, src, row, p0, MM_SEG_LEN, lane, 64);
+  if (RG && seg >= src.n_seg) return;                      // ragged: behind the row's own segments (wave-uniform)
+  seg_load<NS, RG>(src, p0, slab, lane);
   wave_lds_sync();
   double* q = slab + lane * MM_SEG_CH;
   double Z[S2];
@@ -327,7 +365,7 @@ __global__ __launch_bounds__(64 * MM_SEG_WAVES) void sos_seg_apply_kernel(SegArg
   // u(0) = the segment's start state, u(k) = S(k - 1)
   {
     double z0[S2];
-    if (a.n_seg == 1) {
+    if (src.n_seg == 1) {
       const double x0 = slab[0];
 #pragma unroll
       for (int s = 0; s < NS; ++s) { z0[2 * s] = a.f.zi[s][0] * x0; z0[2 * s + 1] = a.f.zi[s][1] * x0; }
@@ -356,7 +394,7 @@ __global__ __launch_bounds__(64 * MM_SEG_WAVES) void sos_seg_apply_kernel(SegArg
     for (int i = 0; i < MM_SEG_CH; ++i) q[i] = v[i];
   }
   wave_lds_sync();
-  seg_store<NS>(a, row, p0, slab, lane);
+  seg_store<NS, RG>(a, src, row, p0, slab, lane);
 }
 
 // A ROW PER WORKGROUP (batches of at least MM_ROW_MIN rows): the three launches above read every sample twice per
@@ -369,8 +407,8 @@ __global__ __launch_bounds__(64 * MM_SEG_WAVES) void sos_seg_apply_kernel(SegArg
 // next round's samples are loaded while this one computes.
 #define MM_ROW_WAVES 16
 #define MM_ROW_MIN 128
-template <int NS>
-__global__ __launch_bounds__(64 * MM_ROW_WAVES) void sos_row_stream_kernel(SegArgs<NS> a) {
+template <int NS, bool RG>
+__global__ __launch_bounds__(64 * MM_ROW_WAVES) void sos_row_stream_kernel(SegArgs<NS, RG> a) {
   extern __shared__ double seg_lds[];
   __shared__ double segS[2][MM_ROW_WAVES][2 * MM_CLIP_NS];
   __shared__ double segZ[MM_ROW_WAVES][2 * MM_CLIP_NS];
@@ -381,27 +419,30 @@ __global__ __launch_bounds__(64 * MM_ROW_WAVES) void sos_row_stream_kernel(SegAr
   double* q = slab + lane * MM_SEG_CH;
   const MM_CONST double* W = (const MM_CONST double*)a.tab;
   const MM_CONST double* P = W + MM_SEG_CH * S2;
-  const SegSource<NS> src(a, row);
+  const SegSource<NS, RG> src(a, row);
+  const int n_seg = src.n_seg;                             // the row's own: uniform over the workgroup, like every barrier below
   __shared__ double carry[2 * MM_CLIP_NS];                 // start state of segment `base` (wave 0 reads and writes it)
-  if (threadIdx.x == 0) {
+  if (threadIdx.x == 0 && (!RG || n_seg > 0)) {
     const double x0 = src.at(0);
 #pragma unroll
     for (int s = 0; s < NS; ++s) { carry[2 * s] = a.f.zi[s][0] * x0; carry[2 * s + 1] = a.f.zi[s][1] * x0; }
   }
+  // ragged, reverse pass: the zeros (and NaN) of the row, shared among the workgroup's threads
+  if (RG && a.reverse) seg_fill<NS, RG>(a, src, row, 0, a.n, threadIdx.x, 64 * MM_ROW_WAVES);
   double v[MM_SEG_CH];
-  bool fetched = wave < a.n_seg ? seg_fetch<NS>(src, (int64_t)wave * MM_SEG_LEN, lane, v) : false;
+  bool fetched = wave < n_seg ? seg_fetch<NS, RG>(src, (int64_t)wave * MM_SEG_LEN, lane, v) : false;
   MM_STAMP_BEGIN(10)
 #pragma unroll 1
-  for (int base = 0, r = 0; base < a.n_seg; base += MM_ROW_WAVES, ++r) {
+  for (int base = 0, r = 0; base < n_seg; base += MM_ROW_WAVES, ++r) {
     const int seg = base + wave;
-    const bool live = seg < a.n_seg;                       // wave-uniform
+    const bool live = seg < n_seg;                         // wave-uniform
     const int64_t p0 = (int64_t)seg * MM_SEG_LEN;
     double S[S2];
     if (live) {
-      seg_put<NS>(src, p0, slab, lane, v, fetched);
+      seg_put<NS, RG>(src, p0, slab, lane, v, fetched);
       wave_lds_sync();
       MM_STAMP_AT(0)
-      if (seg + MM_ROW_WAVES < a.n_seg) fetched = seg_fetch<NS>(src, p0 + (int64_t)MM_ROW_WAVES * MM_SEG_LEN, lane, v);
+      if (seg + MM_ROW_WAVES < n_seg) fetched = seg_fetch<NS, RG>(src, p0 + (int64_t)MM_ROW_WAVES * MM_SEG_LEN, lane, v);
       seg_weighted_sum<NS>(q, W, S);
       MM_STAMP_AT(1)
       double V[S2];
@@ -459,14 +500,13 @@ __global__ __launch_bounds__(64 * MM_ROW_WAVES) void sos_row_stream_kernel(SegAr
       }
       wave_lds_sync();
       MM_STAMP_AT(7)
-      seg_store<NS>(a, row, p0, slab, lane);
+      seg_store<NS, RG>(a, src, row, p0, slab, lane);
       wave_lds_sync();                                     // (the stores have read the slab before the next round's put)
       MM_STAMP_AT(8)
     }
   }
   MM_STAMP_END_BLK(10, gridDim.x - 1)
 }
-
 // ---- host side ----
 template <int NS>
 static void seg_tables(const SosCoef<NS>& c, std::vector<double>& tab) {
@@ -488,11 +528,12 @@ struct SegSrc {                  // where the forward pass reads: float64 rows, 
   const float* xf; int n_mfcc, first_row, n_rows;
 };
 
-template <int NS>
+// lens (DEVICE int64 [rows], or null): the ragged form -- n is then the longest row's length, which shapes every launch
+template <int NS, bool RG>
 static int launch_sos_rows(const SosFilt& f, const SegSrc& src, int64_t rows, int64_t n, double* d_y, double* ws,
-                           hipStream_t st) {
+                           hipStream_t st, const int64_t* lens) {
   constexpr int S2 = 2 * NS;
-  SegArgs<NS> a;
+  SegArgs<NS, RG> a;
   sos_coef_of<NS>(f, &a.f);
   std::vector<double> tab;
   seg_tables<NS>(a.f, tab);
@@ -507,7 +548,7 @@ static int launch_sos_rows(const SosFilt& f, const SegSrc& src, int64_t rows, in
   a.ws = ws + 1024 + 2 * rows * nseg * 2 * MM_CLIP_NS;
   a.ws_stride = seg_ws_stride(a.n_ext);
   a.x = src.x; a.x_stride = src.x_stride; a.xf = src.xf; a.n_mfcc = src.n_mfcc; a.first_row = src.first_row;
-  a.n_rows = src.n_rows; a.y = d_y;
+  a.n_rows = src.n_rows; a.y = d_y; a.lens = lens;
   for (size_t off = 0; off < tab.size(); off += MM_TAB_PIECE) {
     TabPiece c;
     c.n = (int)std::min<size_t>(MM_TAB_PIECE, tab.size() - off);
@@ -515,18 +556,21 @@ static int launch_sos_rows(const SosFilt& f, const SegSrc& src, int64_t rows, in
     memcpy(c.v, tab.data() + off, sizeof(double) * (size_t)c.n);
     hipLaunchKernelGGL(clip_tab_upload_kernel, dim3(1), dim3(MM_TAB_PIECE), 0, st, ws, c);
   }
-  if (rows >= MM_ROW_MIN && nseg > 1 && rows <= 0x7FFFFFFF) {      // a workgroup per row: one read + one write per sample
+  // a workgroup per row: one read + one write per sample.  Ragged rows only up to one round of segments: within a round the
+  // workgroup's scan over segments is the wave-per-segment form's, operation for operation, and a ragged row equals the row
+  // filtered alone (which takes that form) bit for bit; the carry into a second round is rounded differently
+  if (rows >= MM_ROW_MIN && nseg > 1 && rows <= 0x7FFFFFFF && (!RG || nseg <= MM_ROW_WAVES)) {
     static PerDeviceOnce attr_once;
     const size_t rlds = (size_t)MM_ROW_WAVES * MM_SEG_LEN * sizeof(double);
     {
       const int rc = per_device_once(attr_once, "sos_row_stream_kernel", [] {
-        return hipFuncSetAttribute((const void*)sos_row_stream_kernel<NS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds) == hipSuccess;
+        return hipFuncSetAttribute((const void*)sos_row_stream_kernel<NS, RG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds) == hipSuccess;
       });
       if (rc) return rc;
     }
     for (int pass = 0; pass < 2; ++pass) {
       a.reverse = pass;
-      hipLaunchKernelGGL((sos_row_stream_kernel<NS>), dim3((unsigned)rows), dim3(64 * MM_ROW_WAVES), rlds, st, a);
+      hipLaunchKernelGGL((sos_row_stream_kernel<NS, RG>), dim3((unsigned)rows), dim3(64 * MM_ROW_WAVES), rlds, st, a);
     }
     return MM_OK;
   }
@@ -536,19 +580,23 @@ static int launch_sos_rows(const SosFilt& f, const SegSrc& src, int64_t rows, in
     a.reverse = pass;
     if (nseg > 1) {
       const int64_t items = rows * (nseg - 1);
-      hipLaunchKernelGGL((sos_seg_state_kernel<NS>), dim3((unsigned)((items + MM_SEG_WAVES - 1) / MM_SEG_WAVES)), blk, lds, st, a);
-      hipLaunchKernelGGL((sos_seg_scan_kernel<NS>), dim3((unsigned)((rows + MM_SEG_WAVES - 1) / MM_SEG_WAVES)), blk, 0, st, a);
+      hipLaunchKernelGGL((sos_seg_state_kernel<NS, RG>), dim3((unsigned)((items + MM_SEG_WAVES - 1) / MM_SEG_WAVES)), blk, lds, st, a);
+      hipLaunchKernelGGL((sos_seg_scan_kernel<NS, RG>), dim3((unsigned)((rows + MM_SEG_WAVES - 1) / MM_SEG_WAVES)), blk, 0, st, a);
     }
-    hipLaunchKernelGGL((sos_seg_apply_kernel<NS>), dim3((unsigned)((rows * nseg + MM_SEG_WAVES - 1) / MM_SEG_WAVES)), blk, lds, st, a);
+    hipLaunchKernelGGL((sos_seg_apply_kernel<NS, RG>), dim3((unsigned)((rows * nseg + MM_SEG_WAVES - 1) / MM_SEG_WAVES)), blk, lds, st, a);
   }
   return MM_OK;
 }
 
 static int launch_sos_rows_any(const SosFilt& f, const SegSrc& src, int64_t rows, int64_t n, double* d_y, double* ws,
-                               hipStream_t st) {
-  return f.n_sec <= 2 ? launch_sos_rows<2>(f, src, rows, n, d_y, ws, st)
-       : f.n_sec == 3 ? launch_sos_rows<3>(f, src, rows, n, d_y, ws, st)
-                      : launch_sos_rows<4>(f, src, rows, n, d_y, ws, st);
+                               hipStream_t st, const int64_t* lens = nullptr) {
+  if (lens)
+    return f.n_sec <= 2 ? launch_sos_rows<2, true>(f, src, rows, n, d_y, ws, st, lens)
+         : f.n_sec == 3 ? launch_sos_rows<3, true>(f, src, rows, n, d_y, ws, st, lens)
+                        : launch_sos_rows<4, true>(f, src, rows, n, d_y, ws, st, lens);
+  return f.n_sec <= 2 ? launch_sos_rows<2, false>(f, src, rows, n, d_y, ws, st, nullptr)
+       : f.n_sec == 3 ? launch_sos_rows<3, false>(f, src, rows, n, d_y, ws, st, nullptr)
+                      : launch_sos_rows<4, false>(f, src, rows, n, d_y, ws, st, nullptr);
 }
 
 // ---- the MFCC-change tail on the segmented rows: one long recording (the reference's own call: a whole file, tStep

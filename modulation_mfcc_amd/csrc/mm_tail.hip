@@ -273,8 +273,9 @@ int mm_sosfiltfilt_f32_f64(const float* d_x, int64_t rows, int64_t n, int64_t x_
   return sosfiltfilt_impl(nullptr, d_x, rows, n, x_stride, sos, n_sec, d_y, d_ws, ws_bytes, stream);
 }
 
-int mm_stencil_f64(const mm_stencil* st, const double* d_x, int64_t rows, int64_t n, int64_t x_stride, double* d_y,
-                   void* stream) {
+// d_lens (DEVICE int64 [rows], or null): the ragged form, n the longest row's length
+static int stencil_impl(const mm_stencil* st, const double* d_x, int64_t rows, int64_t n, int64_t x_stride,
+                        const int64_t* d_lens, double* d_y, void* stream) {
   if (!st || !d_x || !d_y || rows < 1 || n < 1 || x_stride < n) return MM_ERR_INVALID_ARG;
   if (st->n_c < 1 || st->n_c > MM_ST_MAXW || st->n_edge < 0 || st->n_edge > MM_ST_MAXE || st->edge_w < 0 ||
       st->edge_w > MM_ST_MAXW || (st->n_edge > 0 && st->edge_w < 1) || st->den_c == 0.0 ||
@@ -286,10 +287,61 @@ int mm_stencil_f64(const mm_stencil* st, const double* d_x, int64_t rows, int64_
   if (n < 2 * (int64_t)st->n_edge || n < st->edge_w || -lo > st->n_edge || hi > st->n_edge) return MM_ERR_INVALID_ARG;
   const int64_t total = rows * n;
   if ((total + 255) / 256 > 0x7FFFFFFF) return MM_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(stencil_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *st, d_x,
-                     rows, n, x_stride, d_y);
+  if (d_lens)
+    hipLaunchKernelGGL(stencil_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *st,
+                       d_x, rows, n, x_stride, d_lens, d_y);
+  else
+    hipLaunchKernelGGL(stencil_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *st,
+                       d_x, rows, n, x_stride, d_lens, d_y);
   HIP_TRY(hipGetLastError());
   return MM_OK;
+}
+
+int mm_stencil_f64(const mm_stencil* st, const double* d_x, int64_t rows, int64_t n, int64_t x_stride, double* d_y,
+                   void* stream) {
+  return stencil_impl(st, d_x, rows, n, x_stride, nullptr, d_y, stream);
+}
+
+int mm_stencil_ragged_f64(const mm_stencil* st, const double* d_x, int64_t rows, int64_t n_max, int64_t x_stride,
+                          const int64_t* d_lens, double* d_y, void* stream) {
+  if (!d_lens) return MM_ERR_INVALID_ARG;
+  return stencil_impl(st, d_x, rows, n_max, x_stride, d_lens, d_y, stream);
+}
+
+size_t mm_sosfiltfilt_ragged_workspace_bytes(int64_t rows, int64_t n_max) {
+  if (rows < 1 || n_max < 1) return 0;
+  return seg_workspace_doubles(rows, n_max, 3 * (2 * MM_CLIP_NS + 1)) * sizeof(double);   // the segmented rows only
+}
+
+static int sosfiltfilt_ragged_impl(const double* d_x, const float* d_xf, int64_t rows, int64_t n_max, int64_t x_stride,
+                                   const int64_t* d_lens, const double* sos, int32_t n_sec, double* d_y, void* d_ws,
+                                   size_t ws_bytes, void* stream) {
+  if ((!d_x && !d_xf) || !d_lens || !d_y || !d_ws || rows < 1 || n_max < 1 || x_stride < n_max || n_sec < 1)
+    return MM_ERR_INVALID_ARG;
+  SosFilt f;
+  int rc = make_sosfilt(sos, n_sec, &f);
+  if (rc) return rc;
+  if (f.n_sec > MM_CLIP_NS) return MM_ERR_UNSUPPORTED;    // the time-major kernels stay single-length
+  // what the host can know: not even the longest row is one scipy takes (a shorter one comes out NaN, on the device)
+  if (n_max <= f.padlen) return MM_ERR_INVALID_ARG;
+  if (ws_bytes < mm_sosfiltfilt_ragged_workspace_bytes(rows, n_max)) return MM_ERR_WORKSPACE;
+  const SegSrc src = {d_x, x_stride, d_xf, 0, 0, 0};
+  rc = launch_sos_rows_any(f, src, rows, n_max, d_y, (double*)d_ws, (hipStream_t)stream, d_lens);
+  if (rc) return rc;
+  HIP_TRY(hipGetLastError());
+  return MM_OK;
+}
+
+int mm_sosfiltfilt_ragged_f64(const double* d_x, int64_t rows, int64_t n_max, int64_t x_stride, const int64_t* d_lens,
+                              const double* sos, int32_t n_sec, double* d_y, void* d_ws, size_t ws_bytes, void* stream) {
+  if (!d_x) return MM_ERR_INVALID_ARG;
+  return sosfiltfilt_ragged_impl(d_x, nullptr, rows, n_max, x_stride, d_lens, sos, n_sec, d_y, d_ws, ws_bytes, stream);
+}
+
+int mm_sosfiltfilt_ragged_f32_f64(const float* d_x, int64_t rows, int64_t n_max, int64_t x_stride, const int64_t* d_lens,
+                                  const double* sos, int32_t n_sec, double* d_y, void* d_ws, size_t ws_bytes, void* stream) {
+  if (!d_x) return MM_ERR_INVALID_ARG;
+  return sosfiltfilt_ragged_impl(nullptr, d_x, rows, n_max, x_stride, d_lens, sos, n_sec, d_y, d_ws, ws_bytes, stream);
 }
 
 }  // extern "C"

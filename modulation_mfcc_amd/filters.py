@@ -3,6 +3,8 @@
 host exactly as in the reference.  numpy input is filtered by the reference's own scipy calls; float64 curves
 that live on the GPU are filtered there (mm_sosfiltfilt_f64; mm_stencil_f64 for FIR filters up to 8 taps and
 Savitzky-Golay windows up to 16 samples, mm_fir_filtfilt_f64 / mm_savgol_f64 for every longer one) -- SURVEY.md 8(f) row N1.
+A padded batch of device curves with a length per curve goes through apply_filter_ragged_batch (the mm_*_ragged_* entries:
+every row what applyFilter gives for the row alone, in the launches of one call); applyFilter_batch takes a list of curves.
 """
 from __future__ import annotations
 
@@ -390,6 +392,262 @@ def _apply_filter_device(x, sr, kind, *, filt, cutOff, filtLen, polyOrd, coeffs)
                         filtType=kind[:-4], polyOrd=polyOrd, coeffs=coeffs)
         return torch.from_numpy(np.ascontiguousarray(y)).to(x.device)
     raise UnboundLocalError(f"applyFilter: unknown filt {filt!r} (expected 'iir', 'fir' or 'sg')")
+
+
+# ---- ragged batches: a padded batch [rows, n_max] and a length per row -------------------------------------------------
+# Row b of every function below equals the single-length function on x[b:b+1, :n_b] bit for bit in its first n_b columns
+# and is +0.0 behind them; the columns of x at and behind n_b are never read (NaN, Inf, another row's data).  The launches
+# are those of the single-length call at n_max; device lengths are not read back.
+
+_MSG_PADLEN = "The length of the input vector x must be greater than padlen, which is {}."      # sosfiltfilt's, filtfilt's
+_MSG_SG_WINDOW = "If mode is 'interp', window_length must be less than or equal to the size of x."      # savgol_filter's
+
+
+class RowRefused(ValueError):
+    """scipy's own ValueError for one row of a ragged batch, the row named: ``base`` is scipy's text, ``row`` the index."""
+
+    def __init__(self, base, row, n):
+        super().__init__(f"{base} (row {int(row)} has {int(n)} samples)")
+        self.base, self.row, self.n = base, int(row), int(n)
+
+
+def _ragged_rows(x, lengths):
+    """The common argument checks: (x as [rows, n_max] with unit inner stride and a row stride >= n_max, lengths as
+    plan._check_counts returns them: a validated int64 numpy array, or the caller's int64 device tensor untouched)."""
+    import torch
+    from .plan import _check_counts
+    if not (_is_device_tensor(x) and x.dtype in (torch.float64, torch.float32)):
+        raise TypeError("x must be a float64 or float32 CUDA(HIP) tensor")
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError("x must be [rows, n_max], at least one row and one column")
+    rows, n_max = x.shape
+    if (n_max > 1 and x.stride(1) != 1) or (rows > 1 and x.stride(0) < n_max):
+        x = x.contiguous()
+    return x, _check_counts(lengths, rows, n_max, x.device, "lengths")
+
+
+def _refuse_rows(lens, n_max, least, text):
+    """Rows shorter than ``least`` samples are the ones scipy refuses, with ``text``: host lengths raise it with the first
+    such row named, before any launch; device lengths only where not even n_max reaches (such rows come out NaN)."""
+    if isinstance(lens, np.ndarray):
+        short = np.flatnonzero(lens < least)
+        if short.size:
+            raise RowRefused(text, short[0], lens[short[0]])
+    elif n_max < least:
+        raise ValueError(text)
+
+
+def _lens_device(lens, dev):
+    import torch
+    return torch.from_numpy(lens).to(dev) if isinstance(lens, np.ndarray) else lens
+
+
+def sosfiltfilt_ragged_batch(x, lengths, sos):
+    """sosfiltfilt_batch with a length per row (mm_sosfiltfilt_ragged_f64 / _f32_f64): x float64 or float32 [rows, n_max]
+    on the device (rows may be strided), ``lengths`` host integers or an int64 device tensor [rows] -> float64
+    [rows, n_max].  Both odd extensions are formed about the row's own ends, the backward pass starts at the row's own
+    end.  Host lengths at or below scipy's padlen raise scipy's ValueError with the row named; device lengths go through
+    without a read-back (clamped into [1, n_max]; such a row comes out NaN before its length).  Up to 4 sections (more:
+    NotImplementedError, the library's MM_ERR_UNSUPPORTED -- apply_filter_ragged_batch filters those per distinct length)."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    x2, lens = _ragged_rows(x, lengths)
+    rows, n_max = x2.shape
+    s = sos_sections(sos)
+    ntaps = 2 * s.shape[0] + 1 - min(int((s[:, 2] == 0).sum()), int((s[:, 5] == 0).sum()))
+    _refuse_rows(lens, n_max, 3 * ntaps + 1, _MSG_PADLEN.format(3 * ntaps))
+    lib = _lib.load()
+    d_lens = _lens_device(lens, x.device)
+    out = torch.empty((rows, n_max), dtype=torch.float64, device=x.device)
+    ws = torch.empty(int(lib.mm_sosfiltfilt_ragged_workspace_bytes(rows, n_max)), dtype=torch.uint8, device=x.device)
+    fn, name = (lib.mm_sosfiltfilt_ragged_f64, "mm_sosfiltfilt_ragged_f64") if x2.dtype == torch.float64 else \
+        (lib.mm_sosfiltfilt_ragged_f32_f64, "mm_sosfiltfilt_ragged_f32_f64")
+    with torch.cuda.device(x.device):
+        _lib.check(fn(x2.data_ptr(), rows, n_max, x2.stride(0) if rows > 1 else n_max, d_lens.data_ptr(), s.ctypes.data,
+                      s.shape[0], out.data_ptr(), ws.data_ptr(), ws.numel(),
+                      C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), name)
+    return out
+
+
+def fir_filtfilt_ragged_batch(x, lengths, taps):
+    """fir_filtfilt_batch with a length per row (mm_fir_filtfilt_ragged_f64 / _f32_f64), any number of taps L >= 2: x
+    float64 or float32 [rows, n_max] on the device, ``lengths`` as for sosfiltfilt_ragged_batch -> float64 [rows, n_max].
+    The odd extension is staged about the row's own ends (a float32 row's in float32).  Host lengths <= 3 L raise scipy's
+    ValueError with the row named; such a row comes out NaN with device lengths."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    x2, lens = _ragged_rows(x, lengths)
+    rows, n_max = x2.shape
+    b = np.asarray(taps, dtype=np.float64).ravel()
+    L = len(b)
+    if L < 2:
+        raise ValueError("fir_filtfilt_ragged_batch needs at least two taps")
+    _refuse_rows(lens, n_max, 3 * L + 1, _MSG_PADLEN.format(3 * L))
+    d_lens = _lens_device(lens, x.device)
+    out = torch.empty((rows, n_max), dtype=torch.float64, device=x.device)
+    (h,) = _device_tables(("fir", b.tobytes()), x.device, lambda: (fir_filtfilt_taps(b),))
+    lib = _lib.load()
+    fn, name = (lib.mm_fir_filtfilt_ragged_f64, "mm_fir_filtfilt_ragged_f64") if x2.dtype == torch.float64 else \
+        (lib.mm_fir_filtfilt_ragged_f32_f64, "mm_fir_filtfilt_ragged_f32_f64")
+    with torch.cuda.device(x.device):
+        _lib.check(fn(x2.data_ptr(), rows, n_max, x2.stride(0) if rows > 1 else n_max, d_lens.data_ptr(), h.data_ptr(), L,
+                      out.data_ptr(), n_max, C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), name)
+    return out
+
+
+def savgol_ragged_batch(x, lengths, window_length, polyorder, deriv=0, delta=1.0):
+    """savgol_batch with a length per row (mm_savgol_ragged_f64), any window_length: x float64 or float32 [rows, n_max] on
+    the device, ``lengths`` as for sosfiltfilt_ragged_batch -> [rows, n_max], float64, or float32 for a float32 x (filtered
+    in float64, rounded once).  The edge polynomials are fitted to the row's own first and last window.  Host lengths below
+    the window raise scipy's ValueError with the row named; such a row comes out NaN with device lengths."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    x2, lens = _ragged_rows(x, lengths)
+    W, p, deriv, delta = int(window_length), int(polyorder), int(deriv), float(delta)
+    rows, n_max = x2.shape
+    _refuse_rows(lens, n_max, W, _MSG_SG_WINDOW)
+    c, q, pe = _device_tables(("sg", W, p, deriv, delta), x.device, lambda: savgol_tables(W, p, deriv, delta))
+    was_f32 = x2.dtype == torch.float32
+    if was_f32:
+        x2 = x2.double()        # (the padding converts with the rows; it is never read)
+    d_lens = _lens_device(lens, x.device)
+    out = torch.empty((rows, n_max), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().mm_savgol_ragged_f64(x2.data_ptr(), rows, n_max, x2.stride(0) if rows > 1 else n_max,
+                                                    d_lens.data_ptr(), c.data_ptr(), q.data_ptr(), pe.data_ptr(), W, p + 1,
+                                                    out.data_ptr(), n_max,
+                                                    C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)),
+                   "mm_savgol_ragged_f64")
+    return out.float() if was_f32 else out
+
+
+def _apply_filter_per_length(x, lens, sr, kw):
+    """The per-length route of apply_filter_ragged_batch: applyFilter on every group of rows of one length (device lengths
+    are read back first) -> float64 [rows, n_max], zeros behind each row's length.  Host lengths scipy refuses raise its
+    ValueError with the row named; with device lengths such a row comes out NaN, as in the ragged kernels."""
+    import torch
+    from .plan import by_length
+    on_host = isinstance(lens, np.ndarray)
+    if not on_host:
+        lens = lens.clamp(1, x.shape[1]).cpu().numpy()
+    out = torch.zeros(x.shape, dtype=torch.float64, device=x.device)
+    for n, idx in by_length(lens):
+        ii = torch.from_numpy(idx).to(x.device)
+        try:
+            out[ii, :n] = applyFilter(x[ii, :n], sr, **kw)
+        except ValueError as e:
+            if on_host:
+                raise RowRefused(str(e), idx[0], n) from e
+            out[ii, :n] = float("nan")
+    return out
+
+
+def apply_filter_ragged_batch(x, lengths, sr, /, *, filt: str = "iir", cutOff=[None], filtLen: int = 6,
+                              filtType: str = "low", polyOrd: int = 3, coeffs=None):
+    """``applyFilter`` for a padded batch of device curves with a length per row: x float64 or float32 [rows, n_max] on the
+    device (rows may be strided), ``lengths`` host integers or an int64 device tensor [rows] -> [rows, n_max]; row b holds
+    ``applyFilter(x[b, :n_b], sr, ...)`` bit for bit in its first n_b columns and +0.0 behind them, in one ragged call: the
+    launches of ONE single-length call at n_max, whatever the number of distinct lengths.  The columns of x at and behind
+    n_b are never read.  float64 result, except 'sg' on float32 curves, which comes back float32, as applyFilter returns it.
+
+    The routing is applyFilter's for device curves: 'iir' -> sosfiltfilt_ragged_batch; 'sg' and 'fir' through the banded
+    operator (mm_stencil_ragged_f64) where they fit its struct (windows up to 16 samples, up to 8 taps), through
+    savgol_ragged_batch / fir_filtfilt_ragged_batch beyond.  It raises applyFilter's exceptions for the same bad
+    arguments.  Host lengths that scipy refuses raise scipy's ValueError with the row named (RowRefused) before any launch;
+    device lengths are not read back, and such a row comes out NaN before its length.
+
+    Two cases have no ragged kernel and keep the loop over the distinct lengths (applyFilter per group of rows of one
+    length, device lengths read back first; same layout of the result): a float32 'fir' filter of at most 8 taps (its
+    float32 odd extension is formed in torch around the banded operator), and 'iir' filters of more than 4 sections
+    (time-major kernels)."""
+    import torch
+    from . import _lib
+    kind = _validate(filt, cutOff, filtType, sr)
+    kw = dict(filt=filt, cutOff=cutOff, filtLen=filtLen, filtType=filtType, polyOrd=polyOrd, coeffs=coeffs)
+    x2, lens = _ragged_rows(x, lengths)
+    n_max = x2.shape[1]
+    was_f32 = x2.dtype == torch.float32
+    if filt == "iir":
+        if coeffs is not None:
+            sos = np.asarray(coeffs)
+        else:
+            _band_edges(cutOff, sr, kind)
+            sos = _iir_design(sr, cutOff, filtLen, kind)
+        if sos_sections(sos).shape[0] > _lib.MM_RAGGED_MAX_SEC:
+            return _apply_filter_per_length(x2, lens, sr, kw)
+        return sosfiltfilt_ragged_batch(x2, lens, sos)
+    if filt == "sg":
+        if len(cutOff) != 1:
+            raise Exception(_MSG_SG)
+        from .calc import apply_stencil_ragged, velocity_stencil
+        try:
+            st, _ = velocity_stencil(1.0, 0, "sg", filtLen, 2, polyOrd)
+        except NotImplementedError:
+            return savgol_ragged_batch(x2, lens, filtLen, polyOrd, deriv=0, delta=1.0)
+        _refuse_rows(lens, n_max, len(st["c"]), _MSG_SG_WINDOW)
+        y = apply_stencil_ragged(x2.double() if was_f32 else x2, _lens_device(lens, x.device), st)
+        return y.float() if was_f32 else y
+    if filt == "fir":
+        taps = np.asarray(coeffs) if coeffs is not None else \
+            _sig.firwin(filtLen, _band_edges(cutOff, sr, kind), window=("kaiser", 7.4), pass_zero=kind)
+        try:
+            st = fir_filtfilt_stencil(taps)
+        except NotImplementedError:
+            st = None
+        if st is not None:
+            if was_f32:
+                return _apply_filter_per_length(x2, lens, sr, kw)
+            from .calc import apply_stencil_ragged
+            pad = 3 * len(taps)
+            _refuse_rows(lens, n_max, pad + 1, _MSG_PADLEN.format(pad))
+            return apply_stencil_ragged(x2, _lens_device(lens, x.device), st, n_min=pad + 1)
+        if np.size(taps) >= 2:
+            return fir_filtfilt_ragged_batch(x2, lens, taps)
+        return _apply_filter_per_length(x2, lens, sr, kw)       # a single tap: scipy's own exception, through applyFilter
+    raise UnboundLocalError(f"applyFilter: unknown filt {filt!r} (expected 'iir', 'fir' or 'sg')")
+
+
+def applyFilter_batch(curves, sr, /, **kw):
+    """``applyFilter`` for a list of 1-D curves of any lengths -> a list, each entry what ``applyFilter(curve, sr, **kw)``
+    returns for the curve alone, bit for bit.  A numpy curve is filtered by the reference's own scipy call on the host, as
+    applyFilter filters it, and comes back numpy.  The CUDA(HIP) curves form one padded batch per type (float32; float64
+    and everything else, which applyFilter widens) and run through apply_filter_ragged_batch: one ragged call each instead
+    of one call per distinct length.  A curve scipy refuses raises scipy's ValueError with the curve's index appended."""
+    import torch
+    curves = list(curves)
+    out = [None] * len(curves)
+    on_device = [_is_device_tensor(c) for c in curves]
+    for i, c in enumerate(curves):
+        if on_device[i] and c.dim() != 1:
+            raise ValueError(f"curves must be [n] (curve {i})")
+        if not on_device[i]:
+            try:
+                out[i] = applyFilter(c, sr, **kw)
+            except ValueError as e:
+                raise ValueError(f"{e} (curve {i})") from e
+    groups = ([i for i, c in enumerate(curves) if on_device[i] and c.dtype == torch.float32],
+              [i for i, c in enumerate(curves) if on_device[i] and c.dtype != torch.float32])
+    for idx in groups:
+        if not idx:
+            continue
+        dev = curves[idx[0]].device
+        dtype = torch.float32 if curves[idx[0]].dtype == torch.float32 else torch.float64
+        lens = np.array([curves[i].shape[0] for i in idx], dtype=np.int64)
+        if int(lens.min()) < 1:
+            raise ValueError(f"curves must not be empty (curve {idx[int(lens.argmin())]})")
+        x = torch.empty((len(idx), int(lens.max())), dtype=dtype, device=dev)
+        for b, i in enumerate(idx):
+            x[b, :lens[b]].copy_(curves[i], non_blocking=True)
+        try:
+            y = apply_filter_ragged_batch(x, lens, sr, **kw)
+        except RowRefused as e:
+            raise ValueError(f"{e.base} (curve {idx[e.row]})") from e
+        for b, i in enumerate(idx):
+            out[i] = y[b, :lens[b]].clone()
+    return out
 
 
 def applyFilter(x, sr, /, *, filt: str = "iir", cutOff=[None], filtLen: int = 6,

@@ -25,7 +25,7 @@ import scipy.signal
 import scipy.stats
 from scipy import interpolate
 
-from .filters import applyFilter
+from .filters import RowRefused, applyFilter, apply_filter_ragged_batch
 
 __all__ = ["pyin_batch", "pyin_ragged_batch", "pyin_ragged_frames", "pyin", "interp_NAN", "interp_nan_batch",
            "interp_nan_ragged_batch", "get_f0", "get_f0_batch", "pyin_sizes", "beta_tables", "boltzmann_table",
@@ -715,7 +715,9 @@ def get_f0_batch(clips, sr: float, method: str = "praatac", hopSize: float = 0.0
     The float32 clips and the others (float64; integer PCM becomes float64) form one padded batch each, so every clip keeps
     the precision it has alone, and run through pyin_ragged_batch.  ``interpUnvoiced`` runs ragged on the device
     (interp_nan_ragged_batch; 'quadratic' and 'cubic' per clip through scipy, as interp_NAN does).  ``outFilter`` is
-    applied per group of clips with the same frame count, through applyFilter on [g, T].  ``minMaxQuant``: the first pass
+    ONE ragged call on the padded curves with their frame counts (filters.apply_filter_ragged_batch: every row what
+    applyFilter gives for the row alone, bit for bit; only 'iir' filters of more than 4 sections, which have no ragged
+    kernel, still loop over the distinct frame counts there).  ``minMaxQuant``: the first pass
     is ragged; the second has its own fmin / fmax, and with them its own pitch bins and transition band, per clip, so it
     runs pyin_batch clip by clip.  The errors are get_f0's, with the clip's index appended where one clip is at fault."""
     if (interpUnvoiced is None) & (outFilter is not None):
@@ -725,7 +727,6 @@ def get_f0_batch(clips, sr: float, method: str = "praatac", hopSize: float = 0.0
     if method != "pyin":
         raise UnboundLocalError(f"get_f0: unknown method {method!r}")     # reference: f0 unbound
     import torch
-    from .plan import by_length
     clips = list(clips)
     on_device = [_is_device_tensor(c) for c in clips]
     sigs = [c if d else _to_device_signal(c) for c, d in zip(clips, on_device)]
@@ -775,19 +776,13 @@ def get_f0_batch(clips, sr: float, method: str = "praatac", hopSize: float = 0.0
                         f0[b, :frames[b]] = interp_NAN(f0[b, :frames[b]], interpUnvoiced)
                     except (ValueError, IndexError) as e:
                         raise type(e)(f"{e} (clip {i})") from e
-        curves = [None] * len(idx)
         if outFilter is not None:
-            for T, g in by_length(frames):
-                rows = f0[torch.from_numpy(g).to(dev), :T]
-                try:
-                    y = applyFilter(rows, 1 / hopSize, filt=outFilter, cutOff=outFiltCutOff, filtLen=outFiltLen,
-                                    filtType=outFiltType, polyOrd=outFiltPolyOrd)
-                except ValueError as e:                                   # (too few frames for the filter)
-                    raise ValueError(f"{e} (clip {idx[int(g[0])]})") from e
-                for k, b in enumerate(g):
-                    curves[int(b)] = y[k]
-        else:
-            curves = [f0[b, :frames[b]] for b in range(len(idx))]
+            try:
+                f0 = apply_filter_ragged_batch(f0, frames, 1 / hopSize, filt=outFilter, cutOff=outFiltCutOff,
+                                               filtLen=outFiltLen, filtType=outFiltType, polyOrd=outFiltPolyOrd)
+            except RowRefused as e:                                       # (too few frames for the filter)
+                raise ValueError(f"{e.base} (clip {idx[e.row]})") from e
+        curves = [f0[b, :frames[b]] for b in range(len(idx))]
         for b, i in enumerate(idx):
             f = curves[b].clone() if on_device[i] else curves[b].cpu().numpy()
             out[i] = (f, np.arange(int(frames[b])) * hopSize)

@@ -17,7 +17,7 @@ import functools
 import numpy as np
 from scipy import signal as _sig
 
-from .filters import applyFilter, iir_sos
+from .filters import applyFilter, apply_filter_ragged_batch, iir_sos
 
 
 def time_anchors(n_frames: int, tStep: float, winLen: float) -> np.ndarray:
@@ -68,22 +68,16 @@ def mfcc_change_ragged_device(plan, mfcc_dev, frames, *, tStep: float, removeFir
     """``mfcc_change_device`` with a frame count per clip: [B, n_mfcc, T_max] MFCCs on the GPU (``MfccPlan.mfcc_ragged``)
     + ``frames`` [B] (host integers or an int64 device tensor) -> [B, T_max] f64 tensor, row b = the curve of
     mfcc_dev[b, :, :frames[b]] alone in its first frames[b] columns and 0 behind them.  outFilter None / 'iir' run inside
-    the one ragged launch (``MfccPlan.mfcc_change_ragged``).  'fir' / 'sg' have no ragged form: the ragged launch stops
-    after the norm and ``applyFilter`` runs once per distinct frame count (which reads device ``frames`` back)."""
-    from .plan import by_length
+    the one ragged launch (``MfccPlan.mfcc_change_ragged``).  For 'fir' / 'sg' the ragged launch stops after the norm and
+    the curve goes through ONE ``filters.apply_filter_ragged_batch`` call with the same ``frames``: every row equals
+    ``applyFilter`` on the row alone bit for bit, and device ``frames`` are not read back (a clip the filter is too long for
+    comes out NaN; host ``frames`` raise scipy's ValueError with the row named)."""
     sos1 = design_lowpass(filtOrd, filtCutoff, tStep)
     if outFilter in ("fir", "sg"):
-        import torch
         change = plan.mfcc_change_ragged(mfcc_dev, frames, sos1, None, remove_first=bool(removeFirst),
                                          diff_method=diffMethod, out_filter=False)
-        if isinstance(frames, torch.Tensor):
-            frames = frames.clamp(1, change.shape[1]).cpu().numpy()
-        out = torch.zeros_like(change)
-        for T, idx in by_length(frames):
-            ii = torch.from_numpy(idx).to(change.device)
-            out[ii, :T] = applyFilter(change[ii, :T], 1 / tStep, filt=outFilter, filtType=outFiltType, cutOff=outFiltCutOff,
-                                      filtLen=outFiltLen, polyOrd=outFiltPolyOrd)
-        return out
+        return apply_filter_ragged_batch(change, frames, 1 / tStep, filt=outFilter, filtType=outFiltType,
+                                         cutOff=outFiltCutOff, filtLen=outFiltLen, polyOrd=outFiltPolyOrd)
     sos2 = None if outFilter is None else iir_sos(1 / tStep, cutOff=outFiltCutOff, filtLen=outFiltLen,
                                                   filtType=outFiltType)
     return plan.mfcc_change_ragged(mfcc_dev, frames, sos1, sos2, remove_first=bool(removeFirst), diff_method=diffMethod)
