@@ -464,6 +464,14 @@ int mm_resample_f32(const float* d_x, int64_t rows, int64_t n_in, int64_t x_stri
 int mm_resample_banded_f32(const float* d_x, int64_t rows, int64_t n_in, int64_t x_stride, const float* d_atab,
                            const int32_t* d_lo_off, int32_t F, int32_t S, int32_t NB, int32_t ksteps, int32_t lo_min,
                            int32_t win, float* d_y, int64_t n_out, void* stream);
+/* mm_resample_banded_shape: the launch shape mm_resample_banded_f32 would use for these tables -- *qt = periods per LDS
+ *   tile / 16 (8, 4, 2 or 1), *pad = 1 when the tile carries one pad word per 32 (strides S that put the 16 periods of
+ *   a read on few banks), *lds_bytes = the tile.  Host arithmetic only: no HIP call, no device needed; both entries
+ *   go through the same helper.  MM_OK, MM_ERR_UNSUPPORTED (the tile of 16 periods exceeds the LDS: nothing is written)
+ *   or MM_ERR_INVALID_ARG (NULL outputs, F < 16, S < 1, NB != ceil(F / 16), ksteps no positive multiple of 8,
+ *   win < 4 ksteps). */
+int mm_resample_banded_shape(int32_t F, int32_t S, int32_t NB, int32_t ksteps, int32_t win, int32_t* qt, int32_t* pad,
+                             size_t* lds_bytes);
 
 /* Measurement aid: float4 grid-stride device-to-device copy of n_floats (a multiple of 4; 16-byte
  * aligned pointers) on `stream` -- the practical HBM ceiling bench.py quotes beside the stage-isolated

@@ -305,17 +305,18 @@ int mm_resample_f32(const float* d_x, int64_t rows, int64_t n_in, int64_t x_stri
   return MM_OK;
 }
 
-// The same conversion as a banded GEMM on the matrix pipe (mm_resample.hip.inc).  The host lays the taps out as MFMA A
-// operands (modulation_mfcc_amd/audio_io.py: banded_tables): d_atab [NB][ksteps][64] floats, d_lo_off [NB] int32;
-// F = c L >= 16 outputs per period (the host picks the smallest multiple of L that wastes <= 13 % of its last block of 16),
-// S = F M / L input samples per period, lo_min = first input sample (relative to a
-// period's origin, may be negative) of the first block's window, win = floats of one period's window union.
-int mm_resample_banded_f32(const float* d_x, int64_t rows, int64_t n_in, int64_t x_stride, const float* d_atab,
-                           const int32_t* d_lo_off, int32_t F, int32_t S, int32_t NB, int32_t ksteps, int32_t lo_min,
-                           int32_t win, float* d_y, int64_t n_out, void* stream) {
-  if (!d_x || !d_atab || !d_lo_off || !d_y || rows < 1 || n_in < 1 || x_stride < n_in || F < 16 || S < 1 ||
-      NB != (F + 15) / 16 || ksteps < 8 || (ksteps & 7) || win < 4 * ksteps || n_out < 1 || (((uintptr_t)d_atab) & 15))
-    return MM_ERR_INVALID_ARG;
+// Launch shape of the banded resampler for one set of tables (pure host arithmetic, no HIP call): pad = the LDS tile
+// carries one pad word per 32, QT = periods per tile / 16, lds_bytes = the tile.  The one place that decides them:
+// mm_resample_banded_shape reports it, mm_resample_banded_f32 launches it.
+#ifndef MM_RSM_TILE_KB
+#define MM_RSM_TILE_KB 80
+#endif
+#ifndef MM_RSM_WG_PER_CU
+#define MM_RSM_WG_PER_CU 4          // small tiles (1 / 3, 2 / 1 ...): four workgroups per CU, 0.76 -> 0.67 ms at 48 -> 16 kHz
+#endif
+static int rsm_banded_shape(int32_t F, int32_t S, int32_t NB, int32_t ksteps, int32_t win, int* qt_out, bool* pad_out,
+                            size_t* lds_out) {
+  if (F < 16 || S < 1 || NB != (F + 15) / 16 || ksteps < 8 || (ksteps & 7) || win < 4 * ksteps) return MM_ERR_INVALID_ARG;
   // bank pattern of one ds_read_b32: lanes (k = 0, 1) x (q = 0 .. 15) read words q S + k -- pad the tile when more than
   // two of them share a bank
   int cnt[32] = {0}, worst = 0;
@@ -328,15 +329,42 @@ int mm_resample_banded_f32(const float* d_x, int64_t rows, int64_t n_in, int64_t
   };
   // periods per tile = 16 QT: the largest tile of which two fit a CU (two workgroups: one stages while the other
   // multiplies) -- ratios with few blocks per period (1 / 3: NB = 1) get their units from more period tiles
-#ifndef MM_RSM_TILE_KB
-#define MM_RSM_TILE_KB 80
-#endif
-#ifndef MM_RSM_WG_PER_CU
-#define MM_RSM_WG_PER_CU 4          // small tiles (1 / 3, 2 / 1 ...): four workgroups per CU, 0.76 -> 0.67 ms at 48 -> 16 kHz
-#endif
   int QT = 8;
   while (QT > 1 && tile_bytes(QT) > MM_RSM_TILE_KB * 1024) QT >>= 1;
   if (tile_bytes(QT) > MM_LM_LDS_MAX) return MM_ERR_UNSUPPORTED;     // (the caller falls back to mm_resample_f32)
+  *qt_out = QT; *pad_out = pad; *lds_out = tile_bytes(QT);
+  return MM_OK;
+}
+
+int mm_resample_banded_shape(int32_t F, int32_t S, int32_t NB, int32_t ksteps, int32_t win, int32_t* qt, int32_t* pad,
+                             size_t* lds_bytes) {
+  if (!qt || !pad || !lds_bytes) return MM_ERR_INVALID_ARG;
+  int QT = 0;
+  bool pd = false;
+  size_t lds = 0;
+  const int rc = rsm_banded_shape(F, S, NB, ksteps, win, &QT, &pd, &lds);
+  if (rc != MM_OK) return rc;
+  *qt = QT; *pad = pd ? 1 : 0; *lds_bytes = lds;
+  return MM_OK;
+}
+
+// The same conversion as a banded GEMM on the matrix pipe (mm_resample.hip.inc).  The host lays the taps out as MFMA A
+// operands (modulation_mfcc_amd/audio_io.py: banded_tables): d_atab [NB][ksteps][64] floats, d_lo_off [NB] int32;
+// F = c L >= 16 outputs per period (the host picks the smallest multiple of L that wastes <= 13 % of its last block of 16),
+// S = F M / L input samples per period, lo_min = first input sample (relative to a
+// period's origin, may be negative) of the first block's window, win = floats of one period's window union.
+int mm_resample_banded_f32(const float* d_x, int64_t rows, int64_t n_in, int64_t x_stride, const float* d_atab,
+                           const int32_t* d_lo_off, int32_t F, int32_t S, int32_t NB, int32_t ksteps, int32_t lo_min,
+                           int32_t win, float* d_y, int64_t n_out, void* stream) {
+  if (!d_x || !d_atab || !d_lo_off || !d_y || rows < 1 || n_in < 1 || x_stride < n_in || n_out < 1 || (((uintptr_t)d_atab) & 15))
+    return MM_ERR_INVALID_ARG;
+  int QT = 0;
+  bool pad = false;
+  size_t lds = 0;
+  {
+    const int rc = rsm_banded_shape(F, S, NB, ksteps, win, &QT, &pad, &lds);
+    if (rc != MM_OK) return rc;
+  }
   RsmParams q;
   q.x = d_x; q.rows = rows; q.n_in = n_in; q.x_stride = x_stride; q.atab = d_atab; q.lo_off = d_lo_off;
   q.F = F; q.S = S; q.NB = NB; q.ksteps = ksteps; q.lo_min = lo_min; q.QT = QT;
@@ -360,7 +388,6 @@ int mm_resample_banded_f32(const float* d_x, int64_t rows, int64_t n_in, int64_t
   hipDeviceProp_t prop;
   if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
     cus = prop.multiProcessorCount;
-  const size_t lds = tile_bytes(QT);
   const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(MM_RSM_WG_PER_CU, (size_t)MM_LM_LDS_MAX / lds));
   const int64_t grid = std::min<int64_t>(q.n_items, (int64_t)per_cu * cus);
   const bool vec = (((uintptr_t)d_x) & 15) == 0 && (x_stride & 3) == 0;
