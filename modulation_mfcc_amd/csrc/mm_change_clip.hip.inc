@@ -24,22 +24,19 @@
 //      matrix-vector product; the sequential chain of chg_sos_chunk_kernel costs K of them on the last chunk).
 //      K is a power of two <= 64 and the chunks of a sequence are consecutive lanes of ONE wave, so the values
 //      travel by lane shuffles: no LDS buffer, no barrier (with an LDS buffer and two barriers a step cost ~1000
-//      cycles, and the two scans were a third of the kernel)
+//      cycles, and the two scans were a third of the kernel): sos_lane_scan, mm_sos.hip.inc
 //   C  every thread runs the recursion over its chunk from Z(k) and stores the outputs in place
-// W and the powers of Phi come from the host through the first bytes of the caller's workspace (clip_tables below,
-// uploaded by kernel-argument copies: asynchronous, stateless, graph-capture safe like every compute call).
+// W and the powers of Phi come from the host through the first bytes of the caller's workspace (sos_scan_tables,
+// uploaded by sos_tab_upload).
 //
 // Differs from the time-major kernels and from scipy's sequential recursion by rounding only (~1e-14 relative).
-// Taken when both filters have <= MM_CLIP_NS sections and one row (plus the curve) fits LDS; otherwise
+// Taken when both filters have <= MM_SCAN_MAX_SEC sections and one row (plus the curve) fits LDS; otherwise
 // mm_mfcc_change_f64 keeps the time-major kernels.
-#define MM_CLIP_NS 4
 #define MM_CLIP_MAXTHREADS 1024   // rows resident x chunks per row, rounded up to waves
 #define MM_CLIP_LDS_MAX (160 * 1024)
 #define MM_CLIP_KMAX 64           // chunks per sequence: a power of two, one wave holds a sequence's chunks
 #define MM_CLIP_JMAX 6            // log2 of it
 #define MM_CLIP_LU 16             // row loads in flight per thread
-#define MM_CONST __attribute__((address_space(4)))
-#define MM_TAB_PIECE 480          // doubles per upload launch (3.8 KB of kernel argument: under the 4 KB a launch may carry)
 
 template <int NS>
 struct ClipFilt {
@@ -60,25 +57,13 @@ struct ChgClipArgs {
   const int64_t* frames;         // ragged form only: [batch] valid frames per clip (device)
 };
 
-struct TabPiece { int n, off; double v[MM_TAB_PIECE]; };
-__global__ __launch_bounds__(MM_TAB_PIECE) void clip_tab_upload_kernel(double* dst, TabPiece c) {
-  if ((int)threadIdx.x < c.n) dst[c.off + threadIdx.x] = c.v[threadIdx.x];
-}
-
-// v of the lane whose byte address (4 * lane) is given; a negative address wraps inside the wave
-__device__ __forceinline__ double lane_from(int byte_addr, double v) {
-  const int lo = __builtin_amdgcn_ds_bpermute(byte_addr, __double2loint(v));
-  const int hi = __builtin_amdgcn_ds_bpermute(byte_addr, __double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
-
 // forward + reverse pass in place over n_seq sequences of n samples at X + r * pitch; thread = (sequence, chunk),
 // g.K a power of two <= 64.  tab: clip_tables (global memory, read through the scalar cache).  Every thread of the
 // block must call it (barriers inside); ends with a barrier.
 template <int NS>
 __device__ __forceinline__ void clip_filtfilt(double* X, int pitch, int n, int n_seq, const ClipFilt<NS>& g,
                                               const MM_CONST double* tab MM_STAMP_FWD_DECL) {
-  constexpr int U = 4, S2 = 2 * NS, TRI = 2 * NS * (NS + 1);
+  constexpr int U = 4, S2 = 2 * NS;
   const int task = threadIdx.x;
   const bool on = task < n_seq * g.K;
   const int r = on ? task >> g.J : 0, k = task & (g.K - 1);
@@ -112,9 +97,8 @@ __device__ __forceinline__ void clip_filtfilt(double* X, int pitch, int n, int n
       }
     }
     MM_STAMP_REL(0)
-    // ---- B: u(0) = zi * first sample, u(k) = S(k - 1); inclusive scan over the K lanes of the sequence.
-    //         Raw ds_bpermute (byte address of the source lane): lanes without a source d lanes back inside
-    //         their sequence read some other lane and ignore it
+    // ---- B: u(0) = zi * first sample, u(k) = S(k - 1); inclusive scan over the K lanes of the sequence
+    //         (a lane without a source inside its sequence reads some other lane and ignores it)
     {
       const double x0 = w[pass ? n - 1 : 0];
       const int src = ((int)(threadIdx.x & 63) - 1) << 2;
@@ -124,27 +108,7 @@ __device__ __forceinline__ void clip_filtfilt(double* X, int pitch, int n, int n
         Z[a] = k == 0 ? g.f.zi[a >> 1][a & 1] * x0 : up;
       }
     }
-#pragma unroll 1
-    for (int j = 0; j < g.J; ++j) {
-      const int d = 1 << j;
-      // Phi and its powers are block lower triangular (a section's state never reaches the sections before it):
-      // column b holds rows 2 * (b / 2) .. 2 NS - 1 only, TRI = 2 NS (NS + 1) numbers instead of 4 NS^2
-      double pr[S2], Pm[TRI];
-      const MM_CONST double* Pj = P + j * TRI;
-#pragma unroll
-      for (int e = 0; e < TRI; ++e) Pm[e] = Pj[e];             // the whole matrix in one round trip of the scalar cache
-      const int src = ((int)(threadIdx.x & 63) - d) << 2;
-#pragma unroll
-      for (int b = 0; b < S2; ++b) pr[b] = lane_from(src, Z[b]);
-      if (k >= d) {
-#pragma unroll
-        for (int b = 0; b < S2; ++b) {               // column by column: independent accumulators
-          const int base = (b >> 1) * 2 * (2 * NS - (b >> 1) + 1) + (b & 1) * (S2 - (b & ~1));   // columns before b
-#pragma unroll
-          for (int a = (b & ~1); a < S2; ++a) Z[a] = fma(Pm[base + a - (b & ~1)], pr[b], Z[a]);
-        }
-      }
-    }
+    sos_lane_scan<NS>(Z, P, 0, g.J, (int)(threadIdx.x & 63), k);
     MM_STAMP_REL(1)
     // ---- C: the recursion over the chunk from its start state, outputs in place (A read this chunk only: no barrier)
     {
@@ -273,13 +237,12 @@ __global__ __launch_bounds__(MM_CLIP_MAXTHREADS) void chg_clip_kernel(ChangePara
         }
       } else {
         // first / last sample (T > padlen >= 6): np.gradient's one-sided difference, or the derivative of the
-        // parabola through the three end samples (chg_norm_kernel); x0 x1 x2 = those samples in time order
+        // parabola through the three end samples (chg_end_deriv)
         const double* fe = f + (t == 0 ? 0 : T - 3);
 #pragma unroll 4
         for (int r = 0; r < g; ++r) {
-          const double x0 = fe[r * a.pitch], x1 = fe[r * a.pitch + 1], x2 = fe[r * a.pitch + 2];
-          const double d = t == 0 ? (p.sg ? (-3.0 * x0 + 4.0 * x1 - x2) / 2.0 : x1 - x0)
-                                  : (p.sg ? (3.0 * x2 - 4.0 * x1 + x0) / 2.0 : x2 - x1);
+          const double x[3] = {fe[r * a.pitch], fe[r * a.pitch + 1], fe[r * a.pitch + 2]};
+          const double d = chg_end_deriv(t == 0, p.sg, [&](int i) { return x[i]; });
           acc += d * d;
         }
       }
@@ -305,77 +268,6 @@ __global__ __launch_bounds__(MM_CLIP_MAXTHREADS) void chg_clip_kernel(ChangePara
 }
 
 // ---- host side ----
-template <int NS>
-static void sos_coef_of(const SosFilt& f, SosCoef<NS>* c) {
-  for (int s = 0; s < NS; ++s) {
-    if (s < f.n_sec) {
-      c->c[s][0] = f.c[s][0]; c->c[s][1] = f.c[s][1]; c->c[s][2] = f.c[s][2]; c->c[s][3] = f.c[s][4]; c->c[s][4] = f.c[s][5];
-      c->zi[s][0] = f.zi[s][0]; c->zi[s][1] = f.zi[s][1];
-    } else {
-      c->c[s][0] = 1.0; c->c[s][1] = c->c[s][2] = c->c[s][3] = c->c[s][4] = 0.0;
-      c->zi[s][0] = c->zi[s][1] = 0.0;
-    }
-  }
-}
-
-// The two tables the scans of this file and of mm_sos_rows.hip.inc close the recursion with, for chunks of `chunk` samples:
-//   W[chunk - 1 - m] = the state m zero-input steps after a unit sample                       [chunk][2 NS]
-//   P[j] = Phi^(2^j), j < J; Phi = the transition of one chunk with zero input, stored by columns, rows 2 * (b / 2) .. only
-// Built in the host's extended precision (x87 long double, 64-bit mantissa) and rounded ONCE when stored.  The powers
-// come from repeated squaring, and with the poles within 1e-3 of the unit circle the entries of Phi^k are large against
-// what they add up to: squared in double, a 12 Hz low-pass at 48 kHz (wn = 5e-4) came out 2e-8 of its maximum away from
-// the exact result, a thousand times scipy's own rounding; with exact-to-the-last-bit tables what is left is the
-// device's double arithmetic, which is scipy's (docs/experiments.md, "The IIR filter near the unit circle").
-#include <cfloat>
-#if !defined(__HIP_DEVICE_COMPILE__)
-static_assert(LDBL_MANT_DIG >= 64, "the scan tables need an extended-precision long double on the host");
-#endif
-template <int NS>
-static void sos_scan_tables(const SosCoef<NS>& f, int chunk, int J, double* W, double* P) {
-  typedef long double xreal;
-  constexpr int S2 = 2 * NS;
-  xreal c[NS][5];
-  for (int s = 0; s < NS; ++s) for (int k = 0; k < 5; ++k) c[s][k] = (xreal)f.c[s][k];
-  // one step of the cascade (direct form II transposed) on input x
-  auto step = [&](xreal x, xreal (&z0)[NS], xreal (&z1)[NS]) {
-    for (int s = 0; s < NS; ++s) {
-      const xreal y = c[s][0] * x + z0[s];
-      z0[s] = c[s][1] * x - c[s][3] * y + z1[s];
-      z1[s] = c[s][2] * x - c[s][4] * y;
-      x = y;
-    }
-  };
-  {
-    xreal z0[NS], z1[NS];
-    for (int s = 0; s < NS; ++s) { z0[s] = 0; z1[s] = 0; }
-    for (int m = 0; m < chunk; ++m) {
-      step(m == 0 ? (xreal)1 : (xreal)0, z0, z1);
-      double* Wm = W + (size_t)(chunk - 1 - m) * S2;
-      for (int s = 0; s < NS; ++s) { Wm[2 * s] = (double)z0[s]; Wm[2 * s + 1] = (double)z1[s]; }
-    }
-  }
-  xreal A[S2][S2], B[S2][S2];
-  for (int b = 0; b < S2; ++b) {
-    xreal z0[NS], z1[NS];
-    for (int s = 0; s < NS; ++s) { z0[s] = 0; z1[s] = 0; }
-    (b & 1 ? z1 : z0)[b >> 1] = 1;
-    for (int i = 0; i < chunk; ++i) step(0, z0, z1);
-    for (int s = 0; s < NS; ++s) { A[2 * s][b] = z0[s]; A[2 * s + 1][b] = z1[s]; }
-  }
-  constexpr int TRI = 2 * NS * (NS + 1);
-  for (int j = 0; j < J; ++j) {
-    double* Pj = P + (size_t)j * TRI;
-    int e = 0;
-    for (int b = 0; b < S2; ++b) for (int a = (b & ~1); a < S2; ++a) Pj[e++] = (double)A[a][b];
-    for (int a = 0; a < S2; ++a) for (int b = 0; b < S2; ++b) {
-      xreal acc = 0;
-      for (int k = 0; k < S2; ++k) acc += A[a][k] * A[k][b];
-      B[a][b] = acc;
-    }
-    for (int a = 0; a < S2; ++a) for (int b = 0; b < S2; ++b) A[a][b] = B[a][b];
-  }
-}
-
 // chunk length, scan depth and the two tables of one filter, appended to `tab`
 template <int NS>
 static void clip_filt_of(const SosFilt& f, int n, int K, ClipFilt<NS>* g, std::vector<double>& tab) {
@@ -397,7 +289,7 @@ struct ClipShape { int G, K1, K2, pitch, threads; size_t lds; int64_t tab_n; };
 // rows resident at once (in `groups` equal groups), chunk counts and workgroup size under an LDS budget; G = 0: no room
 static ClipShape clip_shape_under(int n_rows, int64_t n1, int64_t n2, int64_t lds_max, int* groups) {
   ClipShape s;
-  constexpr int64_t S2 = 2 * MM_CLIP_NS;
+  constexpr int64_t S2 = 2 * MM_SCAN_MAX_SEC;
   s.pitch = (int)(n1 | 1);
   s.K2 = MM_CLIP_KMAX;
   const int64_t room = lds_max / 8 - ((n2 + 1) & ~(int64_t)1) - 1;
@@ -413,7 +305,7 @@ static ClipShape clip_shape_under(int n_rows, int64_t n1, int64_t n2, int64_t ld
   while (s.K1 > 1 && G * s.K1 > MM_CLIP_MAXTHREADS) s.K1 >>= 1;
   s.threads = (int)std::max<int64_t>((G * s.K1 + 63) / 64 * 64, s.K2);
   s.lds = (size_t)(((G * s.pitch + 1) & ~(int64_t)1) + ((n2 + 1) & ~(int64_t)1)) * 8;
-  // upper bound of the table (MM_CLIP_NS sections, deepest scan): what the workspace must hold
+  // upper bound of the table (MM_SCAN_MAX_SEC sections, deepest scan): what the workspace must hold
   s.tab_n = (((n1 + s.K1 - 1) / s.K1 | 1) + ((n2 + s.K2 - 1) / s.K2 | 1)) * S2 + 2 * MM_CLIP_JMAX * S2 * S2;
   return s;
 }
@@ -451,13 +343,7 @@ static int launch_chg_clip(const ChangeParams& q, const SosFilt& f1, const SosFi
     clip_filt_of<NS>(f2, (int)n2, s.K2, &a.f2, tab);
   if ((int64_t)tab.size() > s.tab_n) return MM_ERR_WORKSPACE;     // (cannot happen: tab_n is the bound the caller's workspace was checked against)
   a.tab = d_tab; a.tab_n = (int)tab.size();
-  for (size_t off = 0; off < tab.size(); off += MM_TAB_PIECE) {
-    TabPiece c;
-    c.n = (int)std::min<size_t>(MM_TAB_PIECE, tab.size() - off);
-    c.off = (int)off;
-    memcpy(c.v, tab.data() + off, sizeof(double) * (size_t)c.n);
-    hipLaunchKernelGGL(clip_tab_upload_kernel, dim3(1), dim3(MM_TAB_PIECE), 0, st, d_tab, c);
-  }
+  sos_tab_upload(tab, d_tab, st);
   hipLaunchKernelGGL((chg_clip_kernel<NS, RAG>), dim3((unsigned)q.batch), dim3((unsigned)s.threads), s.lds, st, q, a);
   return MM_OK;
 }

@@ -3,10 +3,10 @@
 // applyFilter (script/mfcc.py:29-135, script/calc.py:23-129) on a batch of curves -- amplitude envelopes at the audio rate
 // (method 'Hilb': 160 000 samples per ten-second clip, script/calc.py:284-343), RMS envelopes, MFCC-change curves.
 //
-// The time-major kernels of mm_change.hip.inc give a row to a lane and cut it into 8 chunks: 256 envelopes of 160 000
+// The time-major kernels of mm_sos_tm.hip.inc give a row to a lane and cut it into 8 chunks: 256 envelopes of 160 000
 // samples keep 32 waves busy on a chip that holds 4096 (10 ms, 65 GB/s).  Here a row is cut into SEGMENTS of 64 chunks x
 // 17 samples, a wave per segment with the segment in LDS (coalesced loads along time, lane = chunk), and the linear
-// recursion is closed over three levels (chunk, segment, row) with the machinery of mm_change_clip.hip.inc:
+// recursion is closed over three levels (chunk, segment, row) with the tables and the lane scan of mm_sos.hip.inc:
 //
 //   per direction
 //   1 sos_seg_state_kernel   wave = (row, segment): S(k) = sum_i W[i] x[k][i] per chunk (end state from zero state), then
@@ -74,10 +74,8 @@ struct SegSource {
     }
     if (reverse) { base = a.ws + row * a.ws_stride; e0 = e1 = 0.0; }
     else if (a.xf) {
-      if (a.n_mfcc > 0) {
-        const int64_t clip = row / a.n_rows;
-        basef = a.xf + ((clip * a.n_mfcc + a.first_row + (row - clip * a.n_rows)) * a.n);
-      } else basef = a.xf + row * a.x_stride;
+      if (a.n_mfcc > 0) basef = mfcc_row(a.xf, a.n_mfcc, a.first_row, a.n_rows, a.n, row);
+      else basef = a.xf + row * a.x_stride;
       e0 = (double)basef[0]; e1 = (double)basef[n - 1];
     } else { base = a.x + row * a.x_stride; e0 = base[0]; e1 = base[n - 1]; }
   }
@@ -102,28 +100,36 @@ struct SegSource {
   }
 };
 
+// a segment that touches neither the extension nor the row's end (all but two or three per row) ...
+template <int NS, bool RG>
+__device__ __forceinline__ bool seg_inner(const SegSource<NS, RG>& src, int64_t p0) {
+  return src.reverse ? p0 + MM_SEG_LEN <= src.n_ext : (p0 >= src.pad && p0 + MM_SEG_LEN <= src.pad + src.n);
+}
+// ... is loaded from one address per lane, the 17 loads at immediate offsets
+template <int NS, bool RG>
+__device__ __forceinline__ void seg_inner_loads(const SegSource<NS, RG>& src, int64_t p0, int lane, double (&v)[MM_SEG_CH]) {
+  if (src.reverse) {
+    // ascending addresses over ascending lanes (v[m] = pass position MM_SEG_LEN - 1 - lane - 64 m: the puts below mirror)
+    const double* q = src.base + (src.n_ext - p0 - MM_SEG_LEN + lane);
+#pragma unroll
+    for (int m = 0; m < MM_SEG_CH; ++m) v[m] = q[64 * m];
+  } else if (src.basef) {
+    const float* q = src.basef + (p0 - src.pad + lane);
+#pragma unroll
+    for (int m = 0; m < MM_SEG_CH; ++m) v[m] = (double)q[64 * m];
+  } else {
+    const double* q = src.base + (p0 - src.pad + lane);
+#pragma unroll
+    for (int m = 0; m < MM_SEG_CH; ++m) v[m] = q[64 * m];
+  }
+}
+
 template <int NS, bool RG>
 __device__ __forceinline__ void seg_load(const SegSource<NS, RG>& src, int64_t p0, double* slab, int lane) {
   double v[MM_SEG_CH];
-  // a segment that touches neither the extension nor the row's end (all but two or three per row): one address per
-  // lane, the 17 loads at immediate offsets
-  const bool inner = src.reverse ? p0 + MM_SEG_LEN <= src.n_ext : (p0 >= src.pad && p0 + MM_SEG_LEN <= src.pad + src.n);
-  if (inner) {
-    if (src.reverse) {
-      // ascending addresses over ascending lanes (v[m] = pass position MM_SEG_LEN - 1 - lane - 64 m: the put below mirrors)
-      const double* q = src.base + (src.n_ext - p0 - MM_SEG_LEN + lane);
-#pragma unroll
-      for (int m = 0; m < MM_SEG_CH; ++m) v[m] = q[64 * m];
-    } else if (src.basef) {
-      const float* q = src.basef + (p0 - src.pad + lane);
-#pragma unroll
-      for (int m = 0; m < MM_SEG_CH; ++m) v[m] = (double)q[64 * m];
-    } else {
-      const double* q = src.base + (p0 - src.pad + lane);
-#pragma unroll
-      for (int m = 0; m < MM_SEG_CH; ++m) v[m] = q[64 * m];
-    }
-  } else {
+  const bool inner = seg_inner<NS, RG>(src, p0);
+  if (inner) seg_inner_loads<NS, RG>(src, p0, lane, v);
+  else {
 #pragma unroll
     for (int m = 0; m < MM_SEG_CH; ++m) v[m] = src.at(p0 + lane + 64 * m);
   }
@@ -137,25 +143,12 @@ __device__ __forceinline__ void seg_load(const SegSource<NS, RG>& src, int64_t p
 }
 
 // seg_load in two halves for sos_row_stream_kernel: the loads of a segment issued into registers a round ahead
-// (seg_fetch: only a segment that touches neither the extension nor the row's end), the slab written when its turn comes
+// (seg_fetch: only an inner segment), the slab written when its turn comes
 template <int NS, bool RG>
 __device__ __forceinline__ bool seg_fetch(const SegSource<NS, RG>& src, int64_t p0, int lane, double (&v)[MM_SEG_CH]) {
-  const bool inner = src.reverse ? p0 + MM_SEG_LEN <= src.n_ext : (p0 >= src.pad && p0 + MM_SEG_LEN <= src.pad + src.n);
-  if (!inner) return false;
-  if (src.reverse) {
-    const double* q = src.base + (src.n_ext - p0 - MM_SEG_LEN + lane);
-#pragma unroll
-    for (int m = 0; m < MM_SEG_CH; ++m) v[m] = q[64 * m];
-  } else if (src.basef) {
-    const float* q = src.basef + (p0 - src.pad + lane);
-#pragma unroll
-    for (int m = 0; m < MM_SEG_CH; ++m) v[m] = (double)q[64 * m];
-  } else {
-    const double* q = src.base + (p0 - src.pad + lane);
-#pragma unroll
-    for (int m = 0; m < MM_SEG_CH; ++m) v[m] = q[64 * m];
-  }
-  return true;
+  const bool inner = seg_inner<NS, RG>(src, p0);
+  if (inner) seg_inner_loads<NS, RG>(src, p0, lane, v);
+  return inner;
 }
 
 template <int NS, bool RG>
@@ -187,31 +180,6 @@ __device__ __forceinline__ void seg_weighted_sum(const double* q, const MM_CONST
   }
 }
 
-// inclusive scan over the 64 lanes: Z(lane) <- sum_{i <= lane} M^(lane - i) Z(i), M^(2^j) = P[j0 + j]
-template <int NS>
-__device__ __forceinline__ void seg_scan(double (&Z)[2 * NS], const MM_CONST double* P, int j0, int lane) {
-  constexpr int S2 = 2 * NS, TRI = 2 * NS * (NS + 1);
-#pragma unroll 1
-  for (int j = 0; j < 6; ++j) {
-    const int d = 1 << j;
-    double pr[S2], Pm[TRI];
-    const MM_CONST double* Pj = P + (j0 + j) * TRI;
-#pragma unroll
-    for (int e = 0; e < TRI; ++e) Pm[e] = Pj[e];
-    const int src = (lane - d) << 2;
-#pragma unroll
-    for (int b = 0; b < S2; ++b) pr[b] = lane_from(src, Z[b]);
-    if (lane >= d) {
-#pragma unroll
-      for (int b = 0; b < S2; ++b) {
-        const int base = (b >> 1) * 2 * (2 * NS - (b >> 1) + 1) + (b & 1) * (S2 - (b & ~1));
-#pragma unroll
-        for (int a = (b & ~1); a < S2; ++a) Z[a] = fma(Pm[base + a - (b & ~1)], pr[b], Z[a]);
-      }
-    }
-  }
-}
-
 // Z <- M Z for one packed matrix
 template <int NS>
 __device__ __forceinline__ void seg_matvec(double (&Z)[2 * NS], const MM_CONST double* Pj) {
@@ -221,7 +189,7 @@ __device__ __forceinline__ void seg_matvec(double (&Z)[2 * NS], const MM_CONST d
   for (int a = 0; a < S2; ++a) o[a] = 0.0;
 #pragma unroll
   for (int b = 0; b < S2; ++b) {
-    const int base = (b >> 1) * 2 * (2 * NS - (b >> 1) + 1) + (b & 1) * (S2 - (b & ~1));
+    const int base = sos_tri_col(NS, b);
 #pragma unroll
     for (int a = (b & ~1); a < S2; ++a) o[a] = fma(Pj[base + a - (b & ~1)], Z[b], o[a]);
   }
@@ -248,7 +216,7 @@ __global__ __launch_bounds__(64 * MM_SEG_WAVES) void sos_seg_state_kernel(SegArg
   wave_lds_sync();
   double Z[S2];
   seg_weighted_sum<NS>(slab + lane * MM_SEG_CH, W, Z);
-  seg_scan<NS>(Z, P, 0, lane);
+  sos_lane_scan<NS, 6>(Z, P, 0, 6, lane, lane);
   if (lane == 63) {
     double* o = a.seg_S + (row * a.n_seg + seg) * S2;
 #pragma unroll
@@ -280,7 +248,7 @@ __global__ __launch_bounds__(64 * MM_SEG_WAVES) void sos_seg_scan_kernel(SegArgs
     const bool have = lane > 0 && s - 1 < n_seg - 1;
 #pragma unroll
     for (int c = 0; c < S2; ++c) Z[c] = lane == 0 ? carry[c] : (have ? S[(int64_t)(s - 1) * S2 + c] : 0.0);
-    seg_scan<NS>(Z, P, 6, lane);
+    sos_lane_scan<NS, 6>(Z, P, 6, 6, lane, lane);
     if (s < n_seg) {
 #pragma unroll
       for (int c = 0; c < S2; ++c) Zo[(int64_t)s * S2 + c] = Z[c];
@@ -381,7 +349,7 @@ __global__ __launch_bounds__(64 * MM_SEG_WAVES) void sos_seg_apply_kernel(SegArg
       Z[c] = lane == 0 ? z0[c] : up;
     }
   }
-  seg_scan<NS>(Z, P, 0, lane);
+  sos_lane_scan<NS, 6>(Z, P, 0, 6, lane, lane);
   {
     double z0[NS], z1[NS], v[MM_SEG_CH];
 #pragma unroll
@@ -410,8 +378,8 @@ __global__ __launch_bounds__(64 * MM_SEG_WAVES) void sos_seg_apply_kernel(SegArg
 template <int NS, bool RG>
 __global__ __launch_bounds__(64 * MM_ROW_WAVES) void sos_row_stream_kernel(SegArgs<NS, RG> a) {
   extern __shared__ double seg_lds[];
-  __shared__ double segS[2][MM_ROW_WAVES][2 * MM_CLIP_NS];
-  __shared__ double segZ[MM_ROW_WAVES][2 * MM_CLIP_NS];
+  __shared__ double segS[2][MM_ROW_WAVES][2 * MM_SCAN_MAX_SEC];
+  __shared__ double segZ[MM_ROW_WAVES][2 * MM_SCAN_MAX_SEC];
   constexpr int S2 = 2 * NS;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t row = blockIdx.x;
@@ -421,7 +389,7 @@ __global__ __launch_bounds__(64 * MM_ROW_WAVES) void sos_row_stream_kernel(SegAr
   const MM_CONST double* P = W + MM_SEG_CH * S2;
   const SegSource<NS, RG> src(a, row);
   const int n_seg = src.n_seg;                             // the row's own: uniform over the workgroup, like every barrier below
-  __shared__ double carry[2 * MM_CLIP_NS];                 // start state of segment `base` (wave 0 reads and writes it)
+  __shared__ double carry[2 * MM_SCAN_MAX_SEC];                 // start state of segment `base` (wave 0 reads and writes it)
   if (threadIdx.x == 0 && (!RG || n_seg > 0)) {
     const double x0 = src.at(0);
 #pragma unroll
@@ -448,7 +416,7 @@ __global__ __launch_bounds__(64 * MM_ROW_WAVES) void sos_row_stream_kernel(SegAr
       double V[S2];
 #pragma unroll
       for (int c = 0; c < S2; ++c) V[c] = S[c];
-      seg_scan<NS>(V, P, 0, lane);                         // lane 63: the end state the segment reaches from zero state
+      sos_lane_scan<NS, 6>(V, P, 0, 6, lane, lane);              // lane 63: the end state the segment reaches from zero state
       if (lane == 63) {
 #pragma unroll
         for (int c = 0; c < S2; ++c) segS[r & 1][wave][c] = V[c];
@@ -464,7 +432,7 @@ __global__ __launch_bounds__(64 * MM_ROW_WAVES) void sos_row_stream_kernel(SegAr
       double Z[S2];
 #pragma unroll
       for (int c = 0; c < S2; ++c) Z[c] = lane == 0 ? carry[c] : (lane <= MM_ROW_WAVES ? segS[r & 1][lane - 1 < 0 ? 0 : lane - 1][c] : 0.0);
-      seg_scan<NS>(Z, P, 6, lane);
+      sos_lane_scan<NS, 6>(Z, P, 6, 6, lane, lane);
       if (lane < MM_ROW_WAVES) {
 #pragma unroll
         for (int c = 0; c < S2; ++c) segZ[lane][c] = Z[c];
@@ -485,7 +453,7 @@ __global__ __launch_bounds__(64 * MM_ROW_WAVES) void sos_row_stream_kernel(SegAr
         const double up = lane_from(from, S[c]);
         Z[c] = lane == 0 ? segZ[wave][c] : up;
       }
-      seg_scan<NS>(Z, P, 0, lane);
+      sos_lane_scan<NS, 6>(Z, P, 0, 6, lane, lane);
       MM_STAMP_AT(6)
       {
         double z0[NS], z1[NS], y[MM_SEG_CH];
@@ -512,7 +480,7 @@ template <int NS>
 static void seg_tables(const SosCoef<NS>& c, std::vector<double>& tab) {
   constexpr int S2 = 2 * NS, TRI = 2 * NS * (NS + 1);
   tab.assign((size_t)MM_SEG_CH * S2 + (size_t)MM_SEG_JT * TRI, 0.0);
-  sos_scan_tables<NS>(c, MM_SEG_CH, MM_SEG_JT, tab.data(), tab.data() + (size_t)MM_SEG_CH * S2);   // mm_change_clip.hip.inc
+  sos_scan_tables<NS>(c, MM_SEG_CH, MM_SEG_JT, tab.data(), tab.data() + (size_t)MM_SEG_CH * S2);
 }
 
 static int64_t seg_count(int64_t n_ext) { return (n_ext + MM_SEG_LEN - 1) / MM_SEG_LEN; }
@@ -520,7 +488,7 @@ static int64_t seg_ws_stride(int64_t n_ext) { return (n_ext + 1) & ~(int64_t)1; 
 // doubles of workspace: table | seg_S | seg_Z | padded rows
 static size_t seg_workspace_doubles(int64_t rows, int64_t n, int pad) {
   const int64_t n_ext = n + 2 * (int64_t)pad;
-  return (size_t)(1024 + 2 * rows * seg_count(n_ext) * 2 * MM_CLIP_NS + rows * seg_ws_stride(n_ext));
+  return (size_t)(1024 + 2 * rows * seg_count(n_ext) * 2 * MM_SCAN_MAX_SEC + rows * seg_ws_stride(n_ext));
 }
 
 struct SegSrc {                  // where the forward pass reads: float64 rows, or float32 MFCC rows of clips
@@ -545,17 +513,11 @@ static int launch_sos_rows(const SosFilt& f, const SegSrc& src, int64_t rows, in
   a.tab = ws;
   a.seg_S = ws + 1024;
   a.seg_Z = a.seg_S + rows * nseg * S2;
-  a.ws = ws + 1024 + 2 * rows * nseg * 2 * MM_CLIP_NS;
+  a.ws = ws + 1024 + 2 * rows * nseg * 2 * MM_SCAN_MAX_SEC;
   a.ws_stride = seg_ws_stride(a.n_ext);
   a.x = src.x; a.x_stride = src.x_stride; a.xf = src.xf; a.n_mfcc = src.n_mfcc; a.first_row = src.first_row;
   a.n_rows = src.n_rows; a.y = d_y; a.lens = lens;
-  for (size_t off = 0; off < tab.size(); off += MM_TAB_PIECE) {
-    TabPiece c;
-    c.n = (int)std::min<size_t>(MM_TAB_PIECE, tab.size() - off);
-    c.off = (int)off;
-    memcpy(c.v, tab.data() + off, sizeof(double) * (size_t)c.n);
-    hipLaunchKernelGGL(clip_tab_upload_kernel, dim3(1), dim3(MM_TAB_PIECE), 0, st, ws, c);
-  }
+  sos_tab_upload(tab, ws, st);
   // a workgroup per row: one read + one write per sample.  Ragged rows only up to one round of segments: within a round the
   // workgroup's scan over segments is the wave-per-segment form's, operation for operation, and a ragged row equals the row
   // filtered alone (which takes that form) bit for bit; the carry into a second round is rounded differently
@@ -590,65 +552,9 @@ static int launch_sos_rows(const SosFilt& f, const SegSrc& src, int64_t rows, in
 
 static int launch_sos_rows_any(const SosFilt& f, const SegSrc& src, int64_t rows, int64_t n, double* d_y, double* ws,
                                hipStream_t st, const int64_t* lens = nullptr) {
-  if (lens)
-    return f.n_sec <= 2 ? launch_sos_rows<2, true>(f, src, rows, n, d_y, ws, st, lens)
-         : f.n_sec == 3 ? launch_sos_rows<3, true>(f, src, rows, n, d_y, ws, st, lens)
-                        : launch_sos_rows<4, true>(f, src, rows, n, d_y, ws, st, lens);
-  return f.n_sec <= 2 ? launch_sos_rows<2, false>(f, src, rows, n, d_y, ws, st, nullptr)
-       : f.n_sec == 3 ? launch_sos_rows<3, false>(f, src, rows, n, d_y, ws, st, nullptr)
-                      : launch_sos_rows<4, false>(f, src, rows, n, d_y, ws, st, nullptr);
-}
-
-// ---- the MFCC-change tail on the segmented rows: one long recording (the reference's own call: a whole file, tStep
-// 1 ms -> 10 001 frames per ten seconds) or a few long clips, where neither a workgroup per clip nor a lane per row
-// fills the chip.  rows filter (float32 MFCC rows in, float64 rows out) -> derivative + norm -> curve filter.
-__global__ __launch_bounds__(256) void chg_norm_rowmajor_kernel(const double* __restrict__ f, int64_t batch, int n_rows,
-                                                                int64_t T, int sg, double* __restrict__ out) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= batch * T) return;
-  const int64_t b = idx / T, t = idx - b * T;
-  const double* fr = f + b * n_rows * T;
-  double acc = 0.0;
-  if (t > 0 && t < T - 1) {
-#pragma unroll 4
-    for (int r = 0; r < n_rows; ++r) {
-      const double d = (fr[r * T + t + 1] - fr[r * T + t - 1]) / 2.0;
-      acc += d * d;
-    }
-  } else {
-    const int64_t e = t == 0 ? 0 : T - 3;                  // (T > padlen >= 6)
-    for (int r = 0; r < n_rows; ++r) {
-      const double x0 = fr[r * T + e], x1 = fr[r * T + e + 1], x2 = fr[r * T + e + 2];
-      const double d = t == 0 ? (sg ? (-3.0 * x0 + 4.0 * x1 - x2) / 2.0 : x1 - x0)
-                              : (sg ? (3.0 * x2 - 4.0 * x1 + x0) / 2.0 : x2 - x1);
-      acc += d * d;
-    }
-  }
-  out[idx] = sqrt(acc) / (double)n_rows;
-}
-
-// doubles: rows filter's workspace | filtered rows [R][T] | curve [B][T] | curve filter's workspace
-static size_t chg_seg_workspace_doubles(int64_t batch, int n_rows, int64_t T, int pad1, int pad2) {
-  return seg_workspace_doubles(batch * n_rows, T, pad1) + (size_t)(batch * n_rows * T) + (size_t)(batch * T) +
-         seg_workspace_doubles(batch, T, pad2);
-}
-
-static int launch_chg_segmented(const ChangeParams& q, const SosFilt& f1, const SosFilt& f2, double* ws, hipStream_t st) {
-  const int64_t R = q.batch * q.n_rows, T = q.n_frames;
-  double* ws1 = ws;
-  double* rows_out = ws1 + seg_workspace_doubles(R, T, f1.padlen);
-  double* curve = rows_out + R * T;
-  double* ws2 = curve + q.batch * T;
-  SegSrc s1 = {nullptr, 0, q.mfcc, q.n_mfcc, q.first_row, q.n_rows};
-  int rc = launch_sos_rows_any(f1, s1, R, T, rows_out, ws1, st);
-  if (rc) return rc;
-  if ((q.batch * T + 255) / 256 > 0x7FFFFFFF) return MM_ERR_INVALID_ARG;
-  double* norm_out = f2.n_sec > 0 ? curve : q.out;
-  hipLaunchKernelGGL(chg_norm_rowmajor_kernel, dim3((unsigned)((q.batch * T + 255) / 256)), dim3(256), 0, st, rows_out, q.batch,
-                     q.n_rows, T, q.sg, norm_out);
-  if (f2.n_sec > 0) {
-    SegSrc s2 = {curve, T, nullptr, 0, 0, 0};
-    rc = launch_sos_rows_any(f2, s2, q.batch, T, q.out, ws2, st);
-  }
-  return rc;
+  return with_scan_sections(f.n_sec, [&](auto ns) {
+    constexpr int NS = decltype(ns)::value;
+    return lens ? launch_sos_rows<NS, true>(f, src, rows, n, d_y, ws, st, lens)
+                : launch_sos_rows<NS, false>(f, src, rows, n, d_y, ws, st, nullptr);
+  });
 }

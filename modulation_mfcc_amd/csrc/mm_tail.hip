@@ -4,39 +4,12 @@
 #include "mm_common.h"
 #include "mm_plan.h"
 
-#include "mm_change.hip.inc"
-#include "mm_change_clip.hip.inc"
-#include "mm_sos_rows.hip.inc"
-
-extern "C" {
-
-// scipy.signal.sosfilt_zi + the padlen rule of sosfiltfilt, host side
-static int make_sosfilt(const double* sos, int n_sec, SosFilt* f) {
-  if (n_sec < 0 || n_sec > MM_MAX_SEC || (n_sec > 0 && !sos)) return MM_ERR_INVALID_ARG;
-  f->n_sec = n_sec;
-  f->padlen = 0;
-  if (n_sec == 0) return MM_OK;
-  double scale = 1.0;
-  int zb = 0, za = 0;
-  for (int s = 0; s < n_sec; ++s) {
-    const double* r = sos + 6 * s;
-    if (r[3] == 0.0) return MM_ERR_INVALID_ARG;
-    double b0 = r[0] / r[3], b1 = r[1] / r[3], b2 = r[2] / r[3], a1 = r[4] / r[3], a2 = r[5] / r[3];
-    f->c[s][0] = b0; f->c[s][1] = b1; f->c[s][2] = b2; f->c[s][3] = 1.0; f->c[s][4] = a1; f->c[s][5] = a2;
-    // lfilter_zi: (I - companion(a)^T) zi = b[1:] - a[1:] b0
-    const double B0 = b1 - a1 * b0, B1 = b2 - a2 * b0;
-    const double den = 1.0 + a1 + a2;
-    const double z0 = (B0 + B1) / den;
-    f->zi[s][0] = scale * z0;
-    f->zi[s][1] = scale * (B1 - a2 * z0);
-    scale *= (b0 + b1 + b2) / (1.0 + a1 + a2);
-    if (r[2] == 0.0) ++zb;
-    if (r[5] == 0.0) ++za;
-  }
-  const int ntaps = 2 * n_sec + 1 - (zb < za ? zb : za);
-  f->padlen = 3 * ntaps;
-  return MM_OK;
-}
+#include "mm_sos.hip.inc"           // the filter, the cascade step, the tables / lane scan / upload of the time-parallel forms
+#include "mm_sos_tm.hip.inc"        // sosfiltfilt on a time-major workspace (any section count)
+#include "mm_sos_rows.hip.inc"      // sosfiltfilt on segmented rows (up to MM_SCAN_MAX_SEC sections)
+#include "mm_change.hip.inc"        // the change tail: derivative + norm kernels, the segmented form
+#include "mm_change_clip.hip.inc"   // the change tail as one clip-resident launch
+#include "mm_stencil.hip.inc"       // the banded stencil
 
 static int change_pads(int n_sec1, const double* sos1, int n_sec2, const double* sos2, SosFilt* f1, SosFilt* f2) {
   int rc = make_sosfilt(sos1, n_sec1, f1);
@@ -47,20 +20,6 @@ static int change_pads(int n_sec1, const double* sos1, int n_sec2, const double*
 
 static int64_t round64(int64_t v) { return (v + 63) / 64 * 64; }
 
-// Upper bound over the three forms and every filter of up to MM_MAX_SEC sections (a caller that does not know its
-// filters yet); mm_change_workspace_bytes_for() sizes the form a given call takes.
-size_t mm_change_workspace_bytes(const mm_plan* p, int64_t batch, int64_t n_frames) {
-  if (!p || batch < 1 || n_frames < 1) return 0;
-  // two time-major buffers [T + 2 pad][columns padded to 64]; worst-case padding 3 * (2 * MM_MAX_SEC + 1)
-  const int64_t padmax = 3 * (2 * MM_MAX_SEC + 1);
-  const int64_t n = n_frames + 2 * padmax;
-  const size_t tm = (size_t)n * (size_t)(round64(batch * p->cfg.n_mfcc) + round64(batch));
-  // ... or the segmented rows' buffers (mm_sos_rows.hip.inc), whichever is larger
-  const int pads = 3 * (2 * MM_CLIP_NS + 1);
-  const size_t sg = chg_seg_workspace_doubles(batch, p->cfg.n_mfcc, n_frames, pads, pads);
-  return std::max(tm, sg) * sizeof(double);
-}
-
 // Which of the three device forms a change-tail call takes, and the workspace (in doubles) THAT form needs -- one
 // routine for the size query and for the call, so the two cannot disagree.
 enum { MM_CHG_TIME_MAJOR = 0, MM_CHG_CLIP = 1, MM_CHG_SEGMENTED = 2 };
@@ -70,7 +29,7 @@ static ChgForm change_form(const mm_plan* p, int64_t batch, int64_t n_frames, in
   const int64_t p1 = f1.padlen, p2 = f2.n_sec > 0 ? f2.padlen : 0;
   const int64_t n1 = n_frames + 2 * p1, n2 = n_frames + 2 * p2;
   r.cs = clip_shape(n_rows, n1, n2);
-  const bool small_sec = f1.n_sec <= MM_CLIP_NS && f2.n_sec <= MM_CLIP_NS;
+  const bool small_sec = f1.n_sec <= MM_SCAN_MAX_SEC && f2.n_sec <= MM_SCAN_MAX_SEC;
   // Long clips (one recording at a 1 ms step is 10 001 frames per ten seconds): the clip form holds fewer and fewer rows
   // at once and walks its groups one after the other -- from five groups on (about 5000 frames at 12 rows) a wave per
   // 1088 samples of a row (mm_sos_rows.hip.inc) is faster at every clip count (tools/chg_forms.py: 8001 frames 0.80 ms
@@ -92,6 +51,100 @@ static ChgForm change_form(const mm_plan* p, int64_t batch, int64_t n_frames, in
   return r;
 }
 
+// ---- ragged batches: one frame count per clip (include/modmfcc.h; DESIGN.md 12) ----
+// The clip-resident kernel alone, shaped for the longest clip: chunk tables, K1 / K2, row groups and LDS follow from
+// n_frames_max, a workgroup reads its own length.  No other form: more than MM_SCAN_MAX_SEC sections or a clip whose single row
+// does not fit LDS is MM_ERR_UNSUPPORTED, whatever mm_plan_set_fuse_tail() says.
+static bool change_ragged_shape(int n_rows, int64_t n_frames_max, const SosFilt& f1, const SosFilt& f2, ClipShape* cs) {
+  const int64_t p1 = f1.padlen, p2 = f2.n_sec > 0 ? f2.padlen : 0;
+  *cs = clip_shape(n_rows, n_frames_max + 2 * p1, n_frames_max + 2 * p2);
+  return f1.n_sec <= MM_SCAN_MAX_SEC && f2.n_sec <= MM_SCAN_MAX_SEC && cs->G >= 1;
+}
+
+// Both change entries: the arguments checked, the two filters made and ChangeParams filled for batch clips of n_frames
+// (ragged: the longest clip's); q.ws2 is left to the time-major form
+static int change_setup(const mm_plan* p, const float* d_mfcc, int64_t batch, int64_t n_frames, int32_t remove_first,
+                        int32_t diff_method, const double* sos1, int32_t n_sec1, const double* sos2, int32_t n_sec2,
+                        double* d_change, void* d_ws, SosFilt* f1, SosFilt* f2, ChangeParams* q) {
+  if (!p || !d_mfcc || !d_change || !d_ws || batch < 1 || n_frames < 1) return MM_ERR_INVALID_ARG;
+  if (diff_method < 0 || diff_method > 1 || (diff_method == 1 && n_frames < 3)) return MM_ERR_INVALID_ARG;
+  if (remove_first < 0 || remove_first >= p->cfg.n_mfcc) return MM_ERR_INVALID_ARG;
+  if (batch > 0x7FFFFFFF) return MM_ERR_INVALID_ARG;
+  const int rc = change_pads(n_sec1, sos1, n_sec2, sos2, f1, f2);
+  if (rc) return rc;
+  // scipy: "The length of the input vector x must be greater than padlen" (ragged: what the host can know -- not even
+  // the longest clip is one scipy takes; a shorter one comes out NaN, on the device)
+  if (n_frames <= f1->padlen || n_frames <= f2->padlen) return MM_ERR_INVALID_ARG;
+  q->mfcc = d_mfcc; q->n_frames = n_frames; q->batch = batch; q->n_mfcc = p->cfg.n_mfcc;
+  q->first_row = remove_first ? 1 : 0; q->n_rows = q->n_mfcc - q->first_row;
+  q->p1 = f1->padlen; q->p2 = f2->n_sec > 0 ? f2->padlen : 0; q->sg = diff_method;
+  q->R = batch * q->n_rows; q->Rp = round64(q->R); q->Bp = round64(batch);
+  q->ws1 = (double*)d_ws; q->ws2 = nullptr; q->out = d_change;
+  return MM_OK;
+}
+
+static size_t sosfiltfilt_workspace_doubles(int64_t rows, int64_t n, bool ragged) {
+  const size_t sg = seg_workspace_doubles(rows, n, 3 * (2 * MM_SCAN_MAX_SEC + 1));
+  if (ragged) return sg;                                  // the segmented rows only
+  // the larger of the two device forms: time-major [n + 2 pad][rows padded to 64] | segmented rows (mm_sos_rows.hip.inc)
+  return std::max((size_t)(n + 2 * 3 * (2 * MM_MAX_SEC + 1)) * (size_t)round64(rows), sg);
+}
+
+// d_x (float64 rows) or d_xf (float32 rows: odd extension in float32 arithmetic, see odd_ext_f32)
+// d_lens (DEVICE int64 [rows], or null): the ragged form, n the longest row's length
+static int sosfiltfilt_impl(const double* d_x, const float* d_xf, int64_t rows, int64_t n, int64_t x_stride, const int64_t* d_lens,
+                            const double* sos, int32_t n_sec, double* d_y, void* d_ws, size_t ws_bytes, void* stream) {
+  if ((!d_x && !d_xf) || !d_y || !d_ws || rows < 1 || n < 1 || x_stride < n || n_sec < 1) return MM_ERR_INVALID_ARG;
+  SosFilt f;
+  int rc = make_sosfilt(sos, n_sec, &f);
+  if (rc) return rc;
+  if (d_lens && f.n_sec > MM_SCAN_MAX_SEC) return MM_ERR_UNSUPPORTED;    // the time-major kernels stay single-length
+  // scipy: "The length of the input vector x must be greater than padlen" (ragged: what the host can know -- not even
+  // the longest row is one scipy takes; a shorter one comes out NaN, on the device)
+  if (n <= f.padlen) return MM_ERR_INVALID_ARG;
+  if (ws_bytes < sosfiltfilt_workspace_doubles(rows, n, d_lens != nullptr) * sizeof(double)) return MM_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  if (f.n_sec <= MM_SCAN_MAX_SEC) {     // segmented rows: a wave per 1088 samples of a row, any length
+    const SegSrc src = {d_x, x_stride, d_xf, 0, 0, 0};
+    rc = launch_sos_rows_any(f, src, rows, n, d_y, (double*)d_ws, st, d_lens);
+    if (rc) return rc;
+    HIP_TRY(hipGetLastError());
+    return MM_OK;
+  }
+  const int64_t Wp = round64(rows), tb = (n + 63) / 64;
+  if (tb > 65535 || Wp / 64 > 0x7FFFFFFF || 2 * (int64_t)f.padlen * Wp / 256 + 1 > 0x7FFFFFFF) return MM_ERR_INVALID_ARG;
+  double* ws = (double*)d_ws;
+  const dim3 grid((unsigned)(Wp / 64), (unsigned)tb);
+  if (d_xf)
+    hipLaunchKernelGGL((tm_pack_kernel<PlainRows<float>>), grid, dim3(256), 0, st, PlainRows<float>{d_xf, x_stride}, rows, n,
+                       f.padlen, Wp, ws);
+  else
+    hipLaunchKernelGGL((tm_pack_kernel<PlainRows<double>>), grid, dim3(256), 0, st, PlainRows<double>{d_x, x_stride}, rows, n,
+                       f.padlen, Wp, ws);
+  hipLaunchKernelGGL(chg_pad_kernel, dim3((unsigned)((2 * (int64_t)f.padlen * Wp + 255) / 256)), dim3(256), 0, st, ws, n,
+                     f.padlen, Wp, d_xf ? 1 : 0);
+  launch_sos_any(f, ws, n + 2 * f.padlen, Wp, st);
+  hipLaunchKernelGGL(tm_unpack_kernel, grid, dim3(256), 0, st, ws, rows, n, f.padlen, Wp, d_y);
+  HIP_TRY(hipGetLastError());
+  return MM_OK;
+}
+
+extern "C" {
+
+// Upper bound over the three forms and every filter of up to MM_MAX_SEC sections (a caller that does not know its
+// filters yet); mm_change_workspace_bytes_for() sizes the form a given call takes.
+size_t mm_change_workspace_bytes(const mm_plan* p, int64_t batch, int64_t n_frames) {
+  if (!p || batch < 1 || n_frames < 1) return 0;
+  // two time-major buffers [T + 2 pad][columns padded to 64]; worst-case padding 3 * (2 * MM_MAX_SEC + 1)
+  const int64_t padmax = 3 * (2 * MM_MAX_SEC + 1);
+  const int64_t n = n_frames + 2 * padmax;
+  const size_t tm = (size_t)n * (size_t)(round64(batch * p->cfg.n_mfcc) + round64(batch));
+  // ... or the segmented rows' buffers (mm_sos_rows.hip.inc), whichever is larger
+  const int pads = 3 * (2 * MM_SCAN_MAX_SEC + 1);
+  const size_t sg = chg_seg_workspace_doubles(batch, p->cfg.n_mfcc, n_frames, pads, pads);
+  return std::max(tm, sg) * sizeof(double);
+}
+
 size_t mm_change_workspace_bytes_for(const mm_plan* p, int64_t batch, int64_t n_frames, int32_t remove_first, const double* sos1,
                                      int32_t n_sec1, const double* sos2, int32_t n_sec2) {
   if (!p || batch < 1 || n_frames < 1 || remove_first < 0 || remove_first >= p->cfg.n_mfcc) return 0;
@@ -104,25 +157,15 @@ size_t mm_change_workspace_bytes_for(const mm_plan* p, int64_t batch, int64_t n_
 int mm_mfcc_change_f64(mm_plan* p, const float* d_mfcc, int64_t batch, int64_t n_frames,
                        int32_t remove_first, int32_t diff_method, const double* sos1, int32_t n_sec1, const double* sos2,
                        int32_t n_sec2, double* d_change, void* d_ws, size_t ws_bytes, void* stream) {
-  if (!p || !d_mfcc || !d_change || !d_ws || batch < 1 || n_frames < 1) return MM_ERR_INVALID_ARG;
-  if (diff_method < 0 || diff_method > 1 || (diff_method == 1 && n_frames < 3)) return MM_ERR_INVALID_ARG;
-  if (remove_first < 0 || remove_first >= p->cfg.n_mfcc) return MM_ERR_INVALID_ARG;
-  if (batch > 0x7FFFFFFF) return MM_ERR_INVALID_ARG;
   SosFilt f1, f2;
-  int rc = change_pads(n_sec1, sos1, n_sec2, sos2, &f1, &f2);
-  if (rc) return rc;
-  // scipy: "The length of the input vector x must be greater than padlen"
-  if (n_frames <= f1.padlen || n_frames <= f2.padlen) return MM_ERR_INVALID_ARG;
   ChangeParams q;
-  q.mfcc = d_mfcc; q.n_frames = n_frames; q.batch = batch; q.n_mfcc = p->cfg.n_mfcc;
-  q.first_row = remove_first ? 1 : 0; q.n_rows = q.n_mfcc - q.first_row;
-  q.p1 = f1.padlen; q.p2 = f2.n_sec > 0 ? f2.padlen : 0; q.sg = diff_method;
-  q.R = batch * q.n_rows; q.Rp = round64(q.R); q.Bp = round64(batch);
+  int rc = change_setup(p, d_mfcc, batch, n_frames, remove_first, diff_method, sos1, n_sec1, sos2, n_sec2, d_change, d_ws, &f1, &f2, &q);
+  if (rc) return rc;
   const int64_t n1 = n_frames + 2 * q.p1, n2 = n_frames + 2 * q.p2;
   // the workspace of the form that runs (mm_change_workspace_bytes_for); mm_change_workspace_bytes is the bound over all forms
   const ChgForm cf = change_form(p, batch, n_frames, q.n_rows, f1, f2);
   if (ws_bytes < cf.need * sizeof(double)) return MM_ERR_WORKSPACE;
-  q.ws1 = (double*)d_ws; q.ws2 = q.ws1 + n1 * q.Rp; q.out = d_change;
+  q.ws2 = q.ws1 + n1 * q.Rp;
   const int64_t tblocks = (n_frames + 63) / 64;
   if (tblocks > 65535 || 2 * (int64_t)q.p1 * q.Rp / 256 + 1 > 0x7FFFFFFF || n_frames * q.Bp / 256 + 1 > 0x7FFFFFFF ||
       q.Bp / 64 > 65535 || n_frames > 0x7FFFFFFF)
@@ -136,16 +179,16 @@ int mm_mfcc_change_f64(mm_plan* p, const float* d_mfcc, int64_t batch, int64_t n
     return MM_OK;
   }
   if (cf.form == MM_CHG_CLIP) {            // mm_change_clip.hip.inc: one launch, no workspace traffic
-    const ClipShape& cs = cf.cs;
-    const int ns = std::max(f1.n_sec, f2.n_sec);
-    rc = ns <= 2 ? launch_chg_clip<2>(q, f1, f2, cs, n1, n2, q.ws1, st)
-       : ns == 3 ? launch_chg_clip<3>(q, f1, f2, cs, n1, n2, q.ws1, st)
-                 : launch_chg_clip<4>(q, f1, f2, cs, n1, n2, q.ws1, st);
+    rc = with_scan_sections(std::max(f1.n_sec, f2.n_sec), [&](auto ns) {
+      return launch_chg_clip<decltype(ns)::value>(q, f1, f2, cf.cs, n1, n2, q.ws1, st);
+    });
     if (rc) return rc;
     HIP_TRY(hipGetLastError());
     return MM_OK;
   }
-  hipLaunchKernelGGL(chg_pack_kernel, dim3((unsigned)(q.Rp / 64), (unsigned)tblocks), dim3(256), 0, st, q);
+  const dim3 rows_grid((unsigned)(q.Rp / 64), (unsigned)tblocks), curve_grid((unsigned)(q.Bp / 64), (unsigned)tblocks);
+  hipLaunchKernelGGL(tm_pack_kernel<MfccRows>, rows_grid, dim3(256), 0, st,
+                     MfccRows{q.mfcc, q.n_mfcc, q.first_row, q.n_rows, n_frames}, q.R, n_frames, q.p1, q.Rp, q.ws1);
   hipLaunchKernelGGL(chg_pad_kernel, dim3((unsigned)((2 * (int64_t)q.p1 * q.Rp + 255) / 256)), dim3(256), 0, st,
                      q.ws1, n_frames, q.p1, q.Rp, 1);
   launch_sos_any(f1, q.ws1, n1, q.Rp, st);
@@ -158,19 +201,9 @@ int mm_mfcc_change_f64(mm_plan* p, const float* d_mfcc, int64_t batch, int64_t n
                        q.ws2, n_frames, q.p2, q.Bp, 0);
     launch_sos_any(f2, q.ws2, n2, q.Bp, st);
   }
-  hipLaunchKernelGGL(chg_unpack_kernel, dim3((unsigned)(q.Bp / 64), (unsigned)tblocks), dim3(256), 0, st, q);
+  hipLaunchKernelGGL(tm_unpack_kernel, curve_grid, dim3(256), 0, st, q.ws2, batch, n_frames, q.p2, q.Bp, q.out);
   HIP_TRY(hipGetLastError());
   return MM_OK;
-}
-
-// ---- ragged batches: one frame count per clip (include/modmfcc.h; DESIGN.md 12) ----
-// The clip-resident kernel alone, shaped for the longest clip: chunk tables, K1 / K2, row groups and LDS follow from
-// n_frames_max, a workgroup reads its own length.  No other form: more than MM_CLIP_NS sections or a clip whose single row
-// does not fit LDS is MM_ERR_UNSUPPORTED, whatever mm_plan_set_fuse_tail() says.
-static bool change_ragged_shape(int n_rows, int64_t n_frames_max, const SosFilt& f1, const SosFilt& f2, ClipShape* cs) {
-  const int64_t p1 = f1.padlen, p2 = f2.n_sec > 0 ? f2.padlen : 0;
-  *cs = clip_shape(n_rows, n_frames_max + 2 * p1, n_frames_max + 2 * p2);
-  return f1.n_sec <= MM_CLIP_NS && f2.n_sec <= MM_CLIP_NS && cs->G >= 1;
 }
 
 size_t mm_change_ragged_workspace_bytes_for(const mm_plan* p, int64_t batch, int64_t n_frames_max, int32_t remove_first,
@@ -188,113 +221,39 @@ size_t mm_change_ragged_workspace_bytes_for(const mm_plan* p, int64_t batch, int
 int mm_mfcc_change_ragged_f64(mm_plan* p, const float* d_mfcc, int64_t batch, int64_t n_frames_max, const int64_t* d_frames,
                               int32_t remove_first, int32_t diff_method, const double* sos1, int32_t n_sec1,
                               const double* sos2, int32_t n_sec2, double* d_change, void* d_ws, size_t ws_bytes, void* stream) {
-  if (!p || !d_mfcc || !d_frames || !d_change || !d_ws || batch < 1 || n_frames_max < 1) return MM_ERR_INVALID_ARG;
-  if (diff_method < 0 || diff_method > 1 || (diff_method == 1 && n_frames_max < 3)) return MM_ERR_INVALID_ARG;
-  if (remove_first < 0 || remove_first >= p->cfg.n_mfcc) return MM_ERR_INVALID_ARG;
-  if (batch > 0x7FFFFFFF || n_frames_max > 0x7FFFFFFF) return MM_ERR_INVALID_ARG;
+  if (!d_frames || n_frames_max > 0x7FFFFFFF) return MM_ERR_INVALID_ARG;
   SosFilt f1, f2;
-  int rc = change_pads(n_sec1, sos1, n_sec2, sos2, &f1, &f2);
-  if (rc) return rc;
-  // what the host can know: not even the longest clip is one scipy takes (a shorter one comes out NaN, on the device)
-  if (n_frames_max <= f1.padlen || n_frames_max <= f2.padlen) return MM_ERR_INVALID_ARG;
   ChangeParams q;
-  q.mfcc = d_mfcc; q.n_frames = n_frames_max; q.batch = batch; q.n_mfcc = p->cfg.n_mfcc;
-  q.first_row = remove_first ? 1 : 0; q.n_rows = q.n_mfcc - q.first_row;
-  q.p1 = f1.padlen; q.p2 = f2.n_sec > 0 ? f2.padlen : 0; q.sg = diff_method;
-  q.R = batch * q.n_rows; q.Rp = round64(q.R); q.Bp = round64(batch);
-  q.ws1 = (double*)d_ws; q.ws2 = nullptr; q.out = d_change;
+  int rc = change_setup(p, d_mfcc, batch, n_frames_max, remove_first, diff_method, sos1, n_sec1, sos2, n_sec2, d_change, d_ws, &f1, &f2, &q);
+  if (rc) return rc;
   ClipShape cs;
   if (!change_ragged_shape(q.n_rows, n_frames_max, f1, f2, &cs)) return MM_ERR_UNSUPPORTED;
   if (ws_bytes < (size_t)cs.tab_n * sizeof(double)) return MM_ERR_WORKSPACE;
   const int64_t n1 = n_frames_max + 2 * q.p1, n2 = n_frames_max + 2 * q.p2;
   hipStream_t st = (hipStream_t)stream;
   StageTimer tm(p, MM_STAGE_CHANGE, st);
-  const int ns = std::max(f1.n_sec, f2.n_sec);
-  rc = ns <= 2 ? launch_chg_clip<2, true>(q, f1, f2, cs, n1, n2, q.ws1, st, d_frames)
-     : ns == 3 ? launch_chg_clip<3, true>(q, f1, f2, cs, n1, n2, q.ws1, st, d_frames)
-               : launch_chg_clip<4, true>(q, f1, f2, cs, n1, n2, q.ws1, st, d_frames);
+  rc = with_scan_sections(std::max(f1.n_sec, f2.n_sec), [&](auto ns) {
+    return launch_chg_clip<decltype(ns)::value, true>(q, f1, f2, cs, n1, n2, q.ws1, st, d_frames);
+  });
   if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return MM_OK;
 }
 
 size_t mm_sosfiltfilt_workspace_bytes(int64_t rows, int64_t n) {
-  if (rows < 1 || n < 1) return 0;
-  // the larger of the two device forms: time-major [n + 2 pad][rows padded to 64] | segmented rows (mm_sos_rows.hip.inc)
-  const size_t tm = (size_t)(n + 2 * 3 * (2 * MM_MAX_SEC + 1)) * (size_t)round64(rows);
-  const size_t sg = seg_workspace_doubles(rows, n, 3 * (2 * MM_CLIP_NS + 1));
-  return std::max(tm, sg) * sizeof(double);
-}
-
-// d_x (float64 rows) or d_xf (float32 rows: odd extension in float32 arithmetic, see odd_ext_f32)
-static int sosfiltfilt_impl(const double* d_x, const float* d_xf, int64_t rows, int64_t n, int64_t x_stride, const double* sos,
-                            int32_t n_sec, double* d_y, void* d_ws, size_t ws_bytes, void* stream) {
-  if ((!d_x && !d_xf) || !d_y || !d_ws || rows < 1 || n < 1 || x_stride < n || n_sec < 1) return MM_ERR_INVALID_ARG;
-  SosFilt f;
-  int rc = make_sosfilt(sos, n_sec, &f);
-  if (rc) return rc;
-  if (n <= f.padlen) return MM_ERR_INVALID_ARG;      // scipy: "The length of the input vector x must be greater than padlen"
-  if (ws_bytes < mm_sosfiltfilt_workspace_bytes(rows, n)) return MM_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  if (f.n_sec <= MM_CLIP_NS) {     // segmented rows: a wave per 1088 samples of a row, any length
-    const SegSrc src = {d_x, x_stride, d_xf, 0, 0, 0};
-    rc = launch_sos_rows_any(f, src, rows, n, d_y, (double*)d_ws, st);
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    return MM_OK;
-  }
-  const int64_t Wp = round64(rows), tb = (n + 63) / 64;
-  if (tb > 65535 || Wp / 64 > 0x7FFFFFFF || 2 * (int64_t)f.padlen * Wp / 256 + 1 > 0x7FFFFFFF) return MM_ERR_INVALID_ARG;
-  double* ws = (double*)d_ws;
-  if (d_xf)
-    hipLaunchKernelGGL((sos_rows_pack_kernel<float>), dim3((unsigned)(Wp / 64), (unsigned)tb), dim3(256), 0, st, d_xf, rows, n,
-                       x_stride, f.padlen, Wp, ws);
-  else
-    hipLaunchKernelGGL((sos_rows_pack_kernel<double>), dim3((unsigned)(Wp / 64), (unsigned)tb), dim3(256), 0, st, d_x, rows, n,
-                       x_stride, f.padlen, Wp, ws);
-  hipLaunchKernelGGL(chg_pad_kernel, dim3((unsigned)((2 * (int64_t)f.padlen * Wp + 255) / 256)), dim3(256), 0, st, ws, n,
-                     f.padlen, Wp, d_xf ? 1 : 0);
-  launch_sos_any(f, ws, n + 2 * f.padlen, Wp, st);
-  hipLaunchKernelGGL(sos_rows_unpack_kernel, dim3((unsigned)(Wp / 64), (unsigned)tb), dim3(256), 0, st, ws, rows, n, f.padlen,
-                     Wp, d_y);
-  HIP_TRY(hipGetLastError());
-  return MM_OK;
+  return rows < 1 || n < 1 ? 0 : sosfiltfilt_workspace_doubles(rows, n, false) * sizeof(double);
 }
 
 int mm_sosfiltfilt_f64(const double* d_x, int64_t rows, int64_t n, int64_t x_stride, const double* sos, int32_t n_sec,
                        double* d_y, void* d_ws, size_t ws_bytes, void* stream) {
   if (!d_x) return MM_ERR_INVALID_ARG;
-  return sosfiltfilt_impl(d_x, nullptr, rows, n, x_stride, sos, n_sec, d_y, d_ws, ws_bytes, stream);
+  return sosfiltfilt_impl(d_x, nullptr, rows, n, x_stride, nullptr, sos, n_sec, d_y, d_ws, ws_bytes, stream);
 }
 
 int mm_sosfiltfilt_f32_f64(const float* d_x, int64_t rows, int64_t n, int64_t x_stride, const double* sos, int32_t n_sec,
                            double* d_y, void* d_ws, size_t ws_bytes, void* stream) {
   if (!d_x) return MM_ERR_INVALID_ARG;
-  return sosfiltfilt_impl(nullptr, d_x, rows, n, x_stride, sos, n_sec, d_y, d_ws, ws_bytes, stream);
-}
-
-// d_lens (DEVICE int64 [rows], or null): the ragged form, n the longest row's length
-static int stencil_impl(const mm_stencil* st, const double* d_x, int64_t rows, int64_t n, int64_t x_stride,
-                        const int64_t* d_lens, double* d_y, void* stream) {
-  if (!st || !d_x || !d_y || rows < 1 || n < 1 || x_stride < n) return MM_ERR_INVALID_ARG;
-  if (st->n_c < 1 || st->n_c > MM_ST_MAXW || st->n_edge < 0 || st->n_edge > MM_ST_MAXE || st->edge_w < 0 ||
-      st->edge_w > MM_ST_MAXW || (st->n_edge > 0 && st->edge_w < 1) || st->den_c == 0.0 ||
-      (st->n_edge > 0 && st->den_e == 0.0))
-    return MM_ERR_INVALID_ARG;
-  int lo = 0, hi = 0;
-  for (int k = 0; k < st->n_c; ++k) { lo = std::min(lo, st->off[k]); hi = std::max(hi, st->off[k]); }
-  // every interior output must find its taps inside the row, the edge rows their inputs
-  if (n < 2 * (int64_t)st->n_edge || n < st->edge_w || -lo > st->n_edge || hi > st->n_edge) return MM_ERR_INVALID_ARG;
-  const int64_t total = rows * n;
-  if ((total + 255) / 256 > 0x7FFFFFFF) return MM_ERR_INVALID_ARG;
-  if (d_lens)
-    hipLaunchKernelGGL(stencil_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *st,
-                       d_x, rows, n, x_stride, d_lens, d_y);
-  else
-    hipLaunchKernelGGL(stencil_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *st,
-                       d_x, rows, n, x_stride, d_lens, d_y);
-  HIP_TRY(hipGetLastError());
-  return MM_OK;
+  return sosfiltfilt_impl(nullptr, d_x, rows, n, x_stride, nullptr, sos, n_sec, d_y, d_ws, ws_bytes, stream);
 }
 
 int mm_stencil_f64(const mm_stencil* st, const double* d_x, int64_t rows, int64_t n, int64_t x_stride, double* d_y,
@@ -309,39 +268,19 @@ int mm_stencil_ragged_f64(const mm_stencil* st, const double* d_x, int64_t rows,
 }
 
 size_t mm_sosfiltfilt_ragged_workspace_bytes(int64_t rows, int64_t n_max) {
-  if (rows < 1 || n_max < 1) return 0;
-  return seg_workspace_doubles(rows, n_max, 3 * (2 * MM_CLIP_NS + 1)) * sizeof(double);   // the segmented rows only
-}
-
-static int sosfiltfilt_ragged_impl(const double* d_x, const float* d_xf, int64_t rows, int64_t n_max, int64_t x_stride,
-                                   const int64_t* d_lens, const double* sos, int32_t n_sec, double* d_y, void* d_ws,
-                                   size_t ws_bytes, void* stream) {
-  if ((!d_x && !d_xf) || !d_lens || !d_y || !d_ws || rows < 1 || n_max < 1 || x_stride < n_max || n_sec < 1)
-    return MM_ERR_INVALID_ARG;
-  SosFilt f;
-  int rc = make_sosfilt(sos, n_sec, &f);
-  if (rc) return rc;
-  if (f.n_sec > MM_CLIP_NS) return MM_ERR_UNSUPPORTED;    // the time-major kernels stay single-length
-  // what the host can know: not even the longest row is one scipy takes (a shorter one comes out NaN, on the device)
-  if (n_max <= f.padlen) return MM_ERR_INVALID_ARG;
-  if (ws_bytes < mm_sosfiltfilt_ragged_workspace_bytes(rows, n_max)) return MM_ERR_WORKSPACE;
-  const SegSrc src = {d_x, x_stride, d_xf, 0, 0, 0};
-  rc = launch_sos_rows_any(f, src, rows, n_max, d_y, (double*)d_ws, (hipStream_t)stream, d_lens);
-  if (rc) return rc;
-  HIP_TRY(hipGetLastError());
-  return MM_OK;
+  return rows < 1 || n_max < 1 ? 0 : sosfiltfilt_workspace_doubles(rows, n_max, true) * sizeof(double);
 }
 
 int mm_sosfiltfilt_ragged_f64(const double* d_x, int64_t rows, int64_t n_max, int64_t x_stride, const int64_t* d_lens,
                               const double* sos, int32_t n_sec, double* d_y, void* d_ws, size_t ws_bytes, void* stream) {
-  if (!d_x) return MM_ERR_INVALID_ARG;
-  return sosfiltfilt_ragged_impl(d_x, nullptr, rows, n_max, x_stride, d_lens, sos, n_sec, d_y, d_ws, ws_bytes, stream);
+  if (!d_x || !d_lens) return MM_ERR_INVALID_ARG;
+  return sosfiltfilt_impl(d_x, nullptr, rows, n_max, x_stride, d_lens, sos, n_sec, d_y, d_ws, ws_bytes, stream);
 }
 
 int mm_sosfiltfilt_ragged_f32_f64(const float* d_x, int64_t rows, int64_t n_max, int64_t x_stride, const int64_t* d_lens,
                                   const double* sos, int32_t n_sec, double* d_y, void* d_ws, size_t ws_bytes, void* stream) {
-  if (!d_x) return MM_ERR_INVALID_ARG;
-  return sosfiltfilt_ragged_impl(nullptr, d_x, rows, n_max, x_stride, d_lens, sos, n_sec, d_y, d_ws, ws_bytes, stream);
+  if (!d_x || !d_lens) return MM_ERR_INVALID_ARG;
+  return sosfiltfilt_impl(nullptr, d_x, rows, n_max, x_stride, d_lens, sos, n_sec, d_y, d_ws, ws_bytes, stream);
 }
 
 }  // extern "C"

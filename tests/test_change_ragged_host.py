@@ -28,7 +28,7 @@ def test_symbols_are_exported_and_prototyped():
 
 def test_c_entry_rejects_a_null_plan_and_null_pointers():
     lib = _lib.load()
-    buf = np.zeros(64, dtype=np.float64)          # never dereferenced: the plan is checked first
+    buf = np.zeros(64, dtype=np.float64)          # never dereferenced: the plan is checked before any pointer is used
     fr = np.ones(1, dtype=np.int64)
     p, s = buf.ctypes.data, SOS.ctypes.data
     f = lib.mm_mfcc_change_ragged_f64

@@ -38,7 +38,7 @@ workgroup per row; butter(10, .) is five sections: the time-major kernels at bot
     butter10_12Hz@16k            5       4.02e-12      1.47e-12   0.37        1.47e-12   0.37
 
 Worst ratio 3.28 (butter(8, 5.4e-4)); R = 4 x 3.28 = 13.1, rounded up to a power of two: 16.  Before the scan tables were
-built in extended precision (mm_change_clip.hip.inc, sos_scan_tables) the same sweep gave ratios of 55 - 2700 and
+built in extended precision (mm_sos.hip.inc, sos_scan_tables) the same sweep gave ratios of 55 - 2700 and
 E_dev = 6.5e-9 - 2.9e-8 at 12 Hz on 44.1 / 48 kHz.
 """
 import contextlib

@@ -6,7 +6,8 @@ one process per library; two files are then compared bit for bit (a schedule mov
     python tools/lib_outputs.py --compare parent.npz branch.npz
 
 Case set `s16`: the smallest shapes that reach each code path of the staged n_fft-512 kernel (logmel512s_kernel) and the
-matrix-pipe kernel.  n_fft 512, 16 kHz, win 400, 40 mel / 13 MFCC unless said otherwise."""
+matrix-pipe kernel.  n_fft 512, 16 kHz, win 400, 40 mel / 13 MFCC unless said otherwise.
+Case set `tail`: every kernel of mm_tail.hip and its includes (tail_cases)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -110,7 +111,101 @@ def s16_cases():
     return out
 
 
-CASESETS = {"s16": s16_cases}
+def tail_cases():
+    """Case set `tail`: every kernel of mm_tail.hip (sosfiltfilt on curves, the MFCC-change tail in its three forms and its
+    ragged form, the banded stencil) at the smallest shape that reaches it."""
+    import torch
+    import scipy.signal
+    from modulation_mfcc_amd import MfccConfig, MfccPlan, tail
+    from modulation_mfcc_amd.calc import apply_stencil, apply_stencil_ragged, velocity_stencil
+    from modulation_mfcc_amd.filters import fir_filtfilt_stencil, sosfiltfilt_batch, sosfiltfilt_ragged_batch
+    dev = torch.device("cuda", 0)
+    out = {}
+    SEG = 1088                                  # MM_SEG_LEN: samples per segment of the segmented rows
+
+    def keep(name, t):
+        out[name] = t.cpu().numpy()
+
+    def curves(seed, rows, n, dtype=np.float64):
+        return torch.from_numpy(np.random.default_rng(seed).standard_normal((rows, n)).cumsum(axis=1).astype(dtype)).to(dev)
+
+    # sosfiltfilt_batch.  1 - 4 sections: the segmented rows (instantiations 2 / 2 / 3 / 4), 3 rows a wave per segment, 130
+    # (MM_ROW_MIN is 128) a workgroup per row; 5, 8, 16 sections: the time-major kernels (instantiations 6 / 8 / 16; the
+    # sequential one -- the chunked form stops at 4 sections).  Lengths: padlen + 1, one segment exactly, one more, ~3000
+    for ns in (1, 2, 3, 4, 5, 8, 16):
+        sos = scipy.signal.butter(2 * ns, 0.2, output="sos")
+        pad = 3 * (2 * ns + 1)
+        for rows in (3, 130):
+            for n in (pad + 1, SEG - 2 * pad, SEG - 2 * pad + 1, 3001):
+                keep("sos.ns%d.r%d.n%d" % (ns, rows, n), sosfiltfilt_batch(curves(ns + n, rows, n), sos))
+    sos = scipy.signal.butter(6, 0.05, output="sos")
+    pad = 21
+    # 18 501 samples are more than 16 segments: the row stream takes a second round
+    keep("sos.long.r130", sosfiltfilt_batch(curves(1, 130, 18501), sos))
+    keep("sos.long.r3", sosfiltfilt_batch(curves(2, 3, 18501), sos))
+    for rows in (3, 130):                       # float32 rows, and a strided batch (every other row of a wider buffer)
+        keep("sos.f32.r%d" % rows, sosfiltfilt_batch(curves(3, rows, 3001, np.float32), sos))
+        keep("sos.strided.r%d" % rows, sosfiltfilt_batch(curves(4, rows, 2 * 3100)[:, 50:3051], sos))
+    keep("sos.f32.ns5", sosfiltfilt_batch(curves(5, 3, 3001, np.float32), scipy.signal.butter(10, 0.2, output="sos")))
+    # sosfiltfilt_ragged_batch: device lengths 1, padlen (refused: a NaN row), padlen + 1, a segment boundary, n_max
+    for rows in (3, 130):
+        n_max = 3 * SEG + 7
+        lens = np.random.default_rng(rows).integers(pad + 1, n_max + 1, rows)
+        lens[:3] = (1, SEG - 2 * pad, n_max)
+        if rows > 3:
+            lens[3:7] = (pad, pad + 1, SEG - 2 * pad + 1, 2 * SEG - 2 * pad)
+        else:
+            keep("sosrag.short.r3", sosfiltfilt_ragged_batch(curves(6, 3, n_max), torch.tensor([pad, pad + 1, 2 * SEG - 2 * pad], device=dev), sos))
+        ld = torch.from_numpy(lens.astype(np.int64)).to(dev)
+        for dt in (np.float64, np.float32):
+            keep("sosrag.r%d.%s" % (rows, np.dtype(dt).name), sosfiltfilt_ragged_batch(curves(7, rows, n_max, dt), ld, sos))
+        for ns in (2, 4):                       # (the lengths of this batch suit every padlen up to 21: four sections pad 27)
+            s_ns = scipy.signal.butter(2 * ns, 0.05, output="sos")
+            keep("sosrag.r%d.ns%d" % (rows, ns), sosfiltfilt_ragged_batch(curves(7, rows, n_max), torch.clamp(ld, min=28), s_ns))
+
+    # mfcc_change_device on the shapes of tests/test_gpu_sos.py (segmented with a wave per segment, clip-resident in three
+    # groups of rows, segmented with a workgroup per row) and a short clip; fused, and on the time-major kernels (chunked
+    # at n_ext >= 256, sequential at 101 frames)
+    base = dict(sr=16000.0, n_fft=512, win_length=400, hop_length=160, n_mels=40, n_mfcc=13, fmin=100.0, fmax=8000.0)
+    sets = {"default": dict(outFiltCutOff=[12]), "sg": dict(diffMethod="sg", outFiltCutOff=[12]), "nofilt": dict(outFilter=None),
+            "sec1v4": dict(filtOrd=2, outFiltLen=8, outFiltCutOff=[12]), "sec4v1": dict(filtOrd=8, outFiltLen=1, outFiltCutOff=[12]), "sec2": dict(filtOrd=4, outFiltLen=4, outFiltCutOff=[12])}
+    plan = MfccPlan(MfccConfig(**base))
+    for B, T in ((2, 5500), (3, 3001), (130, 5500), (3, 101)):
+        m = torch.from_numpy(np.random.default_rng(4).standard_normal((B, 13, T)).cumsum(axis=2).astype(np.float32)).to(dev)
+        for fuse in (True, False):
+            prev = plan.set_fuse_tail(fuse)
+            for name, kw in sets.items():
+                if B < 128 or name in ("default", "sg"):
+                    keep("chg.%dx%d.%s.%s" % (B, T, "fused" if fuse else "tm", name), tail.mfcc_change_device(plan, m, tStep=0.005, **kw))
+            plan.set_fuse_tail(prev)
+    # more than 64 rows after c0 on the time-major kernels: chg_norm_rows_kernel
+    plan70 = MfccPlan(MfccConfig(**dict(base, n_mels=80, n_mfcc=70)))
+    m = torch.from_numpy(np.random.default_rng(5).standard_normal((3, 70, 301)).cumsum(axis=2).astype(np.float32)).to(dev)
+    plan70.set_fuse_tail(False)
+    for name in ("default", "sg"):
+        keep("chg.rows69.%s" % name, tail.mfcc_change_device(plan70, m, tStep=0.005, **sets[name]))
+    # mfcc_change_ragged: frame counts 1, a refused one, padlen + 1, T_max; T_max 1001 takes the 12 rows in two groups
+    for T in (301, 1001):
+        fr = np.random.default_rng(T).integers(22, T + 1, 9)
+        fr[:4] = (1, 15, 22, T)
+        fd = torch.from_numpy(fr.astype(np.int64)).to(dev)
+        m = torch.from_numpy(np.random.default_rng(6).standard_normal((9, 13, T)).cumsum(axis=2).astype(np.float32)).to(dev)
+        for name in ("default", "sg", "nofilt", "sec1v4", "sec2"):
+            keep("chgrag.T%d.%s" % (T, name), tail.mfcc_change_ragged_device(plan, m, fd, tStep=0.005, **sets[name]))
+
+    # apply_stencil / apply_stencil_ragged: np.gradient, Savitzky-Golay window 5, a 6-tap FIR filtfilt
+    x = curves(8, 5, 700)
+    ld = torch.tensor([700, 1, 9, 350, 699], dtype=torch.int64, device=dev)
+    stencils = {"grad": velocity_stencil(100.0, 1, "gradient")[0], "sg5": velocity_stencil(100.0, 1, "sg", width=5)[0],
+                "fir6": fir_filtfilt_stencil(scipy.signal.firwin(6, 0.3))}
+    for name, st in stencils.items():
+        keep("stencil." + name, apply_stencil(x, st))
+        keep("stencilrag." + name, apply_stencil_ragged(x, ld, st, 19 if name == "fir6" else 0))
+    torch.cuda.synchronize()
+    return out
+
+
+CASESETS = {"s16": s16_cases, "tail": tail_cases}
 
 if __name__ == "__main__":
     if len(sys.argv) == 4 and sys.argv[1] == "--compare":
