@@ -30,6 +30,8 @@
  *   mm_fir_filtfilt_ragged_f64,
  *   mm_savgol_ragged_f64   <- the four filters above on a padded batch with one length per curve, each curve filtered as
  *                             if it were called alone, bit for bit (build-defined; no reference site)
+ *   mm_rms_ragged_f32,
+ *   mm_hilbert_envelope_ragged <- the two envelopes below for a padded batch with one length per clip
  *   mm_rms_f32,
  *   mm_hilbert_envelope    <- calculate_amplitude_envelope (script/calc.py:284-343): librosa.feature.rms /
  *                             |scipy.signal.hilbert| -- row N3
@@ -400,6 +402,15 @@ int mm_savgol_ragged_f64(const double* d_x, int64_t rows, int64_t n_max, int64_t
 int64_t mm_rms_num_frames(int64_t n_samples, int32_t frame_length, int32_t hop_length, int32_t center);
 int mm_rms_f32(const float* d_audio, int64_t batch, int64_t n_samples, int64_t audio_stride,
                int32_t frame_length, int32_t hop_length, int32_t center, float* d_rms, void* stream);
+/* The same for a ragged batch (no reference site: the reference takes one clip per call): d_audio [batch][audio_stride]
+ * padded to n_max samples and d_lens (DEVICE, int64 [batch]), the valid samples of each clip, clamped by the kernels into
+ * [1, n_max] -> d_rms [batch][t_max], t_max = mm_rms_num_frames(n_max, ...).  Row b holds the T_b = mm_rms_num_frames(n_b,
+ * ...) frames of audio[b, :n_b] -- its own centre padding, zeros for everything at or behind n_b, which is never read --
+ * bit for bit what mm_rms_f32 gives for that clip alone (the same kernels, the same summation order), and +0.0 in
+ * [T_b, t_max).  Without centring a clip shorter than frame_length has no frame: its row is NaN.  The launch is that of
+ * n_max, whatever the lengths. */
+int mm_rms_ragged_f32(const float* d_audio, int64_t batch, int64_t n_max, int64_t audio_stride, const int64_t* d_lens,
+                      int32_t frame_length, int32_t hop_length, int32_t center, float* d_rms, void* stream);
 
 /* Hilbert envelope (row N3): np.abs(scipy.signal.hilbert(x)) as called at script/calc.py:286 -- the DFT of the
  * clip at its own length n (any integer 1 .. 2^24), negative frequencies zeroed, positive ones doubled, the
@@ -425,6 +436,27 @@ int64_t mm_hilbert_fft_size(const mm_hilbert* h);
 size_t mm_hilbert_workspace_bytes(const mm_hilbert* h, int64_t rows);
 int mm_hilbert_envelope(mm_hilbert* h, const void* d_x, int64_t rows, int64_t x_stride, void* d_env,
                         int64_t env_stride, void* d_workspace, size_t ws_bytes, void* stream);
+/* The Hilbert envelope of a ragged batch (no reference site: the reference takes one clip per call): d_x [rows][x_stride]
+ * padded to n_max samples and d_lens (DEVICE, int64 [rows]), clamped by the kernels into [1, n_max] -> d_env [rows]
+ * [env_stride]: row b holds |scipy.signal.hilbert(x[b, :n_b])| in [0, n_b) and +0.0 in [n_b, n_max).  scipy's DFT runs at
+ * the clip's own length, so every row goes through Bluestein's identity with its OWN chirp exp(-i pi k^2 / n_b) over one
+ * shared power-of-two FFT: mm_hilbert_ragged_create(n_max, dtype) fixes M = 2^p >= max(16, 2 n_max - 1) (mm_hilbert_
+ * fft_size) and owns the twiddle tables of M only, so one handle serves every call whose n_max it covers (2 n_max - 1 <=
+ * M), whatever the lengths.  Per call: the rows' chirps and wrapped chirps (integers k^2 mod 2 n_b, sincospi in float64,
+ * rounded once), their spectra by one batched FFT in the clips' precision, then the four transforms of the chirp branch
+ * of mm_hilbert_envelope with one clip per transform (two clips could share one only if they shared a chirp).  Nothing at
+ * or behind n_b is read; a NaN or an infinity inside a clip makes that row NaN in [0, n_b) and touches no other row.
+ * The clips are transformed unscaled (mm_hilbert_envelope's power-of-two scaling serves its pairing): the unnormalised
+ * transforms reach max(envelope) n_b M, so a float32 clip stays finite where scipy does only while that product is below
+ * 3.4e38: amplitudes up to about 1e27 at 160 000 samples (M = 2^19), 6e23 at 2^24 samples; float64: no practical limit.
+ * Asynchronous on `stream`, no allocation, rows <= 65535; workspace = mm_hilbert_ragged_workspace_bytes(h, rows, n_max) =
+ * three [rows][M] complex buffers, the [rows][n_max] chirps and a flag per row (0 for invalid arguments; MM_ERR_WORKSPACE
+ * below it).  A ragged handle is not taken by mm_hilbert_envelope / mm_hilbert_rfft_f32, nor the other way round. */
+int mm_hilbert_ragged_create(int64_t n_max, int32_t dtype, mm_hilbert** out);
+size_t mm_hilbert_ragged_workspace_bytes(const mm_hilbert* h, int64_t rows, int64_t n_max);
+int mm_hilbert_envelope_ragged(mm_hilbert* h, const void* d_x, int64_t rows, int64_t n_max, int64_t x_stride,
+                               const int64_t* d_lens, void* d_env, int64_t env_stride, void* d_workspace, size_t ws_bytes,
+                               void* stream);
 /* rFFT of real float32 rows zero-padded to the plan's length n (a plan of dtype 0 whose length is even and 2 / 3 / 5 / 7-
  * smooth, i.e. mm_hilbert_fft_size() == n): d_x [rows][x_stride] with n_valid <= n samples each -> d_out complex64
  * [rows][n / 2 + 1] -- the trajectory rFFT (np.fft.rfft(mfcc, n, axis=-1), row A8 of the hot path) for clips with more

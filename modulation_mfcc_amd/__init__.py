@@ -7,9 +7,12 @@ include/modmfcc.h).  torch is used for device buffers, streams and torch.distrib
 from .plan import MfccConfig, MfccPlan, get_plan, butter_sos  # noqa: F401
 from .batch import mfcc_batch, modspec_batch, mfcc_modspec_batch, rfft_batch, rms_batch  # noqa: F401
 from .batch import mfcc_ragged_batch, mfcc_modspec_ragged_batch, mfcc_change_ragged_batch, pack_clips  # noqa: F401
+from .batch import rms_ragged_batch, rms_ragged_frames  # noqa: F401
 from .mfcc import get_MFCCS_change, get_MFCCS_change_batch, load_channel, applyFilter, get_amplitude  # noqa: F401
+from .mfcc import get_amplitude_batch  # noqa: F401
 from .calc import (get_velocity, calculate_amplitude_envelope, velocity_batch, amplitude_envelope_batch,  # noqa: F401
-                   hilbert_envelope_batch, find_peaks_batch, find_peaks_ex_batch,
+                   hilbert_envelope_batch, hilbert_envelope_ragged_batch, amplitude_envelope_ragged_batch,
+                   calculate_amplitude_envelope_batch, find_peaks_batch, find_peaks_ex_batch,
                    peaks_to_list, MinMaxFinder)
 from .filters import sosfiltfilt_batch, fir_filtfilt_batch, savgol_batch  # noqa: F401
 from .filters import (sosfiltfilt_ragged_batch, fir_filtfilt_ragged_batch, savgol_ragged_batch,  # noqa: F401

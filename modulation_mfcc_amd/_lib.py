@@ -167,6 +167,10 @@ PROTOTYPES = {
                                             C.c_int32, _vp, _vp, C.c_size_t, _vp]),
     "mm_rms_num_frames": (_i64, [_i64, C.c_int32, C.c_int32, C.c_int32]),
     "mm_rms_f32": (C.c_int, [_vp, _i64, _i64, _i64, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    "mm_rms_ragged_f32": (C.c_int, [_vp, _i64, _i64, _i64, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    "mm_hilbert_ragged_create": (C.c_int, [_i64, C.c_int32, C.POINTER(_vp)]),
+    "mm_hilbert_ragged_workspace_bytes": (C.c_size_t, [_vp, _i64, _i64]),
+    "mm_hilbert_envelope_ragged": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, C.c_size_t, _vp]),
     "mm_hilbert_create": (C.c_int, [_i64, C.c_int32, C.POINTER(_vp)]),
     "mm_hilbert_destroy": (None, [_vp]),
     "mm_hilbert_fft_size": (_i64, [_vp]),

@@ -57,22 +57,24 @@ def mfcc_change_ragged_batch(audio, lengths, cfg: MfccConfig, *, tStep=None, **t
     return _tail.mfcc_change_ragged_device(plan, mfcc, fr, tStep=tStep, **tail), frames
 
 
-def pack_clips(clips):
+def pack_clips(clips, dtype=None):
     """A list of 1-D float32 tensors (one device) -> (audio [B, n_max] on that device, lengths int64 [B] on the host) for
-    the ragged calls.  The padding behind each clip is left as allocated: the ragged calls never read it into a result."""
+    the ragged calls.  The padding behind each clip is left as allocated: the ragged calls never read it into a result.
+    ``dtype``: another type the clips all have (torch.float64: the double-precision Hilbert envelope)."""
     import torch
+    dtype = torch.float32 if dtype is None else dtype
     clips = list(clips)
     if not clips:
         raise ValueError("pack_clips: no clips")
     for c in clips:
-        if not (isinstance(c, torch.Tensor) and c.dtype == torch.float32 and c.dim() == 1):
-            raise TypeError("pack_clips: every clip must be a 1-D float32 tensor")
+        if not (isinstance(c, torch.Tensor) and c.dtype == dtype and c.dim() == 1):
+            raise TypeError(f"pack_clips: every clip must be a 1-D {str(dtype).replace('torch.', '')} tensor")
         if c.device != clips[0].device:
             raise ValueError(f"pack_clips: clips on {clips[0].device} and {c.device}")
         if c.shape[0] < 1:
             raise ValueError("pack_clips: empty clip")
     lengths = torch.tensor([c.shape[0] for c in clips], dtype=torch.int64)
-    audio = torch.empty((len(clips), int(lengths.max())), dtype=torch.float32, device=clips[0].device)
+    audio = torch.empty((len(clips), int(lengths.max())), dtype=dtype, device=clips[0].device)
     for b, c in enumerate(clips):
         audio[b, :c.shape[0]].copy_(c, non_blocking=True)
     return audio, lengths
@@ -105,4 +107,55 @@ def rms_batch(audio, frame_length: int, hop_length: int, center: bool = True):
     stream = C.c_void_p(torch.cuda.current_stream(audio.device).cuda_stream)
     _lib.check(lib.mm_rms_f32(audio.data_ptr(), B, n, audio.stride(0), int(frame_length), int(hop_length),
                               1 if center else 0, out.data_ptr(), stream), "mm_rms_f32")
+    return out
+
+
+def rms_ragged_frames(lengths, frame_length, hop_length, center=True):
+    """RMS frames of clips of ``lengths`` samples (host integers) -> int64 numpy array: mm_rms_num_frames per clip, 0 for a
+    clip too short for one frame (only without centring).  No GPU needed."""
+    import numpy as np
+    n = np.asarray(lengths, dtype=np.int64)
+    padded = n + (2 * (int(frame_length) // 2) if center else 0)
+    return np.where((n >= 1) & (padded >= frame_length), 1 + (padded - int(frame_length)) // int(hop_length), 0).astype(np.int64)
+
+
+def rms_ragged_batch(audio, lengths, frame_length: int, hop_length: int, center: bool = True):
+    """rms_batch for clips of different lengths in one padded batch (mm_rms_ragged_f32): ``audio`` [B, n_max] float32 on the
+    device and one valid sample count per clip -> [B, t_max] float32, t_max the frames of n_max.  Row b holds, in its first
+    rms_ragged_frames(lengths[b]) columns, rms_batch(audio[b, :lengths[b]]) bit for bit -- the clip's own centre padding,
+    zeros for everything behind its end -- and +0.0 behind them; what the padding of ``audio`` holds never matters.
+
+    ``lengths``: host integers (validated: ValueError outside [1, n_max], and for a clip shorter than the frame without
+    centring, the clip named) or an int64 device tensor (no read-back; the kernels clamp it, and a clip without a frame gets
+    a NaN row).  One launch, that of n_max."""
+    import ctypes as C
+    import numpy as np
+    import torch
+    from . import _lib
+    from .plan import check_lengths
+    lib = _lib.load()
+    if not (isinstance(audio, torch.Tensor) and audio.is_cuda and audio.dtype == torch.float32):
+        raise TypeError("audio must be a float32 CUDA(HIP) tensor")
+    if audio.dim() != 2:
+        raise ValueError("audio must be [B, n_max]")
+    B, n = audio.shape
+    if (n > 1 and audio.stride(1) != 1) or (B > 1 and audio.stride(0) < n):
+        audio = audio.contiguous()
+    lens = check_lengths(lengths, B, n, audio.device)
+    frame_length, hop_length, center = int(frame_length), int(hop_length), 1 if center else 0
+    t_max = lib.mm_rms_num_frames(n, frame_length, hop_length, center)
+    if t_max < 0:
+        _lib.check(int(t_max), "mm_rms_num_frames")
+    if isinstance(lens, np.ndarray):
+        none = np.flatnonzero(rms_ragged_frames(lens, frame_length, hop_length, center) < 1)
+        if none.size:
+            raise ValueError(f"rms: a clip of {int(lens[none[0]])} samples is shorter than frame_length={frame_length} "
+                             f"(clip {int(none[0])})")
+    out = torch.empty((B, t_max), dtype=torch.float32, device=audio.device)
+    with torch.cuda.device(audio.device):
+        lens_dev = torch.from_numpy(lens).to(audio.device, non_blocking=True) if isinstance(lens, np.ndarray) else lens
+        stream = C.c_void_p(torch.cuda.current_stream(audio.device).cuda_stream)
+        _lib.check(lib.mm_rms_ragged_f32(audio.data_ptr(), B, n, audio.stride(0) if B > 1 else n,
+                                         lens_dev.data_ptr(), frame_length, hop_length, center, out.data_ptr(), stream),
+                   "mm_rms_ragged_f32")
     return out

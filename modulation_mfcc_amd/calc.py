@@ -21,7 +21,8 @@ from .ema import read_AG50x, read_AG50x_arrays, read_pos_header  # noqa: F401
 __all__ = ["applyFilter", "get_f0", "get_f0_batch", "interp_NAN", "interp_nan_batch", "interp_nan_ragged_batch",
            "read_AG50x", "read_AG50x_arrays", "read_pos_header",
            "get_velocity", "calculate_amplitude_envelope", "velocity_stencil", "velocity_batch", "apply_stencil",
-           "hilbert_envelope_batch", "amplitude_envelope_batch", "find_peaks_batch", "find_peaks_ex_batch",
+           "hilbert_envelope_batch", "amplitude_envelope_batch", "hilbert_envelope_ragged_batch",
+           "amplitude_envelope_ragged_batch", "calculate_amplitude_envelope_batch", "find_peaks_batch", "find_peaks_ex_batch",
            "peaks_to_list", "MinMaxFinder"]
 
 
@@ -39,14 +40,17 @@ HILBERT_WS_BYTES = 4 << 30      # workspace bound of one mm_hilbert_envelope cal
 class _HilbertPlan:
     """Owner of one mm_hilbert handle (constant chirp / twiddle tables of one clip length on one device)."""
 
-    def __init__(self, n, dtype_code, device):
+    def __init__(self, n, dtype_code, device, ragged=False):
         import ctypes as C
         import torch
         from . import _lib
         self._lib = _lib.load()
         h = C.c_void_p()
         with torch.cuda.device(device):
-            _lib.check(self._lib.mm_hilbert_create(n, dtype_code, C.byref(h)), "mm_hilbert_create")
+            if ragged:       # n: the longest clip of the transform length the handle is for
+                _lib.check(self._lib.mm_hilbert_ragged_create(n, dtype_code, C.byref(h)), "mm_hilbert_ragged_create")
+            else:
+                _lib.check(self._lib.mm_hilbert_create(n, dtype_code, C.byref(h)), "mm_hilbert_create")
         self.h = h
 
     def __del__(self):
@@ -56,6 +60,19 @@ class _HilbertPlan:
                 self.h = None
         except Exception:
             pass
+
+
+_HILBERT_RAGGED_PLANS = {}      # (M, dtype, device) -> _HilbertPlan of the ragged envelope: twiddle tables only (16 M / 1024 +
+                                # 16 KiB bytes), at most 22 transform lengths -- kept, never evicted
+
+
+def _hilbert_ragged_plan(M, code, device):
+    """The mm_hilbert handle of the ragged envelope for the transform length M (mm_hilbert_ragged_create at the longest
+    clip M takes, M / 2), kept per (M, dtype code, device) apart from the single-length plans' LRU."""
+    key = (int(M), int(code), str(device))
+    if key not in _HILBERT_RAGGED_PLANS:
+        _HILBERT_RAGGED_PLANS[key] = _HilbertPlan(int(M) // 2, int(code), device, ragged=True)
+    return _HILBERT_RAGGED_PLANS[key]
 
 
 def _hilbert_plan(n, code, device):
@@ -144,6 +161,115 @@ def hilbert_envelope_batch(x):
     return out[0] if squeeze else out
 
 
+def hilbert_ragged_fft_size(n):
+    """The power-of-two transform length of a clip of ``n`` samples in the ragged envelope: M = 2^p >= max(16, 2 n - 1)."""
+    return max(16, 1 << (2 * int(n) - 2).bit_length())
+
+
+def _hilbert_ragged_classes(lens):
+    """Host lengths [B] -> [(M, int64 index array of the rows whose own transform length is M)], ascending M."""
+    M = np.array([hilbert_ragged_fft_size(n) for n in lens], dtype=np.int64)
+    return [(int(m), np.flatnonzero(M == m).astype(np.int64)) for m in np.unique(M)]
+
+
+def _hilbert_ragged_rows(x2, lens_dev, M):
+    """mm_hilbert_envelope_ragged on x2 [rows, n_max] (unit inner stride) with device lengths, through the transform length
+    ``M`` >= 2 n_max - 1 -> [rows, n_max]; the rows are cut into calls of at most HILBERT_WS_BYTES of workspace."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    rows, n = x2.shape
+    code = 0 if x2.dtype == torch.float32 else 1
+    plan = _hilbert_ragged_plan(M, code, x2.device)
+    lib = _lib.load()
+    out = torch.empty((rows, n), dtype=x2.dtype, device=x2.device)
+    per_row = int(lib.mm_hilbert_ragged_workspace_bytes(plan.h, 1, n))
+    chunk = int(max(1, min(rows, 65535, HILBERT_WS_BYTES // max(per_row, 1))))
+    ws = torch.empty(int(lib.mm_hilbert_ragged_workspace_bytes(plan.h, chunk, n)), dtype=torch.uint8, device=x2.device)
+    stream = C.c_void_p(torch.cuda.current_stream(x2.device).cuda_stream)
+    stride = x2.stride(0) if rows > 1 else n
+    with torch.cuda.device(x2.device):
+        for r0 in range(0, rows, chunk):
+            r = min(chunk, rows - r0)
+            _lib.check(lib.mm_hilbert_envelope_ragged(plan.h, x2[r0:].data_ptr(), r, n, stride, lens_dev[r0:].data_ptr(),
+                                                      out[r0:].data_ptr(), n, ws.data_ptr(), ws.numel(), stream),
+                       "mm_hilbert_envelope_ragged")
+    return out
+
+
+def hilbert_envelope_ragged_batch(x, lengths):
+    """hilbert_envelope_batch for clips of different lengths in one padded batch: ``x`` [B, n_max] (float32 or float64 on the
+    device, rows may be strided) and one valid sample count per clip -> [B, n_max] of the same type.  Row b holds
+    |scipy.signal.hilbert(x[b, :n_b])| -- the DFT at the clip's OWN length -- in its first n_b columns and +0.0 behind them;
+    what the padding of ``x`` holds never matters, and a NaN or an infinity inside a clip makes that row NaN and no other.
+
+    Every clip goes through Bluestein's identity with its own chirp over a shared power-of-two FFT (mm_hilbert_envelope_
+    ragged): no tables per length; the handle of a transform length M (its twiddle tables) is kept for good.
+    ``lengths``: host integers (validated: ValueError outside [1, n_max]) -- the rows are then grouped by their own M =
+    2^p >= max(16, 2 n_b - 1), one ragged call per class, so a short clip does not pay for a long neighbour's transform and
+    a row's result depends on its own length only -- or an int64 device tensor (no read-back; the kernels clamp it; one class,
+    that of n_max).  Calls are cut to HILBERT_WS_BYTES of workspace.
+
+    The clips are transformed as they are, without hilbert_envelope_batch's per-clip power-of-two scaling (that serves its
+    pairing): the unnormalised transforms reach max(envelope) n_b M, so a float32 clip stays finite where scipy does only
+    while that product is below 3.4e38 -- amplitudes up to about 1e27 at ten seconds of 16 kHz, 6e23 at 2^24 samples."""
+    import torch
+    from .plan import check_lengths
+    if not (_is_device_tensor(x) and x.dtype in (torch.float32, torch.float64)):
+        raise TypeError("x must be a float32 / float64 CUDA(HIP) tensor")
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError("x must be [B, n_max], at least one row and one column")
+    B, n_max = x.shape
+    if (n_max > 1 and x.stride(1) != 1) or (B > 1 and x.stride(0) < n_max):
+        x = x.contiguous()
+    lens = check_lengths(lengths, B, n_max, x.device)
+    if not isinstance(lens, np.ndarray):
+        return _hilbert_ragged_rows(x, lens, hilbert_ragged_fft_size(n_max))
+    out = None
+    for M, idx in _hilbert_ragged_classes(lens):
+        n_c = int(lens[idx].max())              # the class's calls are cut to its longest clip: M covers n_c, not n_max
+        lens_c = torch.from_numpy(lens[idx]).to(x.device)
+        if len(idx) == B and n_c == n_max:      # one class that fills the batch: as it is, no gather
+            return _hilbert_ragged_rows(x, lens_c, M)
+        if out is None:
+            out = torch.zeros((B, n_max), dtype=x.dtype, device=x.device)
+        if len(idx) == B:
+            out[:, :n_c] = _hilbert_ragged_rows(x[:, :n_c], lens_c, M)
+        else:
+            ii = torch.from_numpy(idx).to(x.device)
+            out[ii, :n_c] = _hilbert_ragged_rows(x[ii, :n_c], lens_c, M)
+    return out
+
+
+def amplitude_envelope_ragged_batch(x, lengths, sr, *, method: str = "RMS", winLen: float = 0.1, hopLen: float = 0.01,
+                                    center: bool = True):
+    """amplitude_envelope_batch for a padded batch with a length per clip: ``x`` [B, n_max] on the device, ``lengths`` host
+    integers or an int64 device tensor -> (env [B, n_out_max], out_lengths, sample rate of the envelope).  Row b holds what
+    amplitude_envelope_batch gives for x[b, :lengths[b]] alone in its first out_lengths[b] columns ('RMS': bit for bit,
+    batch.rms_ragged_batch; 'Hilb': hilbert_envelope_ragged_batch) and +0.0 behind them.  ``out_lengths`` is a numpy array
+    for host lengths and a device tensor for device lengths (the clamped lengths for 'Hilb', the frame counts for 'RMS')."""
+    from .batch import rms_ragged_batch, rms_ragged_frames
+    if method == "Hilb":
+        env = hilbert_envelope_ragged_batch(x, lengths)
+        out_len = lengths.clamp(1, x.shape[1]) if _is_device_tensor(lengths) else np.asarray(lengths, dtype=np.int64)
+        return env, out_len, 1 / hopLen                   # the reference's rate quirk, as in amplitude_envelope_batch
+    if method == "RMS":
+        import torch
+        xf = x if x.dtype == torch.float32 else x.float()
+        frame, hop = int(winLen * sr), int(hopLen * sr)
+        env = rms_ragged_batch(xf, lengths, frame, hop, center)
+        if _is_device_tensor(lengths):
+            padded = lengths.clamp(1, x.shape[1]) + (2 * (frame // 2) if center else 0)
+            out_len = torch.where(padded >= frame, 1 + torch.div(padded - frame, hop, rounding_mode="floor"),
+                                  torch.zeros_like(padded))
+        else:
+            out_len = rms_ragged_frames(np.asarray(lengths), frame, hop, center)
+        return env, out_len, 1 / hopLen
+    if method == "RMSpraat":
+        raise NotImplementedError("method='RMSpraat' calls Praat through parselmouth; not part of this build")
+    raise UnboundLocalError(f"unknown amplitude method {method!r}")
+
+
 def amplitude_envelope_batch(x, sr, *, method: str = "RMS", winLen: float = 0.1, hopLen: float = 0.01,
                              center: bool = True):
     """The envelope of calculate_amplitude_envelope (script/calc.py:284-343, before its output filter) for a
@@ -200,6 +326,70 @@ def calculate_amplitude_envelope(x, sr, /, *, method: str = "RMS", winLen: float
         env = applyFilter(env, env_sr, filt=outFilter, filtType=outFiltType, cutOff=outFiltCutOff,
                           filtLen=outFiltLen, polyOrd=outFiltPolyOrd)
     return env, times
+
+
+def calculate_amplitude_envelope_batch(clips, sr, /, *, method: str = "RMS", winLen: float = 0.1, hopLen: float = 0.01,
+                                       center: bool = True, outFilter=None, outFiltType: str = "low", outFiltCutOff=[12],
+                                       outFiltLen: int = 6, outFiltPolyOrd: int = 3):
+    """``calculate_amplitude_envelope`` for a list of clips of any lengths ([n] each, numpy or CUDA(HIP) tensors) -> a list of
+    ``(amp, ampT)``, one per clip, each what the single call returns for that clip: numpy ``amp`` for a numpy clip, a device
+    tensor for a device clip, ``ampT = np.arange(len(amp)) * hopLen`` for both methods (the reference's 'hilb' quirk).
+
+    The clips are packed (batch.pack_clips) and run through amplitude_envelope_ragged_batch: 'RMS' as one float32 batch,
+    'Hilb' as one batch of its float32 clips and one of the others (float64), each clip in the precision it has alone.
+    ``outFilter`` is ONE filters.apply_filter_ragged_batch on the padded envelopes at the rate 1 / hopLen -- for numpy clips
+    too, whose single call filters with scipy on the host (equal to rounding) -- and one copy brings the numpy results back.
+    A clip the single call refuses raises that call's exception with the clip's index appended."""
+    if method == "RMSpraat":
+        raise NotImplementedError("method='RMSpraat' calls Praat through parselmouth; not part of this build")
+    if method not in ("Hilb", "RMS"):
+        raise UnboundLocalError(f"unknown amplitude method {method!r}")   # reference: `amp` unbound
+    import torch
+    from .batch import pack_clips
+    from .filters import RowRefused, apply_filter_ragged_batch
+    from .pitch import _blame_clip
+    clips = list(clips)
+    if not clips:
+        return []
+    on_device = [_is_device_tensor(c) for c in clips]
+    if not all(on_device) and not torch.cuda.is_available():
+        raise RuntimeError("modulation_mfcc_amd needs an AMD GPU (gfx950); there is no CPU fallback")
+    sigs = []
+    for i, (c, d) in enumerate(zip(clips, on_device)):
+        if not d:
+            a = np.asarray(c)
+            # librosa.feature.rms / scipy.signal.hilbert keep float32 input in single precision, anything else in double
+            c = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32 if (method == "RMS" or a.dtype == np.float32)
+                                                      else np.float64)).cuda()
+        elif method == "RMS":
+            c = c if c.dtype == torch.float32 else c.float()
+        elif c.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"x must be a float32 / float64 CUDA(HIP) tensor (clip {i})")
+        if c.dim() != 1 or c.shape[0] < 1:
+            raise ValueError(f"every clip must be [n] with at least one sample (clip {i})")
+        sigs.append(c)
+    kw = dict(method=method, winLen=winLen, hopLen=hopLen, center=center)
+    out = [None] * len(clips)
+    for dtype in (torch.float32, torch.float64):
+        idx = [i for i, s in enumerate(sigs) if s.dtype == dtype]
+        if not idx:
+            continue
+        x, lengths = pack_clips([sigs[i] for i in idx], dtype)
+        try:
+            env, out_len, env_sr = amplitude_envelope_ragged_batch(x, lengths.numpy(), sr, **kw)
+        except ValueError as e:
+            _blame_clip(e, lambda b: amplitude_envelope_batch(sigs[idx[b]], sr, **kw), idx)
+        if outFilter is not None:
+            try:
+                env = apply_filter_ragged_batch(env, out_len, env_sr, filt=outFilter, filtType=outFiltType,
+                                                cutOff=outFiltCutOff, filtLen=outFiltLen, polyOrd=outFiltPolyOrd)
+            except RowRefused as e:                               # (an envelope too short for the filter)
+                raise ValueError(f"{e.base} (clip {idx[e.row]})") from e
+        host = None if all(on_device[i] for i in idx) else env.cpu().numpy()
+        for b, i in enumerate(idx):
+            n = int(out_len[b])
+            out[i] = (env[b, :n].clone() if on_device[i] else host[b, :n].copy(), np.arange(n) * hopLen)
+    return out
 
 
 def _findiff_first_axis(x, h, order, acc):

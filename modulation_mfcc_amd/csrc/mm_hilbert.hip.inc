@@ -36,6 +36,12 @@
 // The pointwise steps between the transforms (chirp products, the spectrum mask, the magnitude) ride on the
 // first / last pass of the neighbouring transform (HbIo), so the traffic per clip is that of the passes alone:
 // (2 direct or 4 Bluestein transforms) x passes x 2 x M x sizeof(complex) -- HBM-bound streaming kernels.
+//
+// A LENGTH PER CLIP (mm_hilbert_envelope_ragged).  Clips of different lengths cannot share a mixed-radix plan, but they
+// share the chirp identity: one M = 2^p >= 2 n_max - 1 for all rows, each row with its own chirp exp(-i pi k^2 / n_b) and
+// chirp spectrum, both written per call (hb_chirp_ragged_kernel + one batched FFT in the clips' precision).  The passes
+// are the RG = true instantiations of the same kernels: hb_row_setup loads the row's n, w, bhat and scale once per
+// workgroup.  One clip per transform -- two clips could share one only if they shared a chirp.
 
 #include "mm_hb_math.h"
 
@@ -69,10 +75,24 @@ struct HbIo {
   T da, db, ua, ub;         // the workgroup's row: down / up of its two clips (hb_row_setup; the kernels' own copy)
   hb_c<T>* half;            // HB_OUT_HALF: [rows][half_stride] complex, bins m <= half_bins - 1 of every row
   int64_t half_stride, half_bins;
+  // ragged kernels (RG) only -- a length, a chirp and a chirp spectrum per row (hb_row_setup<T, true>):
+  const int64_t* lens;      //   [rows] valid samples of each clip, clamped into [1, n_max]; n, w, bhat and scale above are then
+  int64_t n_max;            //   the workgroup's row's: w [rows][n_max], bhat [rows][M]
+  const int* bad;           //   [rows] not 0: the clip holds a NaN or an infinity, its envelope is NaN
 };
 
-template <typename T>
-__device__ __forceinline__ void hb_row_setup(HbIo<T>& io, int64_t row) {
+template <typename T, bool RG = false>
+__device__ __forceinline__ void hb_row_setup(HbIo<T>& io, int64_t row, int64_t M) {
+  if constexpr (RG) {
+    // one clip per transformed row, each with its own length, chirp and chirp spectrum: uniform per workgroup, loaded once
+    const int64_t len = io.lens[row];
+    const int64_t n = len < 1 ? 1 : (len > io.n_max ? io.n_max : len);
+    io.n = n;
+    io.w += row * io.n_max;
+    io.bhat += row * M;
+    if (io.out_mode == HB_OUT_ENVELOPE) io.scale = io.bad[row] ? (T)NAN : (T)(1.0 / ((double)M * (double)n));
+    return;
+  }
   if (!io.down) return;
   io.da = io.down[2 * row]; io.ua = io.up[2 * row];
   const bool two = 2 * row + 1 < io.x_rows;
@@ -116,7 +136,7 @@ __device__ __forceinline__ hb_c<T> hb_load(const HbIo<T>& io, const hb_c<T>* __r
   return r;
 }
 
-template <typename T>
+template <typename T, bool RG = false>
 __device__ __forceinline__ void hb_store(const HbIo<T>& io, hb_c<T>* __restrict__ dst, int64_t row, int64_t m, hb_c<T> V) {
   switch (io.out_mode) {
     case HB_OUT_COMPLEX: dst[m] = V; break;
@@ -136,6 +156,8 @@ __device__ __forceinline__ void hb_store(const HbIo<T>& io, hb_c<T>* __restrict_
         // (the scaled clips lie in [-1, 1]: a plain square root neither overflows nor underflows where it matters)
         io.env[2 * row * io.env_stride + m] = sqrt(ab.x * ab.x + ha * ha) * io.ua;
         if (2 * row + 1 < io.x_rows) io.env[(2 * row + 1) * io.env_stride + m] = sqrt(ab.y * ab.y + hb * hb) * io.ub;
+      } else if constexpr (RG) {
+        if (m < io.n_max) io.env[row * io.env_stride + m] = (T)0;       // behind the clip's end: +0.0
       }
       break;
     case HB_OUT_HALF:
@@ -211,7 +233,7 @@ template <typename T, int R> struct HbFuse {
   static constexpr int C = (R == 16 ? MM_HB_C16 : 10) / (sizeof(T) == 8 ? 2 : 1);
   static constexpr int THREADS = C * R;
 };
-template <typename T, int R>
+template <typename T, int R, bool RG = false>
 __global__ __launch_bounds__((HbFuse<T, R>::THREADS)) void hb_pass2_kernel(const hb_c<T>* __restrict__ in, hb_c<T>* __restrict__ out,
                                                                         int64_t M, int64_t Ns, int64_t n_rows,
                                                                         const hb_c<double>* __restrict__ lo,
@@ -231,7 +253,7 @@ __global__ __launch_bounds__((HbFuse<T, R>::THREADS)) void hb_pass2_kernel(const
   const int64_t c = (L - row * nblk) * C + cl;
   const hb_c<T>* src = in + row * M;
   hb_c<T>* dst = out + row * M;
-  hb_row_setup<T>(io, row);
+  hb_row_setup<T, RG>(io, row, M);
   const bool live = c < nbC;
   const int64_t k = live ? (int64_t)((uint32_t)c % (uint32_t)Ns) : 0;
   if (live) {
@@ -278,7 +300,7 @@ __global__ __launch_bounds__((HbFuse<T, R>::THREADS)) void hb_pass2_kernel(const
     if (Ns > 1) {
       const int64_t m0 = (c - k) * RC + k + (int64_t)x * Ns;
 #pragma unroll
-      for (int vv = 0; vv < R; ++vv) hb_store(io, dst, row, m0 + (int64_t)vv * R * Ns, b[hb_perm<R>(vv)]);
+      for (int vv = 0; vv < R; ++vv) hb_store<T, RG>(io, dst, row, m0 + (int64_t)vv * R * Ns, b[hb_perm<R>(vv)]);
     }
   }
   if (Ns == 1) {
@@ -293,7 +315,7 @@ __global__ __launch_bounds__((HbFuse<T, R>::THREADS)) void hb_pass2_kernel(const
     const int64_t c0 = c - cl;
     const int n_live = (int)(nbC - c0 < C ? nbC - c0 : C);
     for (int e = threadIdx.x; e < n_live * RC; e += C * R)
-      hb_store(io, dst, row, c0 * RC + e, tile[(e / RC) * PITCH + (e % RC)]);
+      hb_store<T, RG>(io, dst, row, c0 * RC + e, tile[(e / RC) * PITCH + (e % RC)]);
   }
 }
 
@@ -325,7 +347,7 @@ __global__ __launch_bounds__((HbFuse<T, R>::THREADS)) void hb_mid2_kernel(const 
   const int64_t c = (L - row * nblk) * C + cl;
   const hb_c<T>* src = in + row * M;
   hb_c<T>* dst = out + row * M;
-  hb_row_setup<T>(io, row);
+  hb_row_setup<T>(io, row, M);
   const bool live = c < nbC;
   // ---- forward, last pass (Ns = nbC, so k = c) ----
   if (live) {
@@ -425,7 +447,7 @@ __global__ __launch_bounds__(MM_HB_THREADS) void hb_mid_kernel(const hb_c<T>* __
   const int64_t row = blockIdx.y;
   const hb_c<T>* src = in + row * M;
   hb_c<T>* dst = out + row * M;
-  hb_row_setup<T>(io, row);
+  hb_row_setup<T>(io, row, M);
   const bool live = j < nb;
   hb_c<T> v[R], v2[R];
   if (live) {
@@ -465,7 +487,7 @@ __global__ __launch_bounds__(MM_HB_THREADS) void hb_mid_kernel(const hb_c<T>* __
 }
 
 // One Stockham pass over rows of M complex points (see the header).  grid = (ceil(M / R / 128), rows).
-template <typename T, int R>
+template <typename T, int R, bool RG = false>
 __global__ __launch_bounds__(MM_HB_THREADS) void hb_pass_kernel(const hb_c<T>* __restrict__ in, hb_c<T>* __restrict__ out,
                                                                 int64_t M, int64_t Ns, const hb_c<double>* __restrict__ lo,
                                                                 const hb_c<double>* __restrict__ hi, HbIo<T> io) {
@@ -476,7 +498,7 @@ __global__ __launch_bounds__(MM_HB_THREADS) void hb_pass_kernel(const hb_c<T>* _
   const int64_t row = blockIdx.y;
   const hb_c<T>* src = in + row * M;
   hb_c<T>* dst = out + row * M;
-  hb_row_setup<T>(io, row);
+  hb_row_setup<T, RG>(io, row, M);
   const bool live = j < nb;
   hb_c<T> v[R];
   if (live) {
@@ -512,12 +534,12 @@ __global__ __launch_bounds__(MM_HB_THREADS) void hb_pass_kernel(const hb_c<T>* _
     const int64_t j0 = (int64_t)blockIdx.x * MM_HB_THREADS;
     const int64_t cnt = (nb - j0 < MM_HB_THREADS ? nb - j0 : MM_HB_THREADS) * R;
     for (int64_t e = threadIdx.x; e < cnt; e += MM_HB_THREADS)
-      hb_store(io, dst, row, j0 * R + e, tile[e + e / R]);
+      hb_store<T, RG>(io, dst, row, j0 * R + e, tile[e + e / R]);
   } else if (live) {
     const int64_t k = (int64_t)((uint32_t)j % (uint32_t)Ns);
     const int64_t m0 = (j - k) * R + k;
 #pragma unroll
-    for (int u = 0; u < R; ++u) hb_store(io, dst, row, m0 + u * Ns, v[hb_perm<R>(u)]);
+    for (int u = 0; u < R; ++u) hb_store<T, RG>(io, dst, row, m0 + u * Ns, v[hb_perm<R>(u)]);
   }
 }
 
@@ -551,6 +573,39 @@ __global__ __launch_bounds__(256) void hb_chirp_kernel(hb_c<double>* __restrict_
     sincospi((double)q / (double)n, &r.y, &r.x);
   }
   b[i] = r;
+}
+
+// The same chirp for every row of a ragged batch, each at its own length n = lens[row] (clamped into [1, n_max]), rounded
+// once to the clips' precision: b [rows][M] (the wrapped chirp, whose spectrum one batched hb_fft then takes) and
+// w [rows][n_max] = conj(b[k]), k < n.  On the way the clip is looked through once: a NaN or an infinity in [0, n) sets
+// bad[row] (zeroed by the caller), and the envelope store then writes NaN for that row.  scipy returns NaN for the WHOLE of
+// such a row; the transforms alone do not (an infinity leaves infinities behind: hypot(inf, NaN) = inf), hence the flag.
+// grid = (ceil(M / 256), rows).
+template <typename T>
+__global__ __launch_bounds__(256) void hb_chirp_ragged_kernel(const T* __restrict__ x, int64_t x_stride,
+                                                              const int64_t* __restrict__ lens, int64_t n_max, int64_t M,
+                                                              hb_c<T>* __restrict__ w, hb_c<T>* __restrict__ b,
+                                                              int* __restrict__ bad) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t row = blockIdx.y;
+  if (i >= M) return;
+  const int64_t len = lens[row];
+  const int64_t n = len < 1 ? 1 : (len > n_max ? n_max : len);
+  const int64_t k = i < n ? i : (M - i < n ? M - i : -1);
+  double c = 0.0, s = 0.0;
+  if (k >= 0) {
+    const unsigned long long q = ((unsigned long long)k * (unsigned long long)k) % (unsigned long long)(2 * n);
+    sincospi((double)q / (double)n, &s, &c);
+  }
+  hb_c<T> r;
+  r.x = (T)c; r.y = (T)s;
+  b[row * M + i] = r;
+  if (i < n) {
+    r.y = -r.y;
+    w[row * n_max + i] = r;
+    const T v = x[row * x_stride + i];
+    if (!((v < (T)0 ? -v : v) < (T)INFINITY)) atomicOr(bad + row, 1);
+  }
 }
 
 template <typename T>
@@ -629,6 +684,7 @@ struct mm_hilbert {
   int64_t n, M;
   int dtype;                       // 0 float32, 1 float64
   bool bluestein;
+  bool ragged;                     // mm_hilbert_ragged_create: n = the longest clip any call may bring, tables only (no w, bhat)
   int n_pass;
   int radix[32];
   int device;
@@ -638,9 +694,26 @@ struct mm_hilbert {
   void* hi;
 };
 
-template <typename T>
+template <typename T, bool RG = false>
 static void hb_launch_pass(int R, const hb_c<T>* in, hb_c<T>* out, int64_t M, int64_t Ns, int64_t rows,
                            const hb_c<double>* lo, const hb_c<double>* hi, const HbIo<T>& io, hipStream_t st) {
+  if constexpr (RG) {                   // a ragged batch: M is a power of two, so radix 256 (fused), 16, 8, 4 or 2
+    if (R == 256) {
+      constexpr int C = HbFuse<T, 16>::C;
+      const int64_t total = ((M / 256 + C - 1) / C) * rows;
+      hipLaunchKernelGGL((hb_pass2_kernel<T, 16, true>), dim3((unsigned)((total + 7) / 8 * 8)), dim3(C * 16), 0, st, in, out, M,
+                         Ns, rows, lo, hi, io);
+      return;
+    }
+    const dim3 grid((unsigned)((M / R + MM_HB_THREADS - 1) / MM_HB_THREADS), (unsigned)rows), block(MM_HB_THREADS);
+    switch (R) {
+      case 16: hipLaunchKernelGGL((hb_pass_kernel<T, 16, true>), grid, block, 0, st, in, out, M, Ns, lo, hi, io); break;
+      case 8: hipLaunchKernelGGL((hb_pass_kernel<T, 8, true>), grid, block, 0, st, in, out, M, Ns, lo, hi, io); break;
+      case 4: hipLaunchKernelGGL((hb_pass_kernel<T, 4, true>), grid, block, 0, st, in, out, M, Ns, lo, hi, io); break;
+      default: hipLaunchKernelGGL((hb_pass_kernel<T, 2, true>), grid, block, 0, st, in, out, M, Ns, lo, hi, io); break;
+    }
+    return;
+  }
   if (R == 256 || R == 625) {           // two passes of radix 16 / 25 fused
     if (R == 256) {
       constexpr int C = HbFuse<T, 16>::C;
@@ -698,7 +771,7 @@ static void hb_launch_mid(int R, const hb_c<T>* in, hb_c<T>* out, int64_t M, int
 // `reversed`: the passes in the opposite radix order (any order is a valid Stockham factorisation) -- what the last
 // pass writes decides how well its pointwise step coalesces: the fused radix-16 pair stores runs of 16 points, the
 // fused radix-25 pair runs of 10.
-template <typename T>
+template <typename T, bool RG = false>
 static void hb_fft(const mm_hilbert* h, hb_c<T>** cur, hb_c<T>** other, int64_t rows, const hb_c<double>* lo,
                    const hb_c<double>* hi, const HbIo<T>& io, hipStream_t st, bool reversed = false) {
   int64_t Ns = 1;
@@ -707,7 +780,7 @@ static void hb_fft(const mm_hilbert* h, hb_c<T>** cur, hb_c<T>** other, int64_t 
     if (i > 0) q.in_mode = HB_IN_COMPLEX;
     if (i + 1 < h->n_pass) q.out_mode = HB_OUT_COMPLEX;
     const int R = h->radix[reversed ? h->n_pass - 1 - i : i];
-    hb_launch_pass<T>(R, *cur, *other, h->M, Ns, rows, lo, hi, q, st);
+    hb_launch_pass<T, RG>(R, *cur, *other, h->M, Ns, rows, lo, hi, q, st);
     Ns *= R;
     std::swap(*cur, *other);
   }
@@ -724,6 +797,43 @@ static void hb_free(mm_hilbert* h) {
 
 #define MM_HB_MAX_N ((int64_t)1 << 24)
 #define MM_HB_MAXPART 4096        // partial maxima of hb_rowmax_kernel: about 2048 workgroups over all clips
+
+// the passes of M = 2^cnt[0] 3^cnt[1] 5^cnt[2] 7^cnt[3]
+static void hb_set_passes(mm_hilbert* h, int cnt[4]) {
+  const int primes[4] = {2, 3, 5, 7};
+  h->n_pass = 0;
+  for (; cnt[0] >= 8; cnt[0] -= 8) h->radix[h->n_pass++] = 256;    // two radix-16 passes fused (hb_pass2_kernel)
+  for (; cnt[0] >= 4; cnt[0] -= 4) h->radix[h->n_pass++] = 16;     // the widest power-of-two butterflies first
+  if (cnt[0]) h->radix[h->n_pass++] = 1 << cnt[0];
+  for (int i = 1; i < 4; ++i) {
+    if (primes[i] == 5)
+      for (; cnt[i] >= 4; cnt[i] -= 4) h->radix[h->n_pass++] = 625;  // two radix-25 passes fused
+    for (; cnt[i] >= 2; cnt[i] -= 2) h->radix[h->n_pass++] = primes[i] * primes[i];
+    if (cnt[i]) h->radix[h->n_pass++] = primes[i];
+  }
+}
+
+// the twiddle tables of h->M on the current device: allocated, the kernel that fills them enqueued on `st`
+static int hb_make_tables(mm_hilbert* h, hipStream_t st) {
+  if (hipGetDevice(&h->device) != hipSuccess) return MM_ERR_HIP;
+  const int64_t M = h->M;
+  const int64_t n_lo = M < MM_HB_TWLO ? M : MM_HB_TWLO, n_hi = (M + MM_HB_TWLO - 1) / MM_HB_TWLO;
+  if (hipMalloc(&h->lo, n_lo * sizeof(hb_c<double>)) != hipSuccess || hipMalloc(&h->hi, n_hi * sizeof(hb_c<double>)) != hipSuccess)
+    return MM_ERR_ALLOC;
+  const int64_t nt = n_lo > n_hi ? n_lo : n_hi;
+  hipLaunchKernelGGL(hb_tables_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, (hb_c<double>*)h->lo,
+                     (hb_c<double>*)h->hi, M);
+  return MM_OK;
+}
+
+// the power-of-two transform length of a clip of n samples through chirps: M = 2^p >= max(16, 2 n - 1)
+static int64_t hb_chirp_fft_size(int64_t n, int* log2_out) {
+  int64_t M = 16;
+  int p = 4;
+  while (M < 2 * n - 1) { M *= 2; ++p; }
+  if (log2_out) *log2_out = p;
+  return M;
+}
 
 extern "C" {
 
@@ -742,22 +852,11 @@ int mm_hilbert_create(int64_t n, int32_t dtype, mm_hilbert** out) {
   h->bluestein = rest != 1;
   int64_t M = n;
   if (h->bluestein) {
-    M = 16; cnt[0] = 4; cnt[1] = cnt[2] = cnt[3] = 0;
-    while (M < 2 * n - 1) { M *= 2; ++cnt[0]; }
+    cnt[1] = cnt[2] = cnt[3] = 0;
+    M = hb_chirp_fft_size(n, &cnt[0]);
   }
   h->M = M;
-  h->n_pass = 0;
-  for (; cnt[0] >= 8; cnt[0] -= 8) h->radix[h->n_pass++] = 256;    // two radix-16 passes fused (hb_pass2_kernel)
-  for (; cnt[0] >= 4; cnt[0] -= 4) h->radix[h->n_pass++] = 16;     // the widest power-of-two butterflies first
-  if (cnt[0]) h->radix[h->n_pass++] = 1 << cnt[0];
-  for (int i = 1; i < 4; ++i) {
-    if (primes[i] == 5)
-      for (; cnt[i] >= 4; cnt[i] -= 4) h->radix[h->n_pass++] = 625;  // two radix-25 passes fused
-    for (; cnt[i] >= 2; cnt[i] -= 2) h->radix[h->n_pass++] = primes[i] * primes[i];
-    if (cnt[i]) h->radix[h->n_pass++] = primes[i];
-  }
-  if (hipGetDevice(&h->device) != hipSuccess) { delete h; return MM_ERR_HIP; }
-  const int64_t n_lo = M < MM_HB_TWLO ? M : MM_HB_TWLO, n_hi = (M + MM_HB_TWLO - 1) / MM_HB_TWLO;
+  hb_set_passes(h, cnt);
   const size_t esz = dtype ? sizeof(hb_c<double>) : sizeof(hb_c<float>);
   hb_c<double>*b0 = nullptr, *b1 = nullptr;
   auto fail = [&](int rc) {
@@ -766,12 +865,12 @@ int mm_hilbert_create(int64_t n, int32_t dtype, mm_hilbert** out) {
     hb_free(h);
     return rc;
   };
-  if (hipMalloc(&h->lo, n_lo * sizeof(hb_c<double>)) != hipSuccess || hipMalloc(&h->hi, n_hi * sizeof(hb_c<double>)) != hipSuccess)
-    return fail(MM_ERR_ALLOC);
-  hb_c<double>*lo_d = (hb_c<double>*)h->lo, *hi_d = (hb_c<double>*)h->hi;
   hipStream_t st = nullptr;
-  const int64_t nt = n_lo > n_hi ? n_lo : n_hi;
-  hipLaunchKernelGGL(hb_tables_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, lo_d, hi_d, M);
+  {
+    const int rc = hb_make_tables(h, st);
+    if (rc != MM_OK) return fail(rc);
+  }
+  hb_c<double>*lo_d = (hb_c<double>*)h->lo, *hi_d = (hb_c<double>*)h->hi;
   if (h->bluestein) {
     if (hipMalloc(&b0, M * sizeof(hb_c<double>)) != hipSuccess || hipMalloc(&b1, M * sizeof(hb_c<double>)) != hipSuccess ||
         hipMalloc(&h->w, n * esz) != hipSuccess || hipMalloc(&h->bhat, M * esz) != hipSuccess)
@@ -794,12 +893,32 @@ int mm_hilbert_create(int64_t n, int32_t dtype, mm_hilbert** out) {
   return MM_OK;
 }
 
+// The handle of the ragged envelope: the transform length M of clips of up to n_max samples and its twiddle tables,
+// nothing that belongs to one length (every call brings its rows' chirps, mm_hilbert_envelope_ragged).
+int mm_hilbert_ragged_create(int64_t n_max, int32_t dtype, mm_hilbert** out) {
+  if (!out || n_max < 1 || n_max > MM_HB_MAX_N || dtype < 0 || dtype > 1) return MM_ERR_INVALID_ARG;
+  *out = nullptr;
+  mm_hilbert* h = new (std::nothrow) mm_hilbert();
+  if (!h) return MM_ERR_ALLOC;
+  h->dtype = dtype; h->bluestein = true; h->ragged = true;
+  int cnt[4] = {0, 0, 0, 0};
+  h->M = hb_chirp_fft_size(n_max, &cnt[0]);
+  h->n = h->M / 2;                   // every clip this M takes: 2 n - 1 <= M
+  hb_set_passes(h, cnt);
+  hipStream_t st = nullptr;
+  int rc = hb_make_tables(h, st);
+  if (rc == MM_OK && (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) rc = MM_ERR_HIP;
+  if (rc != MM_OK) { hb_free(h); return rc; }
+  *out = h;
+  return MM_OK;
+}
+
 void mm_hilbert_destroy(mm_hilbert* h) { hb_free(h); }
 
 int64_t mm_hilbert_fft_size(const mm_hilbert* h) { return h ? h->M : MM_ERR_INVALID_ARG; }
 
 size_t mm_hilbert_workspace_bytes(const mm_hilbert* h, int64_t rows) {
-  if (!h || rows < 1) return 0;
+  if (!h || rows < 1 || h->ragged) return 0;
   // two [pairs of clips][fft_size] complex buffers + the clips' maxima and scale factors
   const size_t pairs = (size_t)((rows + 1) / 2);
   return (size_t)2 * pairs * (size_t)h->M * (h->dtype ? sizeof(hb_c<double>) : sizeof(hb_c<float>)) + ((size_t)rows * 3 + MM_HB_MAXPART) * 8 + 256;
@@ -879,13 +998,75 @@ static int hb_envelope(const mm_hilbert* h, const T* d_x, int64_t rows, int64_t 
 
 extern "C" int mm_hilbert_envelope(mm_hilbert* h, const void* d_x, int64_t rows, int64_t x_stride, void* d_env,
                                    int64_t env_stride, void* d_ws, size_t ws_bytes, void* stream) {
-  if (!h || !d_x || !d_env || !d_ws || rows < 1 || rows > 65535 || x_stride < h->n || env_stride < h->n)
+  if (!h || !d_x || !d_env || !d_ws || rows < 1 || rows > 65535 || h->ragged || x_stride < h->n || env_stride < h->n)
     return MM_ERR_INVALID_ARG;
   if (ws_bytes < mm_hilbert_workspace_bytes(h, rows)) return MM_ERR_WORKSPACE;
   if ((h->M + 255) / 256 > 0x7FFFFFFF) return MM_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
   return h->dtype ? hb_envelope<double>(h, (const double*)d_x, rows, x_stride, (double*)d_env, env_stride, d_ws, st)
                   : hb_envelope<float>(h, (const float*)d_x, rows, x_stride, (float*)d_env, env_stride, d_ws, st);
+}
+
+// ---- a ragged batch: a length per clip ----
+// Workspace: bad [rows] int | w [rows][n_max] | three [rows][M] complex buffers (the chirps' spectra and the two the passes
+// alternate between), each part on a 256-byte boundary.
+static size_t hb_ragged_align(size_t b) { return (b + 255) / 256 * 256; }
+
+extern "C" size_t mm_hilbert_ragged_workspace_bytes(const mm_hilbert* h, int64_t rows, int64_t n_max) {
+  if (!h || !h->ragged || rows < 1 || n_max < 1 || n_max > h->n) return 0;
+  const size_t esz = h->dtype ? sizeof(hb_c<double>) : sizeof(hb_c<float>);
+  return hb_ragged_align((size_t)rows * sizeof(int)) + hb_ragged_align((size_t)rows * (size_t)n_max * esz) +
+         (size_t)3 * hb_ragged_align((size_t)rows * (size_t)h->M * esz);
+}
+
+template <typename T>
+static int hb_envelope_ragged(const mm_hilbert* h, const T* d_x, int64_t rows, int64_t n_max, int64_t x_stride,
+                              const int64_t* d_lens, T* d_env, int64_t env_stride, void* d_ws, hipStream_t st) {
+  const int64_t M = h->M;
+  char* p = (char*)d_ws;
+  int* bad = (int*)p;
+  p += hb_ragged_align((size_t)rows * sizeof(int));
+  hb_c<T>* w = (hb_c<T>*)p;
+  p += hb_ragged_align((size_t)rows * (size_t)n_max * sizeof(hb_c<T>));
+  const size_t buf = hb_ragged_align((size_t)rows * (size_t)M * sizeof(hb_c<T>));
+  hb_c<T>* bhat = (hb_c<T>*)p;
+  hb_c<T>* spare = (hb_c<T>*)(p + buf);
+  hb_c<T>* third = (hb_c<T>*)(p + 2 * buf);
+  const hb_c<double>*lo = (const hb_c<double>*)h->lo, *hi = (const hb_c<double>*)h->hi;
+  HIP_TRY(hipMemsetAsync(bad, 0, (size_t)rows * sizeof(int), st));
+  // every row's chirp at its own length, and the chirps' spectra: one batched transform in the clips' precision
+  hipLaunchKernelGGL(hb_chirp_ragged_kernel<T>, dim3((unsigned)((M + 255) / 256), (unsigned)rows), dim3(256), 0, st, d_x, x_stride,
+                     d_lens, n_max, M, w, bhat, bad);
+  HbIo<T> plain = {};
+  hb_fft<T>(h, &bhat, &spare, rows, lo, hi, plain, st);
+  // the four transforms of hb_envelope's chirp branch, one clip per row, n / w / bhat / scale the row's own
+  hb_c<T>*cur = spare, *other = third;
+  HbIo<T> io = {};
+  io.x = d_x; io.x_stride = x_stride; io.w = w; io.bhat = bhat; io.env = d_env; io.env_stride = env_stride;
+  io.n = n_max; io.n_max = n_max; io.x_rows = rows; io.lens = d_lens; io.bad = bad;
+  io.in_mode = HB_IN_REAL_CHIRP; io.out_mode = HB_OUT_MUL_CONJ;
+  hb_fft<T, true>(h, &cur, &other, rows, lo, hi, io, st);
+  io.in_mode = HB_IN_COMPLEX; io.out_mode = HB_OUT_BLUESTEIN_MID; io.scale = (T)(1.0 / (double)M);
+  hb_fft<T, true>(h, &cur, &other, rows, lo, hi, io, st);
+  io.out_mode = HB_OUT_MUL_CONJ;
+  hb_fft<T, true>(h, &cur, &other, rows, lo, hi, io, st);
+  io.out_mode = HB_OUT_ENVELOPE;               // (the scale 1 / (M n_b): hb_row_setup)
+  hb_fft<T, true>(h, &cur, &other, rows, lo, hi, io, st);
+  HIP_TRY(hipGetLastError());
+  return MM_OK;
+}
+
+extern "C" int mm_hilbert_envelope_ragged(mm_hilbert* h, const void* d_x, int64_t rows, int64_t n_max, int64_t x_stride,
+                                          const int64_t* d_lens, void* d_env, int64_t env_stride, void* d_ws, size_t ws_bytes,
+                                          void* stream) {
+  if (rows < 1 || rows > 65535 || !h || !d_x || !d_lens || !d_env || !d_ws) return MM_ERR_INVALID_ARG;
+  if (!h->ragged || n_max < 1 || n_max > h->n || x_stride < n_max || env_stride < n_max) return MM_ERR_INVALID_ARG;
+  if (ws_bytes < mm_hilbert_ragged_workspace_bytes(h, rows, n_max)) return MM_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  return h->dtype ? hb_envelope_ragged<double>(h, (const double*)d_x, rows, n_max, x_stride, d_lens, (double*)d_env, env_stride,
+                                               d_ws, st)
+                  : hb_envelope_ragged<float>(h, (const float*)d_x, rows, n_max, x_stride, d_lens, (float*)d_env, env_stride,
+                                              d_ws, st);
 }
 
 // rFFT of real float32 rows, zero-padded to the plan's length: the forward transform alone (the rows ride in on the first

@@ -1,21 +1,44 @@
 // libmodmfcc: the rows either side of the path that need no MFCC plan -- RMS and Hilbert
-// amplitude envelopes (script/calc.py:284-343), PCM decode and sample-rate conversion of what librosa.load reads
-// (script/mfcc.py:284,373) -- and the bench's device-copy kernel.  gfx950 only.
+// amplitude envelopes (script/calc.py:284-343; also for a padded batch with a length per clip), PCM decode and
+// sample-rate conversion of what librosa.load reads (script/mfcc.py:284,373) -- and the bench's device-copy kernel.
+// gfx950 only.
 #include "mm_common.h"
 
 #include "mm_hilbert.hip.inc"
 #include "mm_resample.hip.inc"
 
-extern "C" {
+// A ragged batch (kRagged: mm_rms_ragged_f32): n_samples and n_out are those of the LONGEST clip and lay out the grid and
+// the rows of `out`; clip b has lens[b] samples (clamped into [1, n_samples]) and its own frame count, is padded about its
+// own ends, and its row is +0.0 behind its last frame -- or NaN throughout where it is too short for one frame.
+struct RmsClip { int64_t n, frames; };
+__device__ __forceinline__ RmsClip rms_clip(const int64_t* __restrict__ lens, int64_t b, int64_t n_max, int frame_length, int hop,
+                                            int pad) {
+  const int64_t len = lens[b];
+  RmsClip c;
+  c.n = len < 1 ? 1 : (len > n_max ? n_max : len);
+  const int64_t padded = c.n + 2 * (int64_t)pad;
+  c.frames = padded < frame_length ? -1 : 1 + (padded - frame_length) / hop;
+  return c;
+}
 
 // one wave per output frame: coalesced strided sum of squares, zero padding outside the clip
+template <bool kRagged>
 __global__ __launch_bounds__(256) void rms_frames_kernel(const float* __restrict__ audio, int64_t n_samples,
                                                          int64_t stride, int frame_length, int hop, int pad,
-                                                         int64_t n_out, int64_t total, float* __restrict__ out) {
+                                                         int64_t n_out, int64_t total, const int64_t* __restrict__ lens,
+                                                         float* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (w >= total) return;
   const int64_t b = w / n_out, t = w - b * n_out;
+  if constexpr (kRagged) {
+    const RmsClip c = rms_clip(lens, b, n_samples, frame_length, hop, pad);
+    n_samples = c.n;
+    if (t >= c.frames) {
+      if (lane == 0) out[w] = c.frames < 0 ? NAN : 0.0f;
+      return;
+    }
+  }
   const float* a = audio + b * stride;
   const int64_t start = t * hop - pad;
   float acc = 0.0f;
@@ -33,15 +56,25 @@ __global__ __launch_bounds__(256) void rms_frames_kernel(const float* __restrict
 // one clip into LDS once (frames overlap frame_length/hop times), then every wave sums whole frames
 // from LDS in the same order as rms_frames_kernel (lane-strided, then a butterfly): same bits, each
 // sample read from global memory ~once instead of frame_length/hop times.
+template <bool kRagged>
 __global__ __launch_bounds__(256) void rms_tile_kernel(const float* __restrict__ audio, int64_t n_samples,
                                                        int64_t stride, int frame_length, int hop, int pad,
                                                        int64_t n_out, int frames_per_tile, int64_t tiles_per_clip,
-                                                       float* __restrict__ out) {
+                                                       const int64_t* __restrict__ lens, float* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) float rms_sq[];
   float* sq = rms_sq;
   const int64_t b = blockIdx.x / tiles_per_clip, tile = blockIdx.x - b * tiles_per_clip;
   const int64_t t0 = tile * frames_per_tile;
-  const int nf = (int)((n_out - t0) < frames_per_tile ? (n_out - t0) : frames_per_tile);
+  int nf = (int)((n_out - t0) < frames_per_tile ? (n_out - t0) : frames_per_tile);
+  if constexpr (kRagged) {
+    // the tile's frames behind the clip's last one only get their filler; the others are summed as in the clip's own call
+    const RmsClip c = rms_clip(lens, b, n_samples, frame_length, hop, pad);
+    n_samples = c.n;
+    const int live = (int)(c.frames - t0 < 0 ? 0 : (c.frames - t0 < nf ? c.frames - t0 : nf));
+    for (int f = live + threadIdx.x; f < nf; f += 256) out[b * n_out + t0 + f] = c.frames < 0 ? NAN : 0.0f;
+    if (live == 0) return;
+    nf = live;
+  }
   const int span = (nf - 1) * hop + frame_length;
   const float* a = audio + b * stride;
   const int64_t start = t0 * hop - pad;
@@ -68,6 +101,8 @@ __global__ __launch_bounds__(256) void rms_tile_kernel(const float* __restrict__
   }
 }
 
+extern "C" {
+
 int64_t mm_rms_num_frames(int64_t n_samples, int32_t frame_length, int32_t hop_length, int32_t center) {
   if (n_samples < 1 || frame_length < 1 || hop_length < 1) return MM_ERR_INVALID_ARG;
   const int64_t padded = n_samples + (center ? 2 * (int64_t)(frame_length / 2) : 0);
@@ -75,8 +110,9 @@ int64_t mm_rms_num_frames(int64_t n_samples, int32_t frame_length, int32_t hop_l
   return 1 + (padded - frame_length) / hop_length;
 }
 
-int mm_rms_f32(const float* d_audio, int64_t batch, int64_t n_samples, int64_t stride, int32_t frame_length,
-               int32_t hop_length, int32_t center, float* d_rms, void* stream) {
+// mm_rms_f32 (d_lens null) and mm_rms_ragged_f32: the same launch shape, that of n_samples
+static int rms_launch(const float* d_audio, int64_t batch, int64_t n_samples, int64_t stride, const int64_t* d_lens,
+                      int32_t frame_length, int32_t hop_length, int32_t center, float* d_rms, void* stream) {
   if (!d_audio || !d_rms || batch < 1 || stride < n_samples) return MM_ERR_INVALID_ARG;
   const int64_t n_out = mm_rms_num_frames(n_samples, frame_length, hop_length, center);
   if (n_out < 0) return (int)n_out;
@@ -92,18 +128,39 @@ int mm_rms_f32(const float* d_audio, int64_t batch, int64_t n_samples, int64_t s
     const int64_t tpc = (n_out + fpt - 1) / fpt;
     if (batch * tpc > 0x7FFFFFFF) return MM_ERR_INVALID_ARG;
     const size_t lds = (size_t)((fpt - 1) * hop_length + frame_length) * 4;
-    hipLaunchKernelGGL(rms_tile_kernel, dim3((unsigned)(batch * tpc)), dim3(256), lds, (hipStream_t)stream, d_audio,
-                       n_samples, stride, frame_length, hop_length, center ? frame_length / 2 : 0, n_out, (int)fpt, tpc,
-                       d_rms);
+    const dim3 grid((unsigned)(batch * tpc)), block(256);
+    const int pad = center ? frame_length / 2 : 0;
+    if (d_lens)
+      hipLaunchKernelGGL(rms_tile_kernel<true>, grid, block, lds, (hipStream_t)stream, d_audio, n_samples, stride, frame_length,
+                         hop_length, pad, n_out, (int)fpt, tpc, d_lens, d_rms);
+    else
+      hipLaunchKernelGGL(rms_tile_kernel<false>, grid, block, lds, (hipStream_t)stream, d_audio, n_samples, stride, frame_length,
+                         hop_length, pad, n_out, (int)fpt, tpc, d_lens, d_rms);
     HIP_TRY(hipGetLastError());
     return MM_OK;
   }
   const int64_t grid = (total + 3) / 4;
   if (grid > 0x7FFFFFFF) return MM_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(rms_frames_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, d_audio,
-                     n_samples, stride, frame_length, hop_length, center ? frame_length / 2 : 0, n_out, total, d_rms);
+  const int pad = center ? frame_length / 2 : 0;
+  if (d_lens)
+    hipLaunchKernelGGL(rms_frames_kernel<true>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, d_audio, n_samples,
+                       stride, frame_length, hop_length, pad, n_out, total, d_lens, d_rms);
+  else
+    hipLaunchKernelGGL(rms_frames_kernel<false>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, d_audio, n_samples,
+                       stride, frame_length, hop_length, pad, n_out, total, d_lens, d_rms);
   HIP_TRY(hipGetLastError());
   return MM_OK;
+}
+
+int mm_rms_f32(const float* d_audio, int64_t batch, int64_t n_samples, int64_t stride, int32_t frame_length,
+               int32_t hop_length, int32_t center, float* d_rms, void* stream) {
+  return rms_launch(d_audio, batch, n_samples, stride, nullptr, frame_length, hop_length, center, d_rms, stream);
+}
+
+int mm_rms_ragged_f32(const float* d_audio, int64_t batch, int64_t n_max, int64_t stride, const int64_t* d_lens,
+                      int32_t frame_length, int32_t hop_length, int32_t center, float* d_rms, void* stream) {
+  if (!d_lens) return MM_ERR_INVALID_ARG;
+  return rms_launch(d_audio, batch, n_max, stride, d_lens, frame_length, hop_length, center, d_rms, stream);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -18,7 +18,7 @@ from . import filters as _filters
 from . import tail as _tail
 from .plan import MfccConfig, get_plan
 
-__all__ = ["applyFilter", "get_amplitude", "load_channel", "get_MFCCS_change", "get_MFCCS_change_batch", "mfcc_array"]
+__all__ = ["applyFilter", "get_amplitude", "get_amplitude_batch", "load_channel", "get_MFCCS_change", "get_MFCCS_change_batch", "mfcc_array"]
 
 applyFilter = _filters.applyFilter
 
@@ -64,6 +64,12 @@ def get_amplitude(x, sr, /, *, method: str = "RMS", winLen: float = 0.1, hopLen:
                                         center=center, outFilter=outFilter, outFiltType=outFiltType,
                                         outFiltCutOff=outFiltCutOff, outFiltLen=outFiltLen,
                                         outFiltPolyOrd=outFiltPolyOrd)
+
+
+def get_amplitude_batch(clips, sr, /, **kw):
+    """get_amplitude for a list of clips of any lengths -- same function as calc.calculate_amplitude_envelope_batch."""
+    from .calc import calculate_amplitude_envelope_batch
+    return calculate_amplitude_envelope_batch(clips, sr, **kw)
 
 
 def get_MFCCS_change(audioIn, sigSr, /, *, channelN: int = 0, tStep: float = 0.001,
