@@ -3,6 +3,7 @@ GUI thread, script/main.py:750-769).  All tensors are float32 / complex64 on the
 """
 from __future__ import annotations
 
+from . import ragged
 from .plan import MfccConfig, get_plan
 
 
@@ -43,17 +44,14 @@ def mfcc_change_ragged_batch(audio, lengths, cfg: MfccConfig, *, tStep=None, **t
     (tail.mfcc_change_ragged_device, whose keywords -- removeFirst, filtCutoff, filtOrd, diffMethod, outFilter, ... -- pass
     through; tStep defaults to the configuration's hop_length / sr); nothing leaves the device.  Host `lengths` are
     validated on the host: a clip with too few frames for the filters raises scipy's ValueError (device lengths: NaN)."""
-    import numpy as np
-    import torch
     from . import tail as _tail
     plan = get_plan(cfg)
     if tStep is None:
         tStep = cfg.hop_length / cfg.sr
     mfcc, frames = plan.mfcc_ragged(audio, lengths)
     fr = frames
-    if not (isinstance(lengths, torch.Tensor) and lengths.is_cuda):      # host lengths: host frame counts, validated by the tail
-        lens = lengths.numpy() if isinstance(lengths, torch.Tensor) else np.asarray(lengths)
-        fr = 1 + (lens.astype(np.int64) - (cfg.n_fft - 2 * (cfg.n_fft // 2))) // cfg.hop_length
+    if not ragged.is_device_tensor(lengths):        # host lengths: host frame counts, validated by the tail
+        fr = ragged.stft_frames(lengths, cfg.n_fft, cfg.hop_length)
     return _tail.mfcc_change_ragged_device(plan, mfcc, fr, tStep=tStep, **tail), frames
 
 
@@ -73,11 +71,8 @@ def pack_clips(clips, dtype=None):
             raise ValueError(f"pack_clips: clips on {clips[0].device} and {c.device}")
         if c.shape[0] < 1:
             raise ValueError("pack_clips: empty clip")
-    lengths = torch.tensor([c.shape[0] for c in clips], dtype=torch.int64)
-    audio = torch.empty((len(clips), int(lengths.max())), dtype=dtype, device=clips[0].device)
-    for b, c in enumerate(clips):
-        audio[b, :c.shape[0]].copy_(c, non_blocking=True)
-    return audio, lengths
+    audio, lengths = ragged.pack(clips, dtype)
+    return audio, torch.from_numpy(lengths)
 
 
 def rfft_batch(rows, n: int, cfg: MfccConfig = None, out=None):
@@ -93,7 +88,7 @@ def rms_batch(audio, frame_length: int, hop_length: int, center: bool = True):
     import torch
     from . import _lib
     lib = _lib.load()
-    if not (isinstance(audio, torch.Tensor) and audio.is_cuda and audio.dtype == torch.float32):
+    if not (ragged.is_device_tensor(audio) and audio.dtype == torch.float32):
         raise TypeError("audio must be a float32 CUDA(HIP) tensor")
     if audio.dim() == 1:
         audio = audio.unsqueeze(0)
@@ -110,13 +105,7 @@ def rms_batch(audio, frame_length: int, hop_length: int, center: bool = True):
     return out
 
 
-def rms_ragged_frames(lengths, frame_length, hop_length, center=True):
-    """RMS frames of clips of ``lengths`` samples (host integers) -> int64 numpy array: mm_rms_num_frames per clip, 0 for a
-    clip too short for one frame (only without centring).  No GPU needed."""
-    import numpy as np
-    n = np.asarray(lengths, dtype=np.int64)
-    padded = n + (2 * (int(frame_length) // 2) if center else 0)
-    return np.where((n >= 1) & (padded >= frame_length), 1 + (padded - int(frame_length)) // int(hop_length), 0).astype(np.int64)
+rms_ragged_frames = ragged.centered_frames      # RMS frames of clips of ``lengths`` samples: mm_rms_num_frames per clip
 
 
 def rms_ragged_batch(audio, lengths, frame_length: int, hop_length: int, center: bool = True):
@@ -129,33 +118,24 @@ def rms_ragged_batch(audio, lengths, frame_length: int, hop_length: int, center:
     centring, the clip named) or an int64 device tensor (no read-back; the kernels clamp it, and a clip without a frame gets
     a NaN row).  One launch, that of n_max."""
     import ctypes as C
-    import numpy as np
     import torch
     from . import _lib
-    from .plan import check_lengths
     lib = _lib.load()
-    if not (isinstance(audio, torch.Tensor) and audio.is_cuda and audio.dtype == torch.float32):
-        raise TypeError("audio must be a float32 CUDA(HIP) tensor")
-    if audio.dim() != 2:
-        raise ValueError("audio must be [B, n_max]")
+    audio = ragged.device_rows(audio, (torch.float32,), "audio must be a float32 CUDA(HIP) tensor", "audio must be [B, n_max]",
+                               nonempty=False)
     B, n = audio.shape
-    if (n > 1 and audio.stride(1) != 1) or (B > 1 and audio.stride(0) < n):
-        audio = audio.contiguous()
-    lens = check_lengths(lengths, B, n, audio.device)
+    lens = ragged.check_lengths(lengths, B, n, audio.device)
     frame_length, hop_length, center = int(frame_length), int(hop_length), 1 if center else 0
     t_max = lib.mm_rms_num_frames(n, frame_length, hop_length, center)
     if t_max < 0:
         _lib.check(int(t_max), "mm_rms_num_frames")
-    if isinstance(lens, np.ndarray):
-        none = np.flatnonzero(rms_ragged_frames(lens, frame_length, hop_length, center) < 1)
-        if none.size:
-            raise ValueError(f"rms: a clip of {int(lens[none[0]])} samples is shorter than frame_length={frame_length} "
-                             f"(clip {int(none[0])})")
+    ragged.refuse_short(lens, n, 1 if center else frame_length,
+                        lambda short: f"rms: a clip of {short} samples is shorter than frame_length={frame_length}", "clip", None)
     out = torch.empty((B, t_max), dtype=torch.float32, device=audio.device)
     with torch.cuda.device(audio.device):
-        lens_dev = torch.from_numpy(lens).to(audio.device, non_blocking=True) if isinstance(lens, np.ndarray) else lens
+        lens_dev = ragged.counts_on_device(lens, audio.device)
         stream = C.c_void_p(torch.cuda.current_stream(audio.device).cuda_stream)
-        _lib.check(lib.mm_rms_ragged_f32(audio.data_ptr(), B, n, audio.stride(0) if B > 1 else n,
+        _lib.check(lib.mm_rms_ragged_f32(audio.data_ptr(), B, n, ragged.row_pitch(audio),
                                          lens_dev.data_ptr(), frame_length, hop_length, center, out.data_ptr(), stream),
                    "mm_rms_ragged_f32")
     return out

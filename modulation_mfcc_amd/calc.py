@@ -14,6 +14,7 @@ from __future__ import annotations
 import numpy as np
 from scipy.signal import savgol_filter
 
+from . import ragged
 from .filters import applyFilter
 from .pitch import get_f0, get_f0_batch, interp_NAN, interp_nan_batch, interp_nan_ragged_batch  # noqa: F401
 from .ema import read_AG50x, read_AG50x_arrays, read_pos_header  # noqa: F401
@@ -24,10 +25,6 @@ __all__ = ["applyFilter", "get_f0", "get_f0_batch", "interp_NAN", "interp_nan_ba
            "hilbert_envelope_batch", "amplitude_envelope_batch", "hilbert_envelope_ragged_batch",
            "amplitude_envelope_ragged_batch", "calculate_amplitude_envelope_batch", "find_peaks_batch", "find_peaks_ex_batch",
            "peaks_to_list", "MinMaxFinder"]
-
-
-def _is_device_tensor(x):
-    return type(x).__module__.startswith("torch") and getattr(x, "is_cuda", False)
 
 
 import collections
@@ -97,7 +94,7 @@ def rfft_rows_long(x, n_fft, out=None):
     reference's default 1 ms step (script/mfcc.py:296).  Rows are taken in chunks that bound the workspace."""
     import torch
     from . import _lib
-    if not (_is_device_tensor(x) and x.dtype == torch.float32 and x.dim() == 2):
+    if not (ragged.is_device_tensor(x) and x.dtype == torch.float32 and x.dim() == 2):
         raise TypeError("x must be a float32 CUDA(HIP) tensor [rows, T]")
     if x.stride(1) != 1:
         x = x.contiguous()
@@ -133,7 +130,7 @@ def hilbert_envelope_batch(x):
     import ctypes as C
     import torch
     from . import _lib
-    if not (_is_device_tensor(x) and x.dtype in (torch.float32, torch.float64)):
+    if not (ragged.is_device_tensor(x) and x.dtype in (torch.float32, torch.float64)):
         raise TypeError("x must be a float32 / float64 CUDA(HIP) tensor")
     squeeze = x.dim() == 1
     x2 = x.unsqueeze(0) if squeeze else x
@@ -168,8 +165,7 @@ def hilbert_ragged_fft_size(n):
 
 def _hilbert_ragged_classes(lens):
     """Host lengths [B] -> [(M, int64 index array of the rows whose own transform length is M)], ascending M."""
-    M = np.array([hilbert_ragged_fft_size(n) for n in lens], dtype=np.int64)
-    return [(int(m), np.flatnonzero(M == m).astype(np.int64)) for m in np.unique(M)]
+    return ragged.group_rows([hilbert_ragged_fft_size(n) for n in lens])
 
 
 def _hilbert_ragged_rows(x2, lens_dev, M):
@@ -187,11 +183,10 @@ def _hilbert_ragged_rows(x2, lens_dev, M):
     chunk = int(max(1, min(rows, 65535, HILBERT_WS_BYTES // max(per_row, 1))))
     ws = torch.empty(int(lib.mm_hilbert_ragged_workspace_bytes(plan.h, chunk, n)), dtype=torch.uint8, device=x2.device)
     stream = C.c_void_p(torch.cuda.current_stream(x2.device).cuda_stream)
-    stride = x2.stride(0) if rows > 1 else n
     with torch.cuda.device(x2.device):
         for r0 in range(0, rows, chunk):
             r = min(chunk, rows - r0)
-            _lib.check(lib.mm_hilbert_envelope_ragged(plan.h, x2[r0:].data_ptr(), r, n, stride, lens_dev[r0:].data_ptr(),
+            _lib.check(lib.mm_hilbert_envelope_ragged(plan.h, x2[r0:].data_ptr(), r, n, ragged.row_pitch(x2), lens_dev[r0:].data_ptr(),
                                                       out[r0:].data_ptr(), n, ws.data_ptr(), ws.numel(), stream),
                        "mm_hilbert_envelope_ragged")
     return out
@@ -214,21 +209,16 @@ def hilbert_envelope_ragged_batch(x, lengths):
     pairing): the unnormalised transforms reach max(envelope) n_b M, so a float32 clip stays finite where scipy does only
     while that product is below 3.4e38 -- amplitudes up to about 1e27 at ten seconds of 16 kHz, 6e23 at 2^24 samples."""
     import torch
-    from .plan import check_lengths
-    if not (_is_device_tensor(x) and x.dtype in (torch.float32, torch.float64)):
-        raise TypeError("x must be a float32 / float64 CUDA(HIP) tensor")
-    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError("x must be [B, n_max], at least one row and one column")
+    x = ragged.device_rows(x, (torch.float32, torch.float64), "x must be a float32 / float64 CUDA(HIP) tensor",
+                           "x must be [B, n_max], at least one row and one column")
     B, n_max = x.shape
-    if (n_max > 1 and x.stride(1) != 1) or (B > 1 and x.stride(0) < n_max):
-        x = x.contiguous()
-    lens = check_lengths(lengths, B, n_max, x.device)
+    lens = ragged.check_lengths(lengths, B, n_max, x.device)
     if not isinstance(lens, np.ndarray):
         return _hilbert_ragged_rows(x, lens, hilbert_ragged_fft_size(n_max))
     out = None
     for M, idx in _hilbert_ragged_classes(lens):
         n_c = int(lens[idx].max())              # the class's calls are cut to its longest clip: M covers n_c, not n_max
-        lens_c = torch.from_numpy(lens[idx]).to(x.device)
+        lens_c = ragged.counts_on_device(lens[idx], x.device)
         if len(idx) == B and n_c == n_max:      # one class that fills the batch: as it is, no gather
             return _hilbert_ragged_rows(x, lens_c, M)
         if out is None:
@@ -248,26 +238,20 @@ def amplitude_envelope_ragged_batch(x, lengths, sr, *, method: str = "RMS", winL
     amplitude_envelope_batch gives for x[b, :lengths[b]] alone in its first out_lengths[b] columns ('RMS': bit for bit,
     batch.rms_ragged_batch; 'Hilb': hilbert_envelope_ragged_batch) and +0.0 behind them.  ``out_lengths`` is a numpy array
     for host lengths and a device tensor for device lengths (the clamped lengths for 'Hilb', the frame counts for 'RMS')."""
-    from .batch import rms_ragged_batch, rms_ragged_frames
+    from .batch import rms_ragged_batch
+
+    def seen():     # the lengths as the kernels see them: device lengths clamped, with no read-back
+        return lengths.clamp(1, x.shape[1]) if ragged.is_device_tensor(lengths) else np.asarray(lengths, dtype=np.int64)
     if method == "Hilb":
         env = hilbert_envelope_ragged_batch(x, lengths)
-        out_len = lengths.clamp(1, x.shape[1]) if _is_device_tensor(lengths) else np.asarray(lengths, dtype=np.int64)
-        return env, out_len, 1 / hopLen                   # the reference's rate quirk, as in amplitude_envelope_batch
+        return env, seen(), 1 / hopLen                    # the reference's rate quirk, as in amplitude_envelope_batch
     if method == "RMS":
         import torch
         xf = x if x.dtype == torch.float32 else x.float()
         frame, hop = int(winLen * sr), int(hopLen * sr)
         env = rms_ragged_batch(xf, lengths, frame, hop, center)
-        if _is_device_tensor(lengths):
-            padded = lengths.clamp(1, x.shape[1]) + (2 * (frame // 2) if center else 0)
-            out_len = torch.where(padded >= frame, 1 + torch.div(padded - frame, hop, rounding_mode="floor"),
-                                  torch.zeros_like(padded))
-        else:
-            out_len = rms_ragged_frames(np.asarray(lengths), frame, hop, center)
-        return env, out_len, 1 / hopLen
-    if method == "RMSpraat":
-        raise NotImplementedError("method='RMSpraat' calls Praat through parselmouth; not part of this build")
-    raise UnboundLocalError(f"unknown amplitude method {method!r}")
+        return env, ragged.centered_frames(seen(), frame, hop, center), 1 / hopLen
+    _envelope_method(method)        # neither: its refusal
 
 
 def amplitude_envelope_batch(x, sr, *, method: str = "RMS", winLen: float = 0.1, hopLen: float = 0.01,
@@ -285,9 +269,29 @@ def amplitude_envelope_batch(x, sr, *, method: str = "RMS", winLen: float = 0.1,
         squeeze = xf.dim() == 1
         env = rms_batch(xf, int(winLen * sr), int(hopLen * sr), center)
         return (env[0] if squeeze else env), 1 / hopLen
+    _envelope_method(method)        # neither: its refusal
+
+
+def _envelope_method(method):
+    """The refusals of calculate_amplitude_envelope and its list form."""
     if method == "RMSpraat":
         raise NotImplementedError("method='RMSpraat' calls Praat through parselmouth; not part of this build")
-    raise UnboundLocalError(f"unknown amplitude method {method!r}")
+    if method not in ("Hilb", "RMS"):
+        raise UnboundLocalError(f"unknown amplitude method {method!r}")   # reference: `amp` unbound
+
+
+def _envelope_signal(x, method):
+    """The signal of calculate_amplitude_envelope and its list form on the device: a CUDA(HIP) tensor as it is, a host
+    signal in the precision the reference computes it in -- librosa.feature.rms / scipy.signal.hilbert keep float32 input
+    in single precision, anything else in double."""
+    if ragged.is_device_tensor(x):
+        return x
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("modulation_mfcc_amd needs an AMD GPU (gfx950); there is no CPU fallback")
+    xa = np.asarray(x)
+    return torch.from_numpy(np.ascontiguousarray(xa, dtype=np.float32 if (method == "RMS" or xa.dtype == np.float32)
+                                                 else np.float64)).cuda()
 
 
 def calculate_amplitude_envelope(x, sr, /, *, method: str = "RMS", winLen: float = 0.1,
@@ -300,22 +304,9 @@ def calculate_amplitude_envelope(x, sr, /, *, method: str = "RMS", winLen: float
     returns numpy arrays like the reference (its output filter, a short per-frame curve, then runs through the
     reference's own scipy calls on the host); a CUDA(HIP) tensor ([n] or a batch [B, n]) returns device tensors and
     is filtered on the device too (applyFilter's device branch)."""
-    if method == "RMSpraat":
-        raise NotImplementedError("method='RMSpraat' calls Praat through parselmouth; not part of this build")
-    if method not in ("Hilb", "RMS"):
-        raise UnboundLocalError(f"unknown amplitude method {method!r}")   # reference: `amp` unbound
-    import torch
-    on_device = _is_device_tensor(x)
-    if on_device:
-        xd = x
-    else:
-        from .plan import _torch  # noqa: F401
-        if not torch.cuda.is_available():
-            raise RuntimeError("modulation_mfcc_amd needs an AMD GPU (gfx950); there is no CPU fallback")
-        xa = np.asarray(x)
-        # librosa.feature.rms / scipy.signal.hilbert keep float32 input in single precision, anything else in double
-        xd = torch.from_numpy(np.ascontiguousarray(xa, dtype=np.float32 if (method == "RMS" or xa.dtype == np.float32)
-                                                   else np.float64)).cuda()
+    _envelope_method(method)
+    on_device = ragged.is_device_tensor(x)
+    xd = _envelope_signal(x, method)
     env, env_sr = amplitude_envelope_batch(xd, sr, method=method, winLen=winLen, hopLen=hopLen, center=center)
     # the reference tests method != 'hilb' (lower case), so 'Hilb' ALSO gets hop-spaced time stamps
     # and the 1/hopLen rate for its output filter (script/calc.py:333-337); kept as is.
@@ -340,51 +331,36 @@ def calculate_amplitude_envelope_batch(clips, sr, /, *, method: str = "RMS", win
     ``outFilter`` is ONE filters.apply_filter_ragged_batch on the padded envelopes at the rate 1 / hopLen -- for numpy clips
     too, whose single call filters with scipy on the host (equal to rounding) -- and one copy brings the numpy results back.
     A clip the single call refuses raises that call's exception with the clip's index appended."""
-    if method == "RMSpraat":
-        raise NotImplementedError("method='RMSpraat' calls Praat through parselmouth; not part of this build")
-    if method not in ("Hilb", "RMS"):
-        raise UnboundLocalError(f"unknown amplitude method {method!r}")   # reference: `amp` unbound
+    _envelope_method(method)
     import torch
     from .batch import pack_clips
-    from .filters import RowRefused, apply_filter_ragged_batch
-    from .pitch import _blame_clip
+    from .filters import apply_filter_ragged_batch
     clips = list(clips)
-    if not clips:
-        return []
-    on_device = [_is_device_tensor(c) for c in clips]
-    if not all(on_device) and not torch.cuda.is_available():
-        raise RuntimeError("modulation_mfcc_amd needs an AMD GPU (gfx950); there is no CPU fallback")
-    sigs = []
-    for i, (c, d) in enumerate(zip(clips, on_device)):
-        if not d:
-            a = np.asarray(c)
-            # librosa.feature.rms / scipy.signal.hilbert keep float32 input in single precision, anything else in double
-            c = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32 if (method == "RMS" or a.dtype == np.float32)
-                                                      else np.float64)).cuda()
-        elif method == "RMS":
-            c = c if c.dtype == torch.float32 else c.float()
+    on_device = [ragged.is_device_tensor(c) for c in clips]
+    sigs = [_envelope_signal(c, method) for c in clips]
+    for i, c in enumerate(sigs):
+        if method == "RMS":
+            sigs[i] = c = c if c.dtype == torch.float32 else c.float()
         elif c.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"x must be a float32 / float64 CUDA(HIP) tensor (clip {i})")
+            raise ragged.named(TypeError("x must be a float32 / float64 CUDA(HIP) tensor"), i)
         if c.dim() != 1 or c.shape[0] < 1:
-            raise ValueError(f"every clip must be [n] with at least one sample (clip {i})")
-        sigs.append(c)
+            raise ragged.named(ValueError("every clip must be [n] with at least one sample"), i)
     kw = dict(method=method, winLen=winLen, hopLen=hopLen, center=center)
     out = [None] * len(clips)
-    for dtype in (torch.float32, torch.float64):
-        idx = [i for i, s in enumerate(sigs) if s.dtype == dtype]
+    for idx in ragged.split_by_dtype(sigs):
         if not idx:
             continue
-        x, lengths = pack_clips([sigs[i] for i in idx], dtype)
+        x, lengths = pack_clips([sigs[i] for i in idx], sigs[idx[0]].dtype)
         try:
             env, out_len, env_sr = amplitude_envelope_ragged_batch(x, lengths.numpy(), sr, **kw)
         except ValueError as e:
-            _blame_clip(e, lambda b: amplitude_envelope_batch(sigs[idx[b]], sr, **kw), idx)
+            ragged.blame_clip(e, lambda b: amplitude_envelope_batch(sigs[idx[b]], sr, **kw), idx)
         if outFilter is not None:
             try:
                 env = apply_filter_ragged_batch(env, out_len, env_sr, filt=outFilter, filtType=outFiltType,
                                                 cutOff=outFiltCutOff, filtLen=outFiltLen, polyOrd=outFiltPolyOrd)
-            except RowRefused as e:                               # (an envelope too short for the filter)
-                raise ValueError(f"{e.base} (clip {idx[e.row]})") from e
+            except ragged.RowRefused as e:                        # (an envelope too short for the filter)
+                raise ragged.named(e, idx[e.row])
         host = None if all(on_device[i] for i in idx) else env.cpu().numpy()
         for b, i in enumerate(idx):
             n = int(out_len[b])
@@ -526,7 +502,7 @@ def apply_stencil_ragged(x2, lens_dev, st, n_min: int = 0):
     cs = _c_stencil(st, n_min)
     out = torch.empty((rows, n), dtype=torch.float64, device=x2.device)
     with torch.cuda.device(x2.device):
-        _lib.check(_lib.load().mm_stencil_ragged_f64(C.byref(cs), x2.data_ptr(), rows, n, x2.stride(0) if rows > 1 else n,
+        _lib.check(_lib.load().mm_stencil_ragged_f64(C.byref(cs), x2.data_ptr(), rows, n, ragged.row_pitch(x2),
                                                      lens_dev.data_ptr(), out.data_ptr(),
                                                      C.c_void_p(torch.cuda.current_stream(x2.device).cuda_stream)),
                    "mm_stencil_ragged_f64")
@@ -548,8 +524,7 @@ def apply_stencil(x2, st, passes: int = 1):
         src = x2
         for _ in range(passes):
             out = torch.empty((rows, n), dtype=torch.float64, device=x2.device)
-            # (a single row's stride is arbitrary -- numpy's x[None, :] gives 0 -- and never used: pass n)
-            _lib.check(lib.mm_stencil_f64(C.byref(cs), src.data_ptr(), rows, n, src.stride(0) if rows > 1 else n,
+            _lib.check(lib.mm_stencil_f64(C.byref(cs), src.data_ptr(), rows, n, ragged.row_pitch(src),
                                           out.data_ptr(), stream), "mm_stencil_f64")
             src = out
     return src
@@ -563,7 +538,7 @@ def velocity_batch(x, sr: float, difference: int = 1, method: str = "gradient", 
     more than 16 samples run through filters.savgol_batch (mm_savgol_f64), any width up to the row's length.  A float32
     tensor (an RMS envelope) comes back float32 for 'gradient' / 'sg', as numpy / scipy return it, to float32 round-off."""
     import torch
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype in (torch.float64, torch.float32)):
+    if not (ragged.is_device_tensor(x) and x.dtype in (torch.float64, torch.float32)):
         raise TypeError("x must be a float64 (or float32) CUDA(HIP) tensor")
     if x.dtype == torch.float32:
         # numpy / scipy keep a float32 curve float32 for 'gradient' and 'sg' (np.gradient in float32 arithmetic,
@@ -585,7 +560,7 @@ def velocity_batch(x, sr: float, difference: int = 1, method: str = "gradient", 
         x2 = x2.contiguous()
     rows, n = x2.shape
     if method == "sg" and n < len(st["c"]):       # scipy.signal.savgol_filter's own check and message
-        raise ValueError("If mode is 'interp', window_length must be less than or equal to the size of x.")
+        raise ValueError(ragged.SG_WINDOW_TEXT)
     if n < max(2 * st["n_edge"], st["edge_w"]):
         raise ValueError("signal too short for the requested finite-difference stencil")
     src = apply_stencil(x2, st, passes)
@@ -604,7 +579,7 @@ def get_velocity(x: np.ndarray, sr: float, difference: int = 1, method: str = "g
     the device (``velocity_batch``: 'gradient', 'sg' of any width, 'finDiff' stencils that fit mm_stencil; a wider
     'finDiff' stencil makes the round trip through the host); numpy input keeps the reference's host arithmetic.
     """
-    if type(x).__module__.startswith("torch") and getattr(x, "is_cuda", False):
+    if ragged.is_device_tensor(x):
         if method not in ("gradient", "sg", "finDiff"):
             raise ValueError("Méthode inconnue. Utilisez 'gradient', 'sg' ou 'finDiff'.")
         try:
@@ -744,7 +719,7 @@ def _find_peaks(x, negate, height, threshold, prominence, lo, hi, ext):
     import math
     import torch
     from . import _lib
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype in (torch.float64, torch.float32)):
+    if not (ragged.is_device_tensor(x) and x.dtype in (torch.float64, torch.float32)):
         raise TypeError("x must be a float64 (or float32) CUDA(HIP) tensor")
     squeeze = x.dim() == 1
     x2 = x.unsqueeze(0) if squeeze else x
@@ -776,7 +751,7 @@ def _find_peaks(x, negate, height, threshold, prominence, lo, hi, ext):
     pout = [i32() for _ in range(3)] if plateau else [None] * 3
     if rows > 0 and n > 0:
         lib = _lib.load()
-        stride = x2.stride(0) if rows > 1 else max(n, x2.stride(0))
+        stride = ragged.row_pitch(x2)
         ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None   # noqa: E731
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         dtype = 0 if x2.dtype == torch.float32 else 1
@@ -846,7 +821,7 @@ class MinMaxFinder:
         """The samples whose time lies in ``start <= t <= end``: ``(times, values)`` as numpy arrays for host input, as
         device tensors when both are CUDA(HIP) tensors.  One device tensor beside host data is a TypeError."""
         start, end = interval
-        on_device = _is_device_tensor(times), _is_device_tensor(values)
+        on_device = ragged.is_device_tensor(times), ragged.is_device_tensor(values)
         if any(on_device):
             if not all(on_device):
                 raise TypeError("times and values must both be host data or both CUDA(HIP) tensors")
@@ -864,7 +839,7 @@ class MinMaxFinder:
             return [], []
         import torch
         interval_times, interval_values = self.find_in_interval(x, y, interval)
-        on_device = _is_device_tensor(interval_values)
+        on_device = ragged.is_device_tensor(interval_values)
         if on_device:
             d = interval_values if interval_values.dtype in (torch.float32, torch.float64) else interval_values.double()
         else:

@@ -14,6 +14,9 @@ import functools
 import numpy as np
 from scipy import signal as _sig
 
+from . import ragged
+from .ragged import RowRefused  # noqa: F401  (callers catch it here)
+
 _KINDS = ("bandpass", "lowpass", "highpass")
 
 _MSG_NO_CUTOFF = "Cannot apply filter without specifying a cut Off freq. (CutOff is None)."
@@ -82,10 +85,6 @@ def iir_sos(sr, *, cutOff, filtLen=6, filtType="low"):
     return np.array(_iir_design(sr, cutOff, filtLen, kind))
 
 
-def _is_device_tensor(x):
-    return type(x).__module__.startswith("torch") and getattr(x, "is_cuda", False)
-
-
 def sos_sections(sos):
     """The float64 [n_sections, 6] array of an SOS argument, or scipy's own ValueError (signal._filter_design._validate_sos:
     same conditions, same messages) -- a flat vector of 6 k numbers, or sections scaled so that a0 != 1, are refused as
@@ -112,7 +111,7 @@ def sosfiltfilt_batch(x, sos):
     import ctypes as C
     import torch
     from . import _lib
-    if not (_is_device_tensor(x) and x.dtype in (torch.float64, torch.float32)):
+    if not (ragged.is_device_tensor(x) and x.dtype in (torch.float64, torch.float32)):
         raise TypeError("x must be a float64 or float32 CUDA(HIP) tensor")
     squeeze = x.dim() == 1
     x2 = x.unsqueeze(0) if squeeze else x
@@ -122,9 +121,8 @@ def sosfiltfilt_batch(x, sos):
         x2 = x2.contiguous()
     rows, n = x2.shape
     s = sos_sections(sos)
-    ntaps = 2 * s.shape[0] + 1 - min(int((s[:, 2] == 0).sum()), int((s[:, 5] == 0).sum()))
-    if n <= 3 * ntaps:   # scipy.signal.sosfiltfilt's own check and message
-        raise ValueError(f"The length of the input vector x must be greater than padlen, which is {3 * ntaps}.")
+    if n <= ragged.sos_padlen(s):   # scipy.signal.sosfiltfilt's own check and message
+        raise ValueError(ragged.PADLEN_TEXT.format(ragged.sos_padlen(s)))
     lib = _lib.load()
     out = torch.empty((rows, n), dtype=torch.float64, device=x.device)
     ws = torch.empty(int(lib.mm_sosfiltfilt_workspace_bytes(rows, n)), dtype=torch.uint8, device=x.device)
@@ -273,7 +271,7 @@ def fir_filtfilt_batch(x, taps):
     import ctypes as C
     import torch
     from . import _lib
-    if not (_is_device_tensor(x) and x.dtype in (torch.float64, torch.float32)):
+    if not (ragged.is_device_tensor(x) and x.dtype in (torch.float64, torch.float32)):
         raise TypeError("x must be a float64 or float32 CUDA(HIP) tensor")
     b = np.asarray(taps, dtype=np.float64).ravel()
     L = len(b)
@@ -282,7 +280,7 @@ def fir_filtfilt_batch(x, taps):
     x2, squeeze = _long_rows(x)
     rows, n = x2.shape
     if n <= 3 * L:      # scipy.signal.filtfilt's own check and message
-        raise ValueError(f"The length of the input vector x must be greater than padlen, which is {3 * L}.")
+        raise ValueError(ragged.PADLEN_TEXT.format(3 * L))
     out = torch.empty((rows, n), dtype=torch.float64, device=x.device)
     if rows:
         (h,) = _device_tables(("fir", b.tobytes()), x.device, lambda: (fir_filtfilt_taps(b),))
@@ -290,7 +288,7 @@ def fir_filtfilt_batch(x, taps):
         fn, name = (lib.mm_fir_filtfilt_f64, "mm_fir_filtfilt_f64") if x2.dtype == torch.float64 else \
             (lib.mm_fir_filtfilt_f32_f64, "mm_fir_filtfilt_f32_f64")
         with torch.cuda.device(x.device):
-            _lib.check(fn(x2.data_ptr(), rows, n, x2.stride(0) if rows > 1 else n, h.data_ptr(), L, out.data_ptr(), n,
+            _lib.check(fn(x2.data_ptr(), rows, n, ragged.row_pitch(x2), h.data_ptr(), L, out.data_ptr(), n,
                           C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), name)
     return out[0] if squeeze else out
 
@@ -303,7 +301,7 @@ def savgol_batch(x, window_length, polyorder, deriv=0, delta=1.0):
     import ctypes as C
     import torch
     from . import _lib
-    if not (_is_device_tensor(x) and x.dtype in (torch.float64, torch.float32)):
+    if not (ragged.is_device_tensor(x) and x.dtype in (torch.float64, torch.float32)):
         raise TypeError("x must be a float64 or float32 CUDA(HIP) tensor")
     W, p, deriv, delta = int(window_length), int(polyorder), int(deriv), float(delta)
     c, q, pe = _device_tables(("sg", W, p, deriv, delta), x.device, lambda: savgol_tables(W, p, deriv, delta))
@@ -311,11 +309,11 @@ def savgol_batch(x, window_length, polyorder, deriv=0, delta=1.0):
     x2, squeeze = _long_rows(x.double() if was_f32 else x)
     rows, n = x2.shape
     if W > n:           # scipy.signal.savgol_filter's own check and message
-        raise ValueError("If mode is 'interp', window_length must be less than or equal to the size of x.")
+        raise ValueError(ragged.SG_WINDOW_TEXT)
     out = torch.empty((rows, n), dtype=torch.float64, device=x.device)
     if rows:
         with torch.cuda.device(x.device):
-            _lib.check(_lib.load().mm_savgol_f64(x2.data_ptr(), rows, n, x2.stride(0) if rows > 1 else n, c.data_ptr(),
+            _lib.check(_lib.load().mm_savgol_f64(x2.data_ptr(), rows, n, ragged.row_pitch(x2), c.data_ptr(),
                                                  q.data_ptr(), pe.data_ptr(), W, p + 1, out.data_ptr(), n,
                                                  C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)),
                        "mm_savgol_f64")
@@ -374,7 +372,7 @@ def _apply_filter_device(x, sr, kind, *, filt, cutOff, filtLen, polyOrd, coeffs)
         if st is not None:
             pad = 3 * len(taps)
             if x.shape[-1] <= pad:             # scipy.signal.filtfilt's own check and message
-                raise ValueError(f"The length of the input vector x must be greater than padlen, which is {pad}.")
+                raise ValueError(ragged.PADLEN_TEXT.format(pad))
             if was_f32:
                 # scipy forms the odd extension of a float32 curve in float32 before lfilter upcasts (as sosfiltfilt does):
                 # extend explicitly in float32, run the operator over the extended curve (its own edge rows then only touch
@@ -399,47 +397,13 @@ def _apply_filter_device(x, sr, kind, *, filt, cutOff, filtLen, polyOrd, coeffs)
 # and is +0.0 behind them; the columns of x at and behind n_b are never read (NaN, Inf, another row's data).  The launches
 # are those of the single-length call at n_max; device lengths are not read back.
 
-_MSG_PADLEN = "The length of the input vector x must be greater than padlen, which is {}."      # sosfiltfilt's, filtfilt's
-_MSG_SG_WINDOW = "If mode is 'interp', window_length must be less than or equal to the size of x."      # savgol_filter's
 
-
-class RowRefused(ValueError):
-    """scipy's own ValueError for one row of a ragged batch, the row named: ``base`` is scipy's text, ``row`` the index."""
-
-    def __init__(self, base, row, n):
-        super().__init__(f"{base} (row {int(row)} has {int(n)} samples)")
-        self.base, self.row, self.n = base, int(row), int(n)
-
-
-def _ragged_rows(x, lengths):
-    """The common argument checks: (x as [rows, n_max] with unit inner stride and a row stride >= n_max, lengths as
-    plan._check_counts returns them: a validated int64 numpy array, or the caller's int64 device tensor untouched)."""
+def _ragged_args(x, lengths):
+    """The common argument checks: (x as ragged.device_rows returns it, lengths as ragged.check_lengths does)."""
     import torch
-    from .plan import _check_counts
-    if not (_is_device_tensor(x) and x.dtype in (torch.float64, torch.float32)):
-        raise TypeError("x must be a float64 or float32 CUDA(HIP) tensor")
-    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError("x must be [rows, n_max], at least one row and one column")
-    rows, n_max = x.shape
-    if (n_max > 1 and x.stride(1) != 1) or (rows > 1 and x.stride(0) < n_max):
-        x = x.contiguous()
-    return x, _check_counts(lengths, rows, n_max, x.device, "lengths")
-
-
-def _refuse_rows(lens, n_max, least, text):
-    """Rows shorter than ``least`` samples are the ones scipy refuses, with ``text``: host lengths raise it with the first
-    such row named, before any launch; device lengths only where not even n_max reaches (such rows come out NaN)."""
-    if isinstance(lens, np.ndarray):
-        short = np.flatnonzero(lens < least)
-        if short.size:
-            raise RowRefused(text, short[0], lens[short[0]])
-    elif n_max < least:
-        raise ValueError(text)
-
-
-def _lens_device(lens, dev):
-    import torch
-    return torch.from_numpy(lens).to(dev) if isinstance(lens, np.ndarray) else lens
+    x = ragged.device_rows(x, (torch.float64, torch.float32), "x must be a float64 or float32 CUDA(HIP) tensor",
+                           "x must be [rows, n_max], at least one row and one column")
+    return x, ragged.check_lengths(lengths, x.shape[0], x.shape[1], x.device)
 
 
 def sosfiltfilt_ragged_batch(x, lengths, sos):
@@ -452,19 +416,19 @@ def sosfiltfilt_ragged_batch(x, lengths, sos):
     import ctypes as C
     import torch
     from . import _lib
-    x2, lens = _ragged_rows(x, lengths)
+    x2, lens = _ragged_args(x, lengths)
     rows, n_max = x2.shape
     s = sos_sections(sos)
-    ntaps = 2 * s.shape[0] + 1 - min(int((s[:, 2] == 0).sum()), int((s[:, 5] == 0).sum()))
-    _refuse_rows(lens, n_max, 3 * ntaps + 1, _MSG_PADLEN.format(3 * ntaps))
+    padlen = ragged.sos_padlen(s)
+    ragged.refuse_short(lens, n_max, padlen + 1, ragged.PADLEN_TEXT.format(padlen))
     lib = _lib.load()
-    d_lens = _lens_device(lens, x.device)
+    d_lens = ragged.counts_on_device(lens, x.device)
     out = torch.empty((rows, n_max), dtype=torch.float64, device=x.device)
     ws = torch.empty(int(lib.mm_sosfiltfilt_ragged_workspace_bytes(rows, n_max)), dtype=torch.uint8, device=x.device)
     fn, name = (lib.mm_sosfiltfilt_ragged_f64, "mm_sosfiltfilt_ragged_f64") if x2.dtype == torch.float64 else \
         (lib.mm_sosfiltfilt_ragged_f32_f64, "mm_sosfiltfilt_ragged_f32_f64")
     with torch.cuda.device(x.device):
-        _lib.check(fn(x2.data_ptr(), rows, n_max, x2.stride(0) if rows > 1 else n_max, d_lens.data_ptr(), s.ctypes.data,
+        _lib.check(fn(x2.data_ptr(), rows, n_max, ragged.row_pitch(x2), d_lens.data_ptr(), s.ctypes.data,
                       s.shape[0], out.data_ptr(), ws.data_ptr(), ws.numel(),
                       C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), name)
     return out
@@ -478,21 +442,21 @@ def fir_filtfilt_ragged_batch(x, lengths, taps):
     import ctypes as C
     import torch
     from . import _lib
-    x2, lens = _ragged_rows(x, lengths)
+    x2, lens = _ragged_args(x, lengths)
     rows, n_max = x2.shape
     b = np.asarray(taps, dtype=np.float64).ravel()
     L = len(b)
     if L < 2:
         raise ValueError("fir_filtfilt_ragged_batch needs at least two taps")
-    _refuse_rows(lens, n_max, 3 * L + 1, _MSG_PADLEN.format(3 * L))
-    d_lens = _lens_device(lens, x.device)
+    ragged.refuse_short(lens, n_max, 3 * L + 1, ragged.PADLEN_TEXT.format(3 * L))
+    d_lens = ragged.counts_on_device(lens, x.device)
     out = torch.empty((rows, n_max), dtype=torch.float64, device=x.device)
     (h,) = _device_tables(("fir", b.tobytes()), x.device, lambda: (fir_filtfilt_taps(b),))
     lib = _lib.load()
     fn, name = (lib.mm_fir_filtfilt_ragged_f64, "mm_fir_filtfilt_ragged_f64") if x2.dtype == torch.float64 else \
         (lib.mm_fir_filtfilt_ragged_f32_f64, "mm_fir_filtfilt_ragged_f32_f64")
     with torch.cuda.device(x.device):
-        _lib.check(fn(x2.data_ptr(), rows, n_max, x2.stride(0) if rows > 1 else n_max, d_lens.data_ptr(), h.data_ptr(), L,
+        _lib.check(fn(x2.data_ptr(), rows, n_max, ragged.row_pitch(x2), d_lens.data_ptr(), h.data_ptr(), L,
                       out.data_ptr(), n_max, C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), name)
     return out
 
@@ -505,18 +469,18 @@ def savgol_ragged_batch(x, lengths, window_length, polyorder, deriv=0, delta=1.0
     import ctypes as C
     import torch
     from . import _lib
-    x2, lens = _ragged_rows(x, lengths)
+    x2, lens = _ragged_args(x, lengths)
     W, p, deriv, delta = int(window_length), int(polyorder), int(deriv), float(delta)
     rows, n_max = x2.shape
-    _refuse_rows(lens, n_max, W, _MSG_SG_WINDOW)
+    ragged.refuse_short(lens, n_max, W, ragged.SG_WINDOW_TEXT)
     c, q, pe = _device_tables(("sg", W, p, deriv, delta), x.device, lambda: savgol_tables(W, p, deriv, delta))
     was_f32 = x2.dtype == torch.float32
     if was_f32:
         x2 = x2.double()        # (the padding converts with the rows; it is never read)
-    d_lens = _lens_device(lens, x.device)
+    d_lens = ragged.counts_on_device(lens, x.device)
     out = torch.empty((rows, n_max), dtype=torch.float64, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.check(_lib.load().mm_savgol_ragged_f64(x2.data_ptr(), rows, n_max, x2.stride(0) if rows > 1 else n_max,
+        _lib.check(_lib.load().mm_savgol_ragged_f64(x2.data_ptr(), rows, n_max, ragged.row_pitch(x2),
                                                     d_lens.data_ptr(), c.data_ptr(), q.data_ptr(), pe.data_ptr(), W, p + 1,
                                                     out.data_ptr(), n_max,
                                                     C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)),
@@ -529,12 +493,11 @@ def _apply_filter_per_length(x, lens, sr, kw):
     are read back first) -> float64 [rows, n_max], zeros behind each row's length.  Host lengths scipy refuses raise its
     ValueError with the row named; with device lengths such a row comes out NaN, as in the ragged kernels."""
     import torch
-    from .plan import by_length
     on_host = isinstance(lens, np.ndarray)
     if not on_host:
         lens = lens.clamp(1, x.shape[1]).cpu().numpy()
     out = torch.zeros(x.shape, dtype=torch.float64, device=x.device)
-    for n, idx in by_length(lens):
+    for n, idx in ragged.group_rows(lens):
         ii = torch.from_numpy(idx).to(x.device)
         try:
             out[ii, :n] = applyFilter(x[ii, :n], sr, **kw)
@@ -567,7 +530,7 @@ def apply_filter_ragged_batch(x, lengths, sr, /, *, filt: str = "iir", cutOff=[N
     from . import _lib
     kind = _validate(filt, cutOff, filtType, sr)
     kw = dict(filt=filt, cutOff=cutOff, filtLen=filtLen, filtType=filtType, polyOrd=polyOrd, coeffs=coeffs)
-    x2, lens = _ragged_rows(x, lengths)
+    x2, lens = _ragged_args(x, lengths)
     n_max = x2.shape[1]
     was_f32 = x2.dtype == torch.float32
     if filt == "iir":
@@ -587,8 +550,8 @@ def apply_filter_ragged_batch(x, lengths, sr, /, *, filt: str = "iir", cutOff=[N
             st, _ = velocity_stencil(1.0, 0, "sg", filtLen, 2, polyOrd)
         except NotImplementedError:
             return savgol_ragged_batch(x2, lens, filtLen, polyOrd, deriv=0, delta=1.0)
-        _refuse_rows(lens, n_max, len(st["c"]), _MSG_SG_WINDOW)
-        y = apply_stencil_ragged(x2.double() if was_f32 else x2, _lens_device(lens, x.device), st)
+        ragged.refuse_short(lens, n_max, len(st["c"]), ragged.SG_WINDOW_TEXT)
+        y = apply_stencil_ragged(x2.double() if was_f32 else x2, ragged.counts_on_device(lens, x.device), st)
         return y.float() if was_f32 else y
     if filt == "fir":
         taps = np.asarray(coeffs) if coeffs is not None else \
@@ -602,8 +565,8 @@ def apply_filter_ragged_batch(x, lengths, sr, /, *, filt: str = "iir", cutOff=[N
                 return _apply_filter_per_length(x2, lens, sr, kw)
             from .calc import apply_stencil_ragged
             pad = 3 * len(taps)
-            _refuse_rows(lens, n_max, pad + 1, _MSG_PADLEN.format(pad))
-            return apply_stencil_ragged(x2, _lens_device(lens, x.device), st, n_min=pad + 1)
+            ragged.refuse_short(lens, n_max, pad + 1, ragged.PADLEN_TEXT.format(pad))
+            return apply_stencil_ragged(x2, ragged.counts_on_device(lens, x.device), st, n_min=pad + 1)
         if np.size(taps) >= 2:
             return fir_filtfilt_ragged_batch(x2, lens, taps)
         return _apply_filter_per_length(x2, lens, sr, kw)       # a single tap: scipy's own exception, through applyFilter
@@ -616,10 +579,9 @@ def applyFilter_batch(curves, sr, /, **kw):
     applyFilter filters it, and comes back numpy.  The CUDA(HIP) curves form one padded batch per type (float32; float64
     and everything else, which applyFilter widens) and run through apply_filter_ragged_batch: one ragged call each instead
     of one call per distinct length.  A curve scipy refuses raises scipy's ValueError with the curve's index appended."""
-    import torch
     curves = list(curves)
     out = [None] * len(curves)
-    on_device = [_is_device_tensor(c) for c in curves]
+    on_device = [ragged.is_device_tensor(c) for c in curves]
     for i, c in enumerate(curves):
         if on_device[i] and c.dim() != 1:
             raise ValueError(f"curves must be [n] (curve {i})")
@@ -627,24 +589,14 @@ def applyFilter_batch(curves, sr, /, **kw):
             try:
                 out[i] = applyFilter(c, sr, **kw)
             except ValueError as e:
-                raise ValueError(f"{e} (curve {i})") from e
-    groups = ([i for i, c in enumerate(curves) if on_device[i] and c.dtype == torch.float32],
-              [i for i, c in enumerate(curves) if on_device[i] and c.dtype != torch.float32])
-    for idx in groups:
-        if not idx:
-            continue
-        dev = curves[idx[0]].device
-        dtype = torch.float32 if curves[idx[0]].dtype == torch.float32 else torch.float64
-        lens = np.array([curves[i].shape[0] for i in idx], dtype=np.int64)
+                raise ragged.named(e, i, "curve")
+    for idx, x, lens in ragged.packed_groups([c if d else None for c, d in zip(curves, on_device)]):
         if int(lens.min()) < 1:
             raise ValueError(f"curves must not be empty (curve {idx[int(lens.argmin())]})")
-        x = torch.empty((len(idx), int(lens.max())), dtype=dtype, device=dev)
-        for b, i in enumerate(idx):
-            x[b, :lens[b]].copy_(curves[i], non_blocking=True)
         try:
             y = apply_filter_ragged_batch(x, lens, sr, **kw)
         except RowRefused as e:
-            raise ValueError(f"{e.base} (curve {idx[e.row]})") from e
+            raise ragged.named(e, idx[e.row], "curve")
         for b, i in enumerate(idx):
             out[i] = y[b, :lens[b]].clone()
     return out
@@ -664,7 +616,7 @@ def applyFilter(x, sr, /, *, filt: str = "iir", cutOff=[None], filtLen: int = 6,
     Raises the reference's bare ``Exception`` messages for the same bad arguments.
     """
     kind = _validate(filt, cutOff, filtType, sr)
-    if _is_device_tensor(x):       # a batch of curves that lives on the GPU stays there
+    if ragged.is_device_tensor(x):       # a batch of curves that lives on the GPU stays there
         return _apply_filter_device(x, sr, kind, filt=filt, cutOff=cutOff, filtLen=filtLen, polyOrd=polyOrd, coeffs=coeffs)
 
     if filt == "iir":

@@ -72,6 +72,25 @@ def get_amplitude_batch(clips, sr, /, **kw):
     return calculate_amplitude_envelope_batch(clips, sr, **kw)
 
 
+def _signal_row(clip, sigSr, channelN, device=None):
+    """The signal of get_MFCCS_change and its list form: a path is loaded on the device (it never leaves the GPU), a
+    [channels, n] array gives its channel ``channelN``; with ``device`` the row is brought there as the float32 [n] the
+    MFCC kernels take (arrays of any float dtype are cast)."""
+    signal = _load_audio_device(clip, sigSr) if isinstance(clip, str) else clip
+    if signal.ndim > 1:
+        signal = signal[channelN, :]
+    if device is None:
+        return signal
+    import torch
+    if isinstance(signal, torch.Tensor):
+        y = signal.to(device=device, dtype=torch.float32)
+    else:
+        y = torch.from_numpy(np.ascontiguousarray(np.asarray(signal), dtype=np.float32)).to(device)
+    if y.dim() != 1:
+        raise ValueError("expected a 1-D signal")
+    return y
+
+
 def get_MFCCS_change(audioIn, sigSr, /, *, channelN: int = 0, tStep: float = 0.001,
                      winLen: float = 0.025, n_mfcc: int = 13, n_fft: int = 512, minFreq: int = 100,
                      maxFreq: int = 10000, removeFirst: int = 1, filtCutoff: int = 12,
@@ -84,22 +103,12 @@ def get_MFCCS_change(audioIn, sigSr, /, *, channelN: int = 0, tStep: float = 0.0
     change curve and the time anchor of every frame, as the reference does.  The MFCCs come from
     the HIP kernels (float32 arithmetic; arrays of any float dtype are cast to float32).
     """
-    signal = _load_audio_device(audioIn, sigSr) if isinstance(audioIn, str) else audioIn   # a path never leaves the GPU
-    if signal.ndim > 1:
-        signal = signal[channelN, :]
-
+    signal = _signal_row(audioIn, sigSr, channelN)
     cfg = MfccConfig.from_reference_call(sigSr, tStep=tStep, winLen=winLen, n_mfcc=n_mfcc,
                                          n_fft=n_fft, minFreq=minFreq, maxFreq=maxFreq)
     if _tail.device_path_applies(diffMethod, outFilter):
-        import torch
         plan = get_plan(cfg)
-        if isinstance(signal, torch.Tensor):
-            y = signal.to(device=plan.device, dtype=torch.float32)
-        else:
-            y = torch.from_numpy(np.ascontiguousarray(np.asarray(signal), dtype=np.float32)).to(plan.device)
-        if y.dim() != 1:
-            raise ValueError("expected a 1-D signal")
-        coeffs_dev = plan.mfcc(y)
+        coeffs_dev = plan.mfcc(_signal_row(signal, sigSr, channelN, plan.device))
         anchors = _tail.time_anchors(coeffs_dev.shape[2], tStep, winLen)
         change = _tail.mfcc_change_device(plan, coeffs_dev, tStep=tStep, removeFirst=removeFirst,
                                           filtCutoff=filtCutoff, filtOrd=filtOrd, diffMethod=diffMethod,
@@ -136,24 +145,11 @@ def get_MFCCS_change_batch(clips, sigSr, /, *, channelN: int = 0, tStep: float =
     clips = list(clips)
     if not _tail.device_path_applies(diffMethod, outFilter) or not clips:
         return [get_MFCCS_change(c, sigSr, **kw) for c in clips]       # (an output filter applyFilter refuses: its own error)
-    import torch
     from .batch import mfcc_change_ragged_batch, pack_clips
     cfg = MfccConfig.from_reference_call(sigSr, tStep=tStep, winLen=winLen, n_mfcc=n_mfcc,
                                          n_fft=n_fft, minFreq=minFreq, maxFreq=maxFreq)
     plan = get_plan(cfg)
-    rows = []
-    for c in clips:
-        signal = _load_audio_device(c, sigSr) if isinstance(c, str) else c
-        if signal.ndim > 1:
-            signal = signal[channelN, :]
-        if isinstance(signal, torch.Tensor):
-            y = signal.to(device=plan.device, dtype=torch.float32)
-        else:
-            y = torch.from_numpy(np.ascontiguousarray(np.asarray(signal), dtype=np.float32)).to(plan.device)
-        if y.dim() != 1:
-            raise ValueError("expected a 1-D signal")
-        rows.append(y)
-    audio, lengths = pack_clips(rows)
+    audio, lengths = pack_clips([_signal_row(c, sigSr, channelN, plan.device) for c in clips])
     change, _ = mfcc_change_ragged_batch(audio, lengths, cfg, tStep=tStep, removeFirst=removeFirst, filtCutoff=filtCutoff,
                                          filtOrd=filtOrd, diffMethod=diffMethod, outFilter=outFilter,
                                          outFiltType=outFiltType, outFiltCutOff=outFiltCutOff, outFiltLen=outFiltLen,

@@ -25,7 +25,8 @@ import scipy.signal
 import scipy.stats
 from scipy import interpolate
 
-from .filters import RowRefused, applyFilter, apply_filter_ragged_batch
+from . import ragged
+from .filters import applyFilter, apply_filter_ragged_batch
 
 __all__ = ["pyin_batch", "pyin_ragged_batch", "pyin_ragged_frames", "pyin", "interp_NAN", "interp_nan_batch",
            "interp_nan_ragged_batch", "get_f0", "get_f0_batch", "pyin_sizes", "beta_tables", "boltzmann_table",
@@ -212,31 +213,13 @@ def _tables(p, z, switch_prob, beta_parameters, boltzmann_parameter, device):
     return _TABLES[dk]
 
 
-def _is_device_tensor(x):
-    return type(x).__module__.startswith("torch") and getattr(x, "is_cuda", False)
-
-
 def _as_signal(audio):
     """Device rows [B, n] in the type the kernels take: float32 stays float32 (librosa's energy terms then run in
-    float32), everything else becomes float64 (integer PCM keeps its values)."""
+    float32), everything else becomes float64 (integer PCM keeps its values) -> (rows, whether audio was [n])."""
     import torch
-    if not _is_device_tensor(audio):
-        raise TypeError("audio must be a CUDA(HIP) tensor [n] or [B, n]")
-    squeeze = audio.dim() == 1
-    x = audio.unsqueeze(0) if squeeze else audio
-    if x.dim() != 2:
-        raise ValueError("audio must be [n] or [B, n]")
-    if x.dtype not in (torch.float32, torch.float64):
-        x = x.to(torch.float64)
-    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
-        # the library takes a row pitch >= n: an expand()ed row (pitch 0) or overlapping rows are copied
-        x = x.contiguous()
-    return x, squeeze
-
-
-def _row_pitch(x):
-    """Elements between the rows of [B, n] as the kernels want it (>= n; the stride of a single row says nothing)."""
-    return x.stride(0) if x.shape[0] > 1 else x.shape[1]
+    x = ragged.device_rows(audio, (torch.float32, torch.float64), "audio must be a CUDA(HIP) tensor [n] or [B, n]",
+                           "audio must be [n] or [B, n]", widen=torch.float64, one_dim=True, nonempty=False)
+    return x, audio.dim() == 1
 
 
 _TORCH_PAD = {"reflect": "reflect", "edge": "replicate", "wrap": "circular"}
@@ -289,7 +272,7 @@ def pyin_batch(audio, sr, *, fmin, fmax, frame_length=2048, win_length=None, hop
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         for r0 in range(0, B, rows):
             r = min(rows, B - r0)
-            _lib.check(fn(C.byref(p), C.byref(tabs.c), x[r0].data_ptr(), r, n, _row_pitch(x), f0[r0].data_ptr(),
+            _lib.check(fn(C.byref(p), C.byref(tabs.c), x[r0].data_ptr(), r, n, ragged.row_pitch(x), f0[r0].data_ptr(),
                           voiced[r0].data_ptr(), vprob[r0].data_ptr(), states[r0].data_ptr(), ws.data_ptr(), ws.numel(),
                           stream), name)
     if fill_na is None:                 # librosa keeps the decoded bin's frequency on unvoiced frames
@@ -298,13 +281,7 @@ def pyin_batch(audio, sr, *, fmin, fmax, frame_length=2048, win_length=None, hop
     return tuple(o[0] for o in out) if squeeze else out
 
 
-def pyin_ragged_frames(lengths, frame_length, hop_length, center=True):
-    """Frames of clips of ``lengths`` samples (host integers) -> int64 numpy array: mm_pyin_num_frames per clip, 0 for a
-    clip too short for one frame (only without centring).  No GPU needed."""
-    n = np.asarray(lengths, dtype=np.int64)
-    padded = n + (2 * (int(frame_length) // 2) if center else 0)
-    return np.where((n >= 1) & (padded >= frame_length), 1 + (padded - int(frame_length)) // int(hop_length), 0).astype(np.int64)
-
+pyin_ragged_frames = ragged.centered_frames     # frames of clips of ``lengths`` samples: mm_pyin_num_frames per clip
 
 _MSG_SHORT = "pyin: a signal of {} samples is shorter than frame_length={}"
 
@@ -326,12 +303,11 @@ def pyin_ragged_batch(audio, lengths, sr, *, fmin, fmax, frame_length=2048, win_
     clips' frames; batches are cut to PYIN_WS_BYTES as in pyin_batch."""
     import torch
     from . import _lib
-    from .plan import check_lengths
     x, _ = _as_signal(audio)
     if audio.dim() != 2:
         raise ValueError("audio must be [B, n_max]")
     B, n = x.shape
-    lens = check_lengths(lengths, B, n, x.device)
+    lens = ragged.check_lengths(lengths, B, n, x.device)
     on_host = isinstance(lens, np.ndarray)
     if center and pad_mode != "constant":
         if not on_host:
@@ -348,10 +324,7 @@ def pyin_ragged_batch(audio, lengths, sr, *, fmin, fmax, frame_length=2048, win_
     T = z["n_frames"]
     if T < 1:
         raise ValueError(_MSG_SHORT.format(n, frame_length))
-    if on_host:
-        none = np.flatnonzero(pyin_ragged_frames(lens, frame_length, z["hop_length"], center) < 1)
-        if none.size:
-            raise ValueError(_MSG_SHORT.format(int(lens[none[0]]), frame_length) + f" (clip {int(none[0])})")
+    ragged.refuse_short(lens, n, 1 if center else frame_length, lambda short: _MSG_SHORT.format(short, frame_length), "clip", None)
     lib = _lib.load()
     dev = x.device
     tabs = _tables(p, z, switch_prob, beta_parameters, boltzmann_parameter, dev)
@@ -369,12 +342,12 @@ def pyin_ragged_batch(audio, lengths, sr, *, fmin, fmax, frame_length=2048, win_
     f32 = x.dtype == torch.float32
     name = "mm_pyin_ragged_f32" if f32 else "mm_pyin_ragged_f64"
     with torch.cuda.device(dev):
-        lens_dev = torch.from_numpy(lens).to(dev, non_blocking=True) if on_host else lens      # (on the current stream)
+        lens_dev = ragged.counts_on_device(lens, dev)       # (on the current stream)
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         for r0 in range(0, B, rows):
             r = min(rows, B - r0)
             fn = lib.mm_pyin_ragged_f32 if f32 else lib.mm_pyin_ragged_f64
-            _lib.check(fn(C.byref(p), C.byref(tabs.c), x[r0].data_ptr(), r, n, _row_pitch(x), lens_dev[r0:].data_ptr(),
+            _lib.check(fn(C.byref(p), C.byref(tabs.c), x[r0].data_ptr(), r, n, ragged.row_pitch(x), lens_dev[r0:].data_ptr(),
                           f0[r0].data_ptr(), voiced[r0].data_ptr(), vprob[r0].data_ptr(), states[r0].data_ptr(),
                           frames[r0:].data_ptr(), ws.data_ptr(), ws.numel(), stream), name)
     if fill_na is None:                 # librosa keeps the decoded bin's frequency on unvoiced frames: of real frames only
@@ -395,7 +368,7 @@ def pyin_cmnd(audio, sr, *, fmin, fmax, frame_length=2048, win_length=None, hop_
     out = torch.empty((B, z["n_frames"], z["max_period"] - z["min_period"] + 1), dtype=torch.float64, device=x.device)
     with torch.cuda.device(x.device):
         _lib.check(_lib.load().mm_pyin_cmnd(C.byref(p), x.data_ptr(), 0 if x.dtype == torch.float32 else 1, B, n,
-                                            _row_pitch(x), out.data_ptr(),
+                                            ragged.row_pitch(x), out.data_ptr(),
                                             C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), "mm_pyin_cmnd")
     return out[0] if squeeze else out
 
@@ -553,7 +526,7 @@ def interp_nan_batch(x, method: str = "linear"):
     samples, one workgroup each).  'quadratic' and 'cubic' need a solve over all knots: NotImplementedError here
     (interp_NAN runs them through scipy on the host); any other name is a ValueError.  Rows with too few valid samples
     raise what the reference raises (interp_NAN's doc string), after one read-back of the smallest count."""
-    if not _is_device_tensor(x):
+    if not ragged.is_device_tensor(x):
         raise TypeError("interp_nan_batch takes a CUDA(HIP) tensor; interp_NAN also takes numpy curves")
     if method == "linear":
         return _interp_linear_device(x)
@@ -572,28 +545,22 @@ def interp_nan_ragged_batch(x, counts, method: str = "linear"):
     from the smallest number of valid samples below a row's count, in one read-back."""
     import torch
     from . import _lib
-    from .plan import _check_counts
-    if not _is_device_tensor(x):
-        raise TypeError("interp_nan_ragged_batch takes a CUDA(HIP) tensor")
+    xd = ragged.device_rows(x, (torch.float64,), "interp_nan_ragged_batch takes a CUDA(HIP) tensor", "x must be [rows, n_max]",
+                            widen=torch.float64, nonempty=False)
     if method != "linear" and method not in _INTERP_KINDS:
         if method in _INTERP_HOST_KINDS:
             raise NotImplementedError(f"method={method!r} needs a banded solve over all knots; not on the device")
         raise ValueError(f"interp_nan_ragged_batch: unknown method {method!r}")
-    if x.dim() != 2:
-        raise ValueError("x must be [rows, n_max]")
     if not x.is_floating_point():
         raise TypeError("x must be a floating-point tensor")
     rows, n = x.shape
     if rows == 0 or n == 0:
         return x.clone()
     dev = x.device
-    cnt = _check_counts(counts, rows, n, dev, "counts")
-    xd = x.to(torch.float64)
-    if xd.stride(1) != 1 or (rows > 1 and xd.stride(0) < n):
-        xd = xd.contiguous()
-    pitch_ = xd.stride(0) if rows > 1 else n
+    cnt = ragged.check_counts(counts, rows, n, dev, "counts")
+    pitch_ = ragged.row_pitch(xd)
     with torch.cuda.device(dev):
-        cd = torch.from_numpy(cnt).to(dev, non_blocking=True) if isinstance(cnt, np.ndarray) else cnt
+        cd = ragged.counts_on_device(cnt, dev)
         c = cd.clamp(1, n)
         valid = ((~torch.isnan(xd)) & (torch.arange(n, device=dev)[None, :] < c[:, None])).sum(dim=1)
         if method == "linear":                              # scipy.interpolate.interp1d needs two points, NaN or not
@@ -631,7 +598,7 @@ def interp_NAN(X, method: str = "linear"):
     sample raises IndexError under 'pchip' and scipy's ValueError for empty input otherwise; 'linear' and 'slinear' need
     two valid samples (ValueError)."""
     if method == "linear":
-        if _is_device_tensor(X):
+        if ragged.is_device_tensor(X):
             return _interp_linear_device(X)
         a = np.asarray(X)
         if np.sum(np.isnan(a)) == 0:
@@ -639,7 +606,7 @@ def interp_NAN(X, method: str = "linear"):
         import torch
         y = _interp_linear_device(torch.from_numpy(np.ascontiguousarray(a)).to(_gpu()))
         return y.cpu().numpy()
-    if _is_device_tensor(X):
+    if ragged.is_device_tensor(X):
         if method in _INTERP_KINDS:
             return _interp_kind_device(X, method)
         import torch
@@ -652,6 +619,22 @@ def interp_NAN(X, method: str = "linear"):
 _MSG_GAPS = inspect.cleandoc("""Post processing filters should be applied (outFiltes is not None) \
         but unvoiced regions are not interpolated (interpUnvoiced is None).
         Cannot filter f0 signal with gaps due to unvoiced regions""")
+
+
+def _pyin_keywords(a):
+    """The arguments of get_f0 / get_f0_batch (their locals()) -> the keywords of their pyin_batch / pyin_ragged_batch
+    calls, after get_f0's refusals."""
+    if (a["interpUnvoiced"] is None) & (a["outFilter"] is not None):
+        raise Exception(_MSG_GAPS)
+    if a["method"] in ("praatac", "praatcc"):
+        raise NotImplementedError(f"method={a['method']!r} calls Praat through parselmouth; not part of this build")
+    if a["method"] != "pyin":
+        raise UnboundLocalError(f"get_f0: unknown method {a['method']!r}")     # reference: f0 unbound
+    return dict(sr=a["sr"], frame_length=a["pyinframe_length"], win_length=a["pyinwin_length"],
+                hop_length=int(a["hopSize"] * a["sr"]), n_thresholds=a["n_thresholds"], beta_parameters=a["beta_parameters"],
+                boltzmann_parameter=a["boltzmann_parameter"], resolution=a["resolution"],
+                max_transition_rate=a["max_transition_rate"], switch_prob=a["switch_prob"],
+                no_trough_prob=a["no_trough_prob"], fill_na=a["pyinfill_na"], center=a["pyincenter"], pad_mode=a["pyinpad_mode"])
 
 
 def get_f0(x, sr: float, method: str = "praatac", hopSize: float = 0.01, minPitch: float = 75, maxPitch: float = 600,
@@ -670,19 +653,9 @@ def get_f0(x, sr: float, method: str = "praatac", hopSize: float = 0.01, minPitc
     A numpy signal returns numpy arrays; a CUDA(HIP) tensor [n] returns f0 as a device tensor (filtered on the device)
     and f0t as numpy, like calculate_amplitude_envelope.  'praatac' / 'praatcc' call Praat (parselmouth): not part of
     this package."""
-    if (interpUnvoiced is None) & (outFilter is not None):
-        raise Exception(_MSG_GAPS)
-    if method in ("praatac", "praatcc"):
-        raise NotImplementedError(f"method={method!r} calls Praat through parselmouth; not part of this build")
-    if method != "pyin":
-        raise UnboundLocalError(f"get_f0: unknown method {method!r}")     # reference: f0 unbound
-    on_device = _is_device_tensor(x)
+    kw = _pyin_keywords(locals())
+    on_device = ragged.is_device_tensor(x)
     xd = x if on_device else _to_device_signal(x)
-    hop_length = int(hopSize * sr)
-    kw = dict(sr=sr, frame_length=pyinframe_length, win_length=pyinwin_length, hop_length=hop_length,
-              n_thresholds=n_thresholds, beta_parameters=beta_parameters, boltzmann_parameter=boltzmann_parameter,
-              resolution=resolution, max_transition_rate=max_transition_rate, switch_prob=switch_prob,
-              no_trough_prob=no_trough_prob, fill_na=pyinfill_na, center=pyincenter, pad_mode=pyinpad_mode)
     f0, _voiced, _vprob = pyin_batch(xd, fmin=minPitch, fmax=maxPitch, **kw)
     if minMaxQuant is not None:
         h = f0.cpu().numpy()
@@ -720,40 +693,19 @@ def get_f0_batch(clips, sr: float, method: str = "praatac", hopSize: float = 0.0
     kernel, still loop over the distinct frame counts there).  ``minMaxQuant``: the first pass
     is ragged; the second has its own fmin / fmax, and with them its own pitch bins and transition band, per clip, so it
     runs pyin_batch clip by clip.  The errors are get_f0's, with the clip's index appended where one clip is at fault."""
-    if (interpUnvoiced is None) & (outFilter is not None):
-        raise Exception(_MSG_GAPS)
-    if method in ("praatac", "praatcc"):
-        raise NotImplementedError(f"method={method!r} calls Praat through parselmouth; not part of this build")
-    if method != "pyin":
-        raise UnboundLocalError(f"get_f0: unknown method {method!r}")     # reference: f0 unbound
-    import torch
+    kw = _pyin_keywords(locals())
     clips = list(clips)
-    on_device = [_is_device_tensor(c) for c in clips]
+    on_device = [ragged.is_device_tensor(c) for c in clips]
     sigs = [c if d else _to_device_signal(c) for c, d in zip(clips, on_device)]
-    hop_length = int(hopSize * sr)
-    kw = dict(sr=sr, frame_length=pyinframe_length, win_length=pyinwin_length, hop_length=hop_length,
-              n_thresholds=n_thresholds, beta_parameters=beta_parameters, boltzmann_parameter=boltzmann_parameter,
-              resolution=resolution, max_transition_rate=max_transition_rate, switch_prob=switch_prob,
-              no_trough_prob=no_trough_prob, fill_na=pyinfill_na, center=pyincenter, pad_mode=pyinpad_mode)
     for i, s in enumerate(sigs):
         if s.dim() != 1:
-            raise ValueError(f"audio must be [n] (clip {i})")
-        if s.shape[0] < 1 or pyin_ragged_frames([s.shape[0]], pyinframe_length, max(hop_length, 1), pyincenter)[0] < 1:
-            raise ValueError(_MSG_SHORT.format(s.shape[0], pyinframe_length) + f" (clip {i})")
+            raise ragged.named(ValueError("audio must be [n]"), i)
+        if s.shape[0] < 1 or pyin_ragged_frames([s.shape[0]], pyinframe_length, max(kw["hop_length"], 1), pyincenter)[0] < 1:
+            raise ragged.named(ValueError(_MSG_SHORT.format(s.shape[0], pyinframe_length)), i)
     out = [None] * len(clips)
-    groups = ([i for i, s in enumerate(sigs) if s.dtype == torch.float32],
-              [i for i, s in enumerate(sigs) if s.dtype != torch.float32])
-    for idx in groups:
-        if not idx:
-            continue
-        dev = sigs[idx[0]].device
-        dtype = torch.float32 if sigs[idx[0]].dtype == torch.float32 else torch.float64
-        lengths = np.array([sigs[i].shape[0] for i in idx], dtype=np.int64)
-        audio = torch.empty((len(idx), int(lengths.max())), dtype=dtype, device=dev)
-        for b, i in enumerate(idx):
-            audio[b, :lengths[b]].copy_(sigs[i], non_blocking=True)       # (integer PCM: converted to float64 here)
+    for idx, audio, lengths in ragged.packed_groups(sigs):      # (integer PCM: converted to float64 on the copy)
         f0 = pyin_ragged_batch(audio, lengths, fmin=minPitch, fmax=maxPitch, **kw)[0]
-        frames = pyin_ragged_frames(lengths, pyinframe_length, hop_length, pyincenter)
+        frames = pyin_ragged_frames(lengths, pyinframe_length, kw["hop_length"], pyincenter)
         if minMaxQuant is not None:
             first = f0.cpu().numpy()
             for b, i in enumerate(idx):
@@ -763,37 +715,26 @@ def get_f0_batch(clips, sr: float, method: str = "praatac", hopSize: float = 0.0
                     quants = np.quantile(h, [minMaxQuant[0], minMaxQuant[1]])
                     f0[b, :frames[b]] = pyin_batch(audio[b, :lengths[b]], fmin=quants[0], fmax=quants[1], **kw)[0]
                 except (ValueError, IndexError, NotImplementedError) as e:
-                    raise type(e)(f"{e} (clip {i})") from e
+                    raise ragged.named(e, i)
         if interpUnvoiced is not None:
             if interpUnvoiced == "linear" or interpUnvoiced in _INTERP_KINDS:
                 try:
                     f0 = interp_nan_ragged_batch(f0, frames, interpUnvoiced)
                 except (ValueError, IndexError) as e:
-                    _blame_clip(e, lambda b: interp_NAN(f0[b, :frames[b]], interpUnvoiced), idx)
+                    ragged.blame_clip(e, lambda b: interp_NAN(f0[b, :frames[b]], interpUnvoiced), idx)
             else:
                 for b, i in enumerate(idx):
                     try:
                         f0[b, :frames[b]] = interp_NAN(f0[b, :frames[b]], interpUnvoiced)
                     except (ValueError, IndexError) as e:
-                        raise type(e)(f"{e} (clip {i})") from e
+                        raise ragged.named(e, i)
         if outFilter is not None:
             try:
                 f0 = apply_filter_ragged_batch(f0, frames, 1 / hopSize, filt=outFilter, cutOff=outFiltCutOff,
                                                filtLen=outFiltLen, filtType=outFiltType, polyOrd=outFiltPolyOrd)
-            except RowRefused as e:                                       # (too few frames for the filter)
-                raise ValueError(f"{e.base} (clip {idx[e.row]})") from e
-        curves = [f0[b, :frames[b]] for b in range(len(idx))]
+            except ragged.RowRefused as e:                                # (too few frames for the filter)
+                raise ragged.named(e, idx[e.row])
         for b, i in enumerate(idx):
-            f = curves[b].clone() if on_device[i] else curves[b].cpu().numpy()
-            out[i] = (f, np.arange(int(frames[b])) * hopSize)
+            f = f0[b, :frames[b]]
+            out[i] = (f.clone() if on_device[i] else f.cpu().numpy(), np.arange(int(frames[b])) * hopSize)
     return out
-
-
-def _blame_clip(err, one, idx):
-    """A batched call raised ``err``: run ``one(b)`` clip by clip and raise the first clip's own error with its index."""
-    for b, i in enumerate(idx):
-        try:
-            one(b)
-        except type(err) as e:
-            raise type(e)(f"{e} (clip {i})") from e
-    raise err

@@ -12,7 +12,8 @@ from dataclasses import dataclass, asdict
 
 import numpy as np
 
-from . import _lib
+from . import _lib, ragged
+from .ragged import check_frames, check_lengths, sos_padlen, group_rows as by_length  # noqa: F401  (this module's public names)
 
 
 @dataclass(frozen=True)
@@ -134,65 +135,6 @@ def _torch():
     return torch
 
 
-def _check_counts(x, batch, hi, device, what):
-    """One integer count per clip, in [1, hi]: host values validated -> int64 numpy array; an int64 tensor on `device`
-    as it is (shape and type checked only: no read-back)."""
-    torch = _torch()
-    if isinstance(x, torch.Tensor) and x.is_cuda:
-        if x.dtype != torch.int64:
-            raise TypeError(f"{what} on the device must be int64, got {x.dtype}")
-        if tuple(x.shape) != (int(batch),):
-            raise ValueError(f"{what} must have shape ({int(batch)},), got {tuple(x.shape)}")
-        if device is not None and x.device != torch.device(device):
-            raise ValueError(f"{what} is on {x.device}, the plan on {device}")
-        return x.contiguous()
-    arr = x.numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
-    if arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer):
-        raise TypeError(f"{what} must be integers, got {arr.dtype}")
-    if arr.shape != (int(batch),):
-        raise ValueError(f"{what} must have shape ({int(batch)},), got {arr.shape}")
-    if int(arr.min()) < 1 or int(arr.max()) > int(hi):
-        raise ValueError(f"{what} must lie in [1, {int(hi)}], got {int(arr.min())} .. {int(arr.max())}")
-    return np.ascontiguousarray(arr, dtype=np.int64)
-
-
-def check_lengths(lengths, batch, n_samples, device=None):
-    """The `lengths` argument of the ragged calls: one valid sample count per clip of a padded [batch, n_samples] batch.
-
-    A host sequence, numpy array or CPU tensor of integers is validated here -- shape [batch], every value in
-    [1, n_samples], ValueError otherwise -- and returned as an int64 numpy array.  An int64 tensor on `device` (a
-    CUDA(HIP) device) is returned as it is, with no read-back: the kernels clamp its values into [1, n_samples]."""
-    return _check_counts(lengths, batch, n_samples, device, "lengths")
-
-
-_PADLEN_TEXT = "The length of the input vector x must be greater than padlen, which is {}."    # scipy.signal.sosfiltfilt's
-
-
-def sos_padlen(sos):
-    """scipy.signal.sosfiltfilt's default padlen for [n_sec, 6] sections: 3 * ntaps."""
-    return 3 * (2 * sos.shape[0] + 1 - min(int((sos[:, 2] == 0).sum()), int((sos[:, 5] == 0).sum())))
-
-
-def check_frames(frames, batch, n_frames_max, padlen=0, device=None):
-    """The `frames` argument of the ragged change tail: one valid frame count per clip of a [batch, n_mfcc, n_frames_max]
-    batch, checked as check_lengths checks sample counts.  Host values must also exceed `padlen`: scipy's own ValueError
-    text for a clip that sosfiltfilt refuses, with the first such clip named.  An int64 tensor on `device` is returned as
-    it is, with no read-back: the kernel clamps its values and writes NaN for a clip that is too short."""
-    arr = _check_counts(frames, batch, n_frames_max, device, "frames")
-    if isinstance(arr, np.ndarray):
-        short = np.flatnonzero(arr <= int(padlen))
-        if short.size:
-            raise ValueError(_PADLEN_TEXT.format(int(padlen)) + f" (clip {int(short[0])} has {int(arr[short[0]])} frames)")
-    return arr
-
-
-def by_length(frames):
-    """Host frame counts [B] -> [(T, int64 index array of the clips with T frames)], ascending T: the grouping behind
-    every per-length route of the ragged change tail."""
-    frames = np.asarray(frames)
-    return [(int(T), np.flatnonzero(frames == T).astype(np.int64)) for T in np.unique(frames)]
-
-
 class MfccPlan:
     """Owns one ``mm_plan`` on the current CUDA(HIP) device.  Raises when no GPU is present.
 
@@ -234,7 +176,7 @@ class MfccPlan:
 
     def _check_audio(self, audio):
         torch = _torch()
-        if not (isinstance(audio, torch.Tensor) and audio.is_cuda):
+        if not ragged.is_device_tensor(audio):
             raise TypeError("audio must be a CUDA(HIP) torch tensor")
         if audio.dtype != torch.float32:
             raise TypeError("audio must be float32")
@@ -254,7 +196,7 @@ class MfccPlan:
         """A caller-provided output must be exactly what the kernel writes: its data_ptr() goes to the C ABI
         unchecked otherwise (a short or strided tensor would be an out-of-bounds device write)."""
         torch = _torch()
-        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == self.device):
+        if not (ragged.is_device_tensor(out) and out.device == self.device):
             raise TypeError(f"{what}: out must be a tensor on {self.device}")
         if out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
             raise ValueError(f"{what}: out must be a contiguous {dtype} tensor of shape {tuple(shape)}, "
@@ -368,13 +310,12 @@ class MfccPlan:
     def _ragged_lengths(self, lengths, B, n):
         """(int64 device tensor [B] for the kernels, frames [B] int64 on the device) -- no synchronisation: host lengths
         are validated on the host and uploaded on the current stream, device lengths go through untouched."""
-        torch = _torch()
-        lens = check_lengths(lengths, B, n, self.device)
-        hop, odd = self.cfg.hop_length, self.cfg.n_fft - 2 * (self.cfg.n_fft // 2)      # frames = 1 + (L - odd) // hop
-        if not isinstance(lens, torch.Tensor):
-            both = torch.from_numpy(np.stack([lens, 1 + (lens - odd) // hop])).to(self.device, non_blocking=True)   # one copy
+        lens = ragged.check_lengths(lengths, B, n, self.device)
+        n_fft, hop = self.cfg.n_fft, self.cfg.hop_length
+        if isinstance(lens, np.ndarray):
+            both = ragged.counts_on_device(np.stack([lens, ragged.stft_frames(lens, n_fft, hop)]), self.device)    # one copy
             return both[0], both[1]
-        return lens, torch.div(lens.clamp(1, n).add_(hop - odd), hop, rounding_mode="floor")
+        return lens, ragged.stft_frames(lens.clamp(1, n), n_fft, hop)
 
     def _ragged(self, audio, lengths, out, out_mod, want_mod):
         torch = _torch()
@@ -445,7 +386,7 @@ class MfccPlan:
     def rfft(self, rows, n, out=None):
         """Stage-isolated batched rFFT: [R, L<=n] float32 -> complex64 [R, n/2+1]."""
         torch = _torch()
-        if not (isinstance(rows, torch.Tensor) and rows.is_cuda and rows.dtype == torch.float32
+        if not (ragged.is_device_tensor(rows) and rows.dtype == torch.float32
                 and rows.dim() == 2):
             raise TypeError("rows must be a 2-D float32 CUDA(HIP) tensor")
         if rows.stride(1) != 1:
@@ -464,7 +405,7 @@ class MfccPlan:
     def modspec(self, mfcc, out=None):
         """[B, n_mfcc, T] -> complex64 [B, n_mfcc, n_mod/2+1] (row A8)."""
         torch = _torch()
-        if not (isinstance(mfcc, torch.Tensor) and mfcc.is_cuda and mfcc.dtype == torch.float32
+        if not (ragged.is_device_tensor(mfcc) and mfcc.dtype == torch.float32
                 and mfcc.dim() == 3 and mfcc.shape[1] == self.cfg.n_mfcc):
             raise TypeError("mfcc must be a float32 CUDA(HIP) tensor [B, n_mfcc, T]")
         mfcc = mfcc.contiguous()
@@ -496,7 +437,7 @@ class MfccPlan:
         output filter to the result).  diff_method 'grad' = np.gradient, anything else = the reference's
         Savitzky-Golay differentiator savgol_filter(x, 3, 2, deriv=1, mode='interp')."""
         torch = _torch()
-        if not (isinstance(mfcc, torch.Tensor) and mfcc.is_cuda and mfcc.dtype == torch.float32
+        if not (ragged.is_device_tensor(mfcc) and mfcc.dtype == torch.float32
                 and mfcc.dim() == 3 and mfcc.shape[1] == self.cfg.n_mfcc):
             raise TypeError("mfcc must be a float32 CUDA(HIP) tensor [B, n_mfcc, T]")
         mfcc = mfcc.contiguous()
@@ -505,13 +446,11 @@ class MfccPlan:
         s1 = sos_sections(sos1)
         s2 = s1 if sos2 is None else sos_sections(sos2)
         for s in ((s1, s2) if out_filter else (s1,)):
-            ntaps = 2 * s.shape[0] + 1 - min(int((s[:, 2] == 0).sum()), int((s[:, 5] == 0).sum()))
-            if T <= 3 * ntaps:   # scipy.signal.sosfiltfilt's own check and message
-                raise ValueError("The length of the input vector x must be greater than padlen, "
-                                 f"which is {3 * ntaps}.")
+            if T <= ragged.sos_padlen(s):   # scipy.signal.sosfiltfilt's own check and message
+                raise ValueError(ragged.PADLEN_TEXT.format(ragged.sos_padlen(s)))
         sg = 0 if diff_method == "grad" else 1
         if sg and T < 3:    # scipy.signal.savgol_filter's own check and message
-            raise ValueError("If mode is 'interp', window_length must be less than or equal to the size of x.")
+            raise ValueError(ragged.SG_WINDOW_TEXT)
         out = torch.empty((B, T), dtype=torch.float64, device=self.device)
         # sized by the form this call takes (a few KB for the clip-resident one), not by the bound over all forms
         need = int(self._lib.mm_change_workspace_bytes_for(self._h, B, T, 1 if remove_first else 0, s1.ctypes.data, s1.shape[0],
@@ -540,7 +479,7 @@ class MfccPlan:
         entry) fall back to one mfcc_change() per distinct frame count, scattered into the zeroed output: correct,
         slower, and the one place this method synchronises (it reads `frames` back when they live on the device)."""
         torch = _torch()
-        if not (isinstance(mfcc, torch.Tensor) and mfcc.is_cuda and mfcc.dtype == torch.float32
+        if not (ragged.is_device_tensor(mfcc) and mfcc.dtype == torch.float32
                 and mfcc.dim() == 3 and mfcc.shape[1] == self.cfg.n_mfcc):
             raise TypeError("mfcc must be a float32 CUDA(HIP) tensor [B, n_mfcc, T]")
         if mfcc.device != self.device:
@@ -550,13 +489,13 @@ class MfccPlan:
         from .filters import sos_sections
         s1 = sos_sections(sos1)
         s2 = s1 if sos2 is None else sos_sections(sos2)
-        padlen = max(sos_padlen(s) for s in ((s1, s2) if out_filter else (s1,)))
+        padlen = max(ragged.sos_padlen(s) for s in ((s1, s2) if out_filter else (s1,)))
         if Tm <= padlen:
-            raise ValueError(_PADLEN_TEXT.format(padlen))
+            raise ValueError(ragged.PADLEN_TEXT.format(padlen))
         sg = 0 if diff_method == "grad" else 1
-        fr = check_frames(frames, B, Tm, padlen, self.device)
-        on_host = not isinstance(fr, torch.Tensor)
-        fr_dev = torch.from_numpy(fr).to(self.device, non_blocking=True) if on_host else fr
+        fr = ragged.check_frames(frames, B, Tm, padlen, self.device)
+        on_host = isinstance(fr, np.ndarray)
+        fr_dev = ragged.counts_on_device(fr, self.device)
         rf, n2 = 1 if remove_first else 0, s2.shape[0] if out_filter else 0
         out = torch.empty((B, Tm), dtype=torch.float64, device=self.device)
         need = int(self._lib.mm_change_ragged_workspace_bytes_for(self._h, B, Tm, rf, s1.ctypes.data, s1.shape[0],
@@ -574,7 +513,7 @@ class MfccPlan:
         # no ragged kernel for this call: one single-length call per distinct frame count (reads device lengths back)
         fr_host = fr if on_host else fr_dev.clamp(1, Tm).cpu().numpy()
         out.zero_()
-        for T, idx in by_length(fr_host):
+        for T, idx in ragged.group_rows(fr_host):
             ii = torch.from_numpy(idx).to(self.device)
             if T <= padlen:                 # device lengths only: what the kernel writes for a clip scipy refuses
                 out[ii, :T] = float("nan")

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from conftest import ROOT
-from modulation_mfcc_amd import _lib, batch, calc, mfcc
+from modulation_mfcc_amd import _lib, batch, calc, mfcc, ragged
 
 ENTRIES = ("mm_rms_ragged_f32", "mm_hilbert_ragged_create", "mm_hilbert_envelope_ragged")
 
@@ -75,7 +75,7 @@ def leaf(monkeypatch):
     def rows(x2, lens_dev, M):
         seen.append((M, tuple(x2.shape), lens_dev.tolist()))
         return torch.full(x2.shape, float(M), dtype=x2.dtype)
-    monkeypatch.setattr(calc, "_is_device_tensor", lambda x: isinstance(x, torch.Tensor))
+    monkeypatch.setattr(ragged, "is_device_tensor", lambda x: isinstance(x, torch.Tensor))
     monkeypatch.setattr(calc, "_hilbert_ragged_rows", rows)
     return seen
 

@@ -10,14 +10,14 @@ import pytest
 import torch
 
 from conftest import ROOT
-from modulation_mfcc_amd import _lib, calc, filters
+from modulation_mfcc_amd import _lib, calc, filters, ragged
 
 ENTRIES = ("mm_sosfiltfilt_ragged_f64", "mm_sosfiltfilt_ragged_f32_f64", "mm_stencil_ragged_f64", "mm_fir_filtfilt_ragged_f64",
            "mm_fir_filtfilt_ragged_f32_f64", "mm_savgol_ragged_f64")
 
 
 class FakeDeviceTensor:
-    """What filters._ragged_rows looks at, and nothing that could launch."""
+    """What ragged.device_rows looks at, and nothing that could launch."""
     __module__ = "torch.fake"
     is_cuda = True
     device = "cuda:0"
@@ -51,7 +51,7 @@ def leaves(monkeypatch):
     for name in ("sosfiltfilt_ragged_batch", "fir_filtfilt_ragged_batch", "savgol_ragged_batch", "_apply_filter_per_length"):
         monkeypatch.setattr(filters, name, rec(name))
     monkeypatch.setattr(calc, "apply_stencil_ragged", rec("apply_stencil_ragged"))
-    monkeypatch.setattr(filters, "_lens_device", lambda lens, dev: lens)
+    monkeypatch.setattr(ragged, "counts_on_device", lambda lens, dev: lens)
     return seen
 
 
@@ -145,7 +145,7 @@ def test_argument_errors(leaves):
 
 def test_scipys_refusals_name_the_row(monkeypatch):
     """Host lengths scipy would refuse: scipy's text, the first such row and its length appended, before any launch."""
-    monkeypatch.setattr(filters, "_lens_device", lambda lens, dev: pytest.fail("lengths were uploaded"))
+    monkeypatch.setattr(ragged, "counts_on_device", lambda lens, dev: pytest.fail("lengths were uploaded"))
     monkeypatch.setattr(calc, "apply_stencil_ragged", lambda *a, **k: pytest.fail("launched"))
     x = FakeDeviceTensor(4, 1000)
     f = filters.apply_filter_ragged_batch

@@ -7,7 +7,9 @@ one process per library; two files are then compared bit for bit (a schedule mov
 
 Case set `s16`: the smallest shapes that reach each code path of the staged n_fft-512 kernel (logmel512s_kernel) and the
 matrix-pipe kernel.  n_fft 512, 16 kHz, win 400, 40 mel / 13 MFCC unless said otherwise.
-Case set `tail`: every kernel of mm_tail.hip and its includes (tail_cases)."""
+Case set `tail`: every kernel of mm_tail.hip and its includes (tail_cases).
+Case set `ragged`: every public *_ragged_batch function with host and with device lengths, and the four list front ends
+(ragged_cases) -- for a change of the host code, run on two checkouts with the same library."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -205,7 +207,93 @@ def tail_cases():
     return out
 
 
-CASESETS = {"s16": s16_cases, "tail": tail_cases}
+RAGGED_LENS = [4000, 2500, 4000, 3100, 2500]
+
+
+def ragged_list(dev):
+    """Five clips at 16 kHz: numpy float32, numpy float64, numpy int16, device float32, device float64 -- two dtype groups,
+    a repeated length within and across them, both return types."""
+    import torch
+    x = [clips(70 + i, 1, n, 16000)[0].astype(np.float64) for i, n in enumerate(RAGGED_LENS)]
+    return [x[0].astype(np.float32), x[1], np.round(x[2] * 20000).astype(np.int16), torch.from_numpy(x[3].astype(np.float32)).to(dev),
+            torch.from_numpy(x[4]).to(dev)]
+
+
+def ragged_cases():
+    """Case set `ragged`: only names the package exports, so that the same code runs on an older checkout."""
+    import torch
+    import scipy.signal
+    import modulation_mfcc_amd as M
+    dev = torch.device("cuda", 0)
+    out = {}
+
+    def flat(r):
+        if isinstance(r, (tuple, list)):
+            return [a for part in r for a in flat(part)]
+        return [r.cpu().numpy()] if isinstance(r, torch.Tensor) else [r] if isinstance(r, np.ndarray) else []
+
+    def keep(name, call):
+        """every array of the call's result, in order; a refusal is kept as its type and text"""
+        try:
+            for k, a in enumerate(flat(call())):
+                out["%s.%d" % (name, k)] = a
+        except (ValueError, IndexError, TypeError, NotImplementedError) as e:
+            out[name + ".error"] = np.frombuffer(("%s: %s" % (type(e).__name__, e)).encode(), dtype=np.uint8)
+            print(name, "raised", type(e).__name__, e, flush=True)
+
+    lens = np.array(RAGGED_LENS, dtype=np.int64)
+    n_max = int(lens.max())
+    x64 = np.full((5, n_max + 3), np.nan)
+    for b, n in enumerate(lens):
+        x64[b, :n] = clips(60 + b, 1, n, 16000)[0]
+    rows = {"f32": torch.from_numpy(x64.astype(np.float32)).to(dev)[:, :n_max], "f64": torch.from_numpy(x64).to(dev)[:, :n_max]}
+    cfg = M.MfccConfig(sr=16000.0, n_fft=512, win_length=400, hop_length=32, n_mels=40, n_mfcc=13, fmin=100.0, fmax=8000.0)
+    sos = scipy.signal.butter(6, 0.05, output="sos")
+    pyin = dict(fmin=100.0, fmax=500.0, frame_length=512, hop_length=32)
+    for where in ("host", "dev"):
+        L = lens if where == "host" else torch.from_numpy(lens).to(dev)
+        f32, f64 = rows["f32"], rows["f64"]
+        keep("mfcc." + where, lambda: M.mfcc_ragged_batch(f32, L, cfg))
+        keep("modspec." + where, lambda: M.mfcc_modspec_ragged_batch(f32, L, cfg))
+        for name, kw in (("iir", dict(outFiltCutOff=[12])), ("sg", dict(outFilter="sg", outFiltCutOff=[12], outFiltLen=7)), ("none", dict(outFilter=None))):
+            keep("change.%s.%s" % (name, where), lambda: M.mfcc_change_ragged_batch(f32, L, cfg, **kw))
+        for center in (True, False):
+            keep("rms.c%d.%s" % (center, where), lambda: M.rms_ragged_batch(f32, L, 160, 32, center))
+        for dt, x in rows.items():
+            keep("hilbert.%s.%s" % (dt, where), lambda: M.hilbert_envelope_ragged_batch(x, L))
+            for method in ("RMS", "Hilb"):
+                keep("envelope.%s.%s.%s" % (method, dt, where), lambda: M.amplitude_envelope_ragged_batch(x, L, 16000, method=method, winLen=0.01, hopLen=0.002)[:2])
+            keep("sos.%s.%s" % (dt, where), lambda: M.sosfiltfilt_ragged_batch(x, L, sos))
+            keep("fir.%s.%s" % (dt, where), lambda: M.fir_filtfilt_ragged_batch(x, L, scipy.signal.firwin(31, 0.2)))
+            keep("savgol.%s.%s" % (dt, where), lambda: M.savgol_ragged_batch(x, L, 21, 3))
+            for name, kw in (("iir", dict(filt="iir", cutOff=[1000])), ("iir10", dict(filt="iir", cutOff=[1000], filtLen=10)), ("fir6", dict(filt="fir", cutOff=[1000], filtLen=6)),
+                             ("fir101", dict(filt="fir", cutOff=[1000], filtLen=101)), ("sg7", dict(filt="sg", cutOff=[1000], filtLen=7)),
+                             ("sg101", dict(filt="sg", cutOff=[1000], filtLen=101))):
+                keep("apply.%s.%s.%s" % (name, dt, where), lambda: M.apply_filter_ragged_batch(x, L, 16000.0, **kw))
+            keep("pyin.%s.%s" % (dt, where), lambda: M.pyin_ragged_batch(x, L, 16000, return_states=True, **pyin))
+            f0 = M.pyin_ragged_batch(x, L, 16000, **pyin)
+            for method in ("linear", "pchip"):
+                keep("interp.%s.%s.%s" % (method, dt, where), lambda: M.interp_nan_ragged_batch(f0[0], f0[3] if where == "dev" else f0[3].cpu().numpy(), method))
+    lst = ragged_list(dev)
+    keep("list.f0", lambda: M.get_f0_batch(lst, 16000, method="pyin", hopSize=0.002, minPitch=100, maxPitch=500, pyinframe_length=512,
+                                   interpUnvoiced="linear", outFilter="iir", outFiltCutOff=[10]))
+    for method in ("RMS", "Hilb"):
+        keep("list.envelope." + method, lambda: M.calculate_amplitude_envelope_batch(lst, 16000, method=method, winLen=0.01, hopLen=0.002,
+                                                                             outFilter="iir"))
+    keep("list.change", lambda: M.get_MFCCS_change_batch(lst, 16000, outFiltCutOff=[12]))
+    for kw in (dict(filt="sg", cutOff=[1000], filtLen=7), dict(filt="iir", cutOff=[1000])):
+        keep("list.apply." + kw["filt"], lambda: M.applyFilter_batch(lst, 16000.0, **kw))
+    for i in (0, 2, 3, 4):      # the single calls, which share their first steps with the list forms
+        keep("single.f0.%d" % i, lambda: M.get_f0(lst[i], 16000, method="pyin", hopSize=0.002, minPitch=100, maxPitch=500,
+                                                  pyinframe_length=512, interpUnvoiced="linear", outFilter="iir", outFiltCutOff=[10]))
+        keep("single.envelope.%d" % i, lambda: M.calculate_amplitude_envelope(lst[i], 16000, method="Hilb", winLen=0.01, hopLen=0.002,
+                                                                              outFilter="iir"))
+        keep("single.change.%d" % i, lambda: M.get_MFCCS_change(lst[i], 16000, outFiltCutOff=[12]))
+    torch.cuda.synchronize()
+    return out
+
+
+CASESETS = {"s16": s16_cases, "tail": tail_cases, "ragged": ragged_cases}
 
 if __name__ == "__main__":
     if len(sys.argv) == 4 and sys.argv[1] == "--compare":
