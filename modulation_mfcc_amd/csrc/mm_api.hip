@@ -793,8 +793,9 @@ static int setup_tile512(mm_plan* p, const PlanHost& h) {
            p->upload(&w16.d_lane_tab, lt.data(), lt.size() * 4) == MM_OK &&
            p->upload(&w16.d_part, balance_parts_over_simds(r16).data(), r16.part.size() * 4) == MM_OK &&
            raise_lds(MM_LM_LDS_MAX, logmel512w_kernel<0>, logmel512w_kernel<1>);
-  // 32-frame tiles, two 8-wave workgroups per CU (mm_logmel16h.hip.inc; opt-in variant 7): pair table from r16
-  if (31 * c.hop_length + 512 + 256 <= MM_H16_NR * 2048 && (c.hop_length % 2) == 0 && c.preemph == 0.0f) {
+  // 32-frame tiles, two 8-wave workgroups per CU (mm_logmel16h.hip.inc; opt-in variant 7): pair table from r16, lane
+  // records from w16 -- which uploads them only when its own tables fit (a 256-filter bank's do not: no h16 plan then)
+  if (w16.ok && 31 * c.hop_length + 512 + 256 <= MM_H16_NR * 2048 && (c.hop_length % 2) == 0 && c.preemph == 0.0f) {
     mm_plan::H16& h16 = p->h16;
     H16Tables ht;
     build_h16_tables(r16, &ht);
