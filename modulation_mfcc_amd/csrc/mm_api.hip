@@ -897,20 +897,18 @@ static void setup_wpf(mm_plan* p, const PlanHost& h) {
          p->upload(&w.d_mel_lane, ml.data(), ml.size() * 4) == MM_OK &&
          set_dct_fm_attr(64 * (MM_WPF_MAXMEL + 1) * 4);
   if (!w.ok) return;
-  // A operands of the matrix-pipe clamp + DCT kernels for the frame-major rows
+  // A operands of the matrix-pipe clamp + DCT kernel for the frame-major rows
   const int nk = (c.n_mels + 3) / 4, kbn = (c.n_mfcc + 15) / 16;
-  const size_t lds = ((size_t)64 * ((4 * nk) | 1) + (size_t)kbn * nk * 64) * 4;
-  if (lds > 65536 || c.n_mels > 128) return;      // the kernel's loader holds 64 frames x 128 filters in registers
+  if (c.n_mels > 128) return;      // the kernel's loader holds 16 frames x 128 filters in a wave's registers
   mm_plan::DctFm& f = p->dctfm;
   const std::vector<float> da = dct_a_operands(c, h.dct.data(), nk);
-  if (p->upload(&f.d_a, da.data(), da.size() * 4) == MM_OK) f.kb = kbn;
   // wave-per-tile kernel: batch of 10 or 8 steps, whichever pads less
   const int ch = ((nk + 9) / 10 * 10 <= (nk + 7) / 8 * 8) ? 10 : 8, nkp = (nk + ch - 1) / ch * ch;
   std::vector<float> dw((size_t)kbn * nkp * 64, 0.0f);
   for (int kb = 0; kb < kbn; ++kb)
     std::memcpy(&dw[(size_t)kb * nkp * 64], &da[(size_t)kb * nk * 64], (size_t)nk * 64 * 4);
   const size_t ldsw = ((size_t)kbn * nkp * 64 + 4 * 16 * (size_t)((4 * nkp) | 1)) * 4;
-  if (f.d_a && ldsw <= 65536 && p->upload(&f.d_wave_a, dw.data(), dw.size() * 4) == MM_OK) { f.wave_nk = nkp; f.ch = ch; }
+  if (ldsw <= 65536 && p->upload(&f.d_wave_a, dw.data(), dw.size() * 4) == MM_OK) { f.kb = kbn; f.wave_nk = nkp; f.ch = ch; }
 }
 
 // the trajectory rFFT: generic (n = 8192 needs 128 KB of dynamic LDS) and the 2048-point wave-per-frame form

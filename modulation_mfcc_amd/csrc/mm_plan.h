@@ -85,8 +85,8 @@ struct mm_plan {
     int z = 0;                     // 3 / 5 / 6 / 7: the window is zero for a lane's first and last Z pairs (logmel_wpf_kernel<.., Z>)
   } wpf;
   struct DctFm {                   // clamp + DCT of the frame-major rows on the matrix pipe
-    float* d_a = nullptr;          // A operands [kb][nk][64] (nullptr: VALU kernel); d_wave_a: the same for
-    float* d_wave_a = nullptr;     // dct_clamp_fm_wave_kernel<CH>, steps padded to a multiple of CH with zeros
+    float* d_wave_a = nullptr;     // A operands [kb][wave_nk][64] of dct_clamp_fm_wave_kernel<CH>, steps padded to a multiple
+                                   // of CH with zeros (nullptr: VALU kernel)
     int kb = 0, wave_nk = 0, ch = 0;
   } dctfm;
   struct Rf2k { bool ok = false; float* d_lane_tab = nullptr; } rf2k;   // rfft_wpf_kernel<4> (stage-isolated rFFT, n = 2048)

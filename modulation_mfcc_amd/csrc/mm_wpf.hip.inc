@@ -500,103 +500,16 @@ __global__ __launch_bounds__(256) void dct_clamp_fm_kernel(const float* __restri
   }
 }
 
-// Matrix-pipe form of the same kernel (round 2): at BASELINE configs[3] the VALU version above spends 0.26 ms on
-// 80 x 40 MACs per frame (a sixth of the FP32 rate: every FMA also costs its issue slot and a scalar-cache
-// operand).  Here a wave takes 16 frames: D[16 coefficients x 16 frames] += DCT[16 x 4 filters] * L[4 filters x 16
-// frames] with v_mfma_f32_16x16x4_f32 (exact f32, 32 cycles, 1024 MACs), 20 steps x 3 coefficient blocks for
-// 80 mel / 40 MFCC.  The clamped 64-frame tile goes through LDS as before (coalesced row reads; odd pitch: the
-// B operand reads -- lane (frame j, kc) reads filter 4 s + kc -- are conflict-free but for one lane pair), the
-// A operands [kb][s][64] are copied to LDS once per workgroup.
-__global__ __launch_bounds__(256) void dct_clamp_fm_mfma_kernel(const float* __restrict__ logmel,
-                                                                 const int* __restrict__ clip_key,
-                                                                 const float* __restrict__ dct_a /*[kbn][nk][64]*/,
-                                                                 float* __restrict__ out, int64_t n_frames, int64_t n_tiles,
-                                                                 int n_mels, int n_mfcc, int nk, int kbn, float top_db) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int pitch = (4 * nk) | 1;                     // >= n_mels, odd
-  float* tile = reinterpret_cast<float*>(smem);       // [64][pitch]
-  float* At = tile + 64 * pitch;                      // [kbn][nk][64]
-  const int64_t bpc = (n_frames + 63) / 64;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int j = lane & 15, g = lane >> 4;
-  for (int i = threadIdx.x; i < kbn * nk * 64; i += 256) At[i] = dct_a[i];       // once per (persistent) workgroup
-  for (int64_t tl = blockIdx.x; tl < n_tiles; tl += gridDim.x) {
-    const int64_t b = tl / bpc;
-    const int64_t t0 = (tl - b * bpc) * 64;
-    const int nf = (int)((n_frames - t0) < 64 ? (n_frames - t0) : 64);
-    const float thr = top_db >= 0.0f ? key_float(clip_key[b]) - top_db : -INFINITY;
-    const float* src = logmel + (b * n_frames + t0) * n_mels;
-    // the tile's nf * n_mels floats are contiguous in the frame-major workspace: every thread issues all of its
-    // 16-byte loads (4-byte aligned addresses: any n_mels) before the first one is used -- one memory round trip
-    // per tile instead of one per row pair.  (Prefetching the next tile's loads across the MFMA phase costs 24
-    // more live VGPRs, drops a workgroup per CU and measured 0.27 instead of 0.18 ms.)
-    const int total = nf * n_mels;
-    constexpr int U = 8;                              // 8 x 256 x 4 floats = 64 frames x 128 filters
-    MmFloat4U v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int e = 4 * ((int)threadIdx.x + 256 * u);
-      if (e + 3 < total) v[u] = *reinterpret_cast<const MmFloat4U*>(src + e);
-      else {
-        v[u].x = e < total ? src[e] : 0.0f; v[u].y = e + 1 < total ? src[e + 1] : 0.0f;
-        v[u].z = e + 2 < total ? src[e + 2] : 0.0f; v[u].w = 0.0f;
-      }
-    }
-    __syncthreads();                                  // the previous tile's MFMA operands have been read
-    if (nf < 64 || n_mels < pitch)                    // rows past nf, filters past n_mels (wave-uniform)
-      for (int i = threadIdx.x; i < 64 * pitch; i += 256) tile[i] = 0.0f;
-    if (nf < 64 || n_mels < pitch) __syncthreads();
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int e = 4 * ((int)threadIdx.x + 256 * u);
-      if (e < total) {
-        int fr = e / n_mels, m = e - fr * n_mels;
-        const float q4[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          if (e + c < total) tile[fr * pitch + m] = fmaxf(q4[c], thr);
-          if (++m == n_mels) { m = 0; ++fr; }
-        }
-      }
-    }
-    __syncthreads();
-    const int64_t t = t0 + 16 * wave + j;
-    if (16 * wave < nf) {                             // wave-uniform
-      const float* Bp = tile + (16 * wave + j) * pitch + g;
-      for (int kb = 0; kb < kbn; ++kb) {
-        const float* Ap = At + (size_t)kb * nk * 64 + lane;
-        mm_f32x4 a0 = {0.0f, 0.0f, 0.0f, 0.0f}, a1 = {0.0f, 0.0f, 0.0f, 0.0f};
-        for (int s0 = 0; s0 < nk; s0 += 10) {
-          float av[10], bv[10];
-#pragma unroll
-          for (int i = 0; i < 10; ++i) {
-            const int s2 = min(s0 + i, nk - 1);
-            av[i] = Ap[s2 * 64];
-            bv[i] = Bp[4 * s2];
-          }
-#pragma unroll
-          for (int i = 0; i < 10; i += 2) {
-            a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(s0 + i < nk ? av[i] : 0.0f, bv[i], a0, 0, 0, 0);
-            a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(s0 + i + 1 < nk ? av[i + 1] : 0.0f, bv[i + 1], a1, 0, 0, 0);
-          }
-        }
-        if (t < n_frames) {
-          float* o = out + (b * n_mfcc + 16 * kb + 4 * g) * n_frames + t;
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (16 * kb + 4 * g + r < n_mfcc) o[(int64_t)r * n_frames] = a0[r] + a1[r];
-        }
-      }
-    }
-  }
-}
-
-// Round 3: the same clamp + DCT with a WAVE per 16-frame tile.  The 64-frame version above runs load -> barrier ->
-// clamp into LDS -> barrier -> MFMA -> store as one serial chain per workgroup (0.18 ms at configs[3]: 2.7 TB/s where the
-// 492 MB it moves would take 0.08 ms); here a wave owns its tile end to end -- wave-private LDS tile [16][pitch], no
-// workgroup barrier in the loop -- and requests the NEXT tile's rows (five 16-byte loads per lane at 80 mel: 20 VGPRs,
-// where prefetching a 64-frame tile had cost 24 more and an occupancy step) before it multiplies the current one, so
-// the sixteen waves of a CU overlap their phases freely.  A operands [kbn][nk][64] in LDS, once per workgroup.
+// Matrix-pipe form of the same clamp + DCT, a WAVE per 16-frame tile: D[16 coefficients x 16 frames] += DCT[16 x 4
+// filters] * L[4 filters x 16 frames] with v_mfma_f32_16x16x4_f32 (exact f32, 32 cycles, 1024 MACs), 20 steps x 3
+// coefficient blocks for 80 mel / 40 MFCC (at BASELINE configs[3] the VALU kernel above spends 0.26 ms on those MACs: a
+// sixth of the FP32 rate).  A 64-frame tile per workgroup runs load -> barrier -> clamp into LDS -> barrier -> MFMA ->
+// store as one serial chain (measured 0.18 ms at configs[3]: 2.7 TB/s where the 492 MB it moves would take 0.08 ms);
+// here a wave owns its tile end to end -- wave-private LDS tile [16][pitch] with an odd pitch (the B operand reads --
+// lane (frame j, kc) reads filter 4 s + kc -- are conflict-free but for one lane pair), no workgroup barrier in the
+// loop -- and requests the NEXT tile's rows (five 16-byte loads per lane at 80 mel: 20 VGPRs, where prefetching a
+// 64-frame tile had cost 24 more and an occupancy step) before it multiplies the current one, so the sixteen waves of a
+// CU overlap their phases freely.  A operands [kbn][nk][64] (dct_a_operands) in LDS, once per workgroup.
 // (First version: 0.18 ms like the 64-frame kernel.  Counters: 7.7 vector instructions per MFMA -- the run-time step
 // index of the operand batches (`min(s0 + i, nk - 1)`, zero selects) made every LDS address a computed one, and on
 // gfx950 vector instructions add to the f32 MFMA's time.  Now the step count is padded to a multiple of the batch CH on
@@ -705,8 +618,7 @@ __global__ __launch_bounds__(256, 4) void dct_clamp_fm_wave_kernel(const float* 
 
 // ---- host side of dct_clamp_fm_kernel: pick KB = ceil(n_mfcc / 4) rounded up to {4, 8, 10, 12, 16} ----
 static bool set_dct_fm_attr(int bytes) {
-  if (hipFuncSetAttribute((const void*)dct_clamp_fm_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536) != hipSuccess ||
-      hipFuncSetAttribute((const void*)dct_clamp_fm_wave_kernel<10, 5, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536) != hipSuccess ||
+  if (hipFuncSetAttribute((const void*)dct_clamp_fm_wave_kernel<10, 5, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536) != hipSuccess ||
       hipFuncSetAttribute((const void*)dct_clamp_fm_wave_kernel<10, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536) != hipSuccess ||
       hipFuncSetAttribute((const void*)dct_clamp_fm_wave_kernel<8, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536) != hipSuccess)
     return false;
