@@ -120,7 +120,7 @@ def take(x, rows, start=ROW_LOUD):
 
 
 def edge_lengths(n):
-    return tuple(sorted({1, 2, 3, n // 2 - 1, n // 2, n // 2 + 1, n - 1, n}))
+    return tuple(sorted(T for T in {1, 2, 3, n // 2 - 1, n // 2, n // 2 + 1, n - 1, n} if 1 <= T <= n))
 
 
 @functools.lru_cache(maxsize=None)
