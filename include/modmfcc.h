@@ -35,6 +35,9 @@
  *   mm_rms_f32,
  *   mm_hilbert_envelope    <- calculate_amplitude_envelope (script/calc.py:284-343): librosa.feature.rms /
  *                             |scipy.signal.hilbert| -- row N3
+ *   mm_pcm_decode_ragged_f32, mm_resample_ragged_f32,
+ *   mm_resample_banded_ragged_f32 <- the loader below for a list of files: one decode launch for all of them, both
+ *                             resamplers with one length per row (build-defined; no reference site)
  *   mm_pcm_decode_f32,
  *   mm_resample_f32        <- librosa.load(path, sr=sigSr, mono=False) (script/mfcc.py:284,373) -- row N4
  *   mm_find_peaks,
@@ -504,6 +507,44 @@ int mm_resample_banded_f32(const float* d_x, int64_t rows, int64_t n_in, int64_t
  *   win < 4 ksteps). */
 int mm_resample_banded_shape(int32_t F, int32_t S, int32_t NB, int32_t ksteps, int32_t win, int32_t* qt, int32_t* pad,
                              size_t* lds_bytes);
+
+/* The input side for a LIST of files (audio_io.load_audio_batch): a padded batch with one length per row.
+ *
+ * mm_pcm_decode_ragged_f32: d_raw = ONE device buffer of raw_bytes bytes holding the data chunks of n_files files,
+ *   d_recs = one mm_wav_rec per file (device): the byte offset of the file's data in d_raw (a multiple of 16 lets the
+ *   16-bit / float32 mono and stereo files take 16-byte loads; any offset decodes), its frame count, the format code
+ *   of mm_pcm_decode_f32, its channel count and the output row of its first channel.  ONE launch, whatever the mix of
+ *   formats and channel counts: channel c of a file goes to row first_row + c of d_out [out_rows][out_stride], planar
+ *   float32, every value bit for bit what mm_pcm_decode_f32 writes; columns [n_frames, max_frames) of those rows are
+ *   +0.0 (no memset needed), columns beyond max_frames are not written.  No byte outside [byte_offset, byte_offset +
+ *   n_frames * channels * bytes per sample) is read; a record whose range leaves the buffer, whose format is not 1 .. 6
+ *   or whose frame count is negative decodes as an empty file (zeros), one whose rows leave [0, out_rows) is skipped.
+ *   Frames beyond max_frames are cut.  Rows must not be shared between records.
+ * mm_resample_ragged_f32 / mm_resample_banded_ragged_f32: mm_resample_f32 / mm_resample_banded_f32 with one length per
+ *   row: d_lens [rows] int64 (device).  Row b holds n_b = clamp(d_lens[b], 1, n_max) samples and gets n_out_b =
+ *   ceil(n_b L / M) outputs (64-bit arithmetic; the banded entry computes it as ceil(n_b F / S), the same number):
+ *   columns [0, n_out_b) of output row b are bit for bit what the single-length entry writes for x[b, :n_b] alone,
+ *   columns [n_out_b, n_out_max) are +0.0.  n_out_max must be ceil(n_max L / M) (MM_ERR_INVALID_ARG otherwise), y_stride
+ *   >= n_out_max is the output's row pitch.  Nothing at or behind x[b, n_b] is read, nothing outside [0, n_out_max) of
+ *   a row is written.  Tables, the rows <= 65535 limit of the float64 kernel and MM_ERR_UNSUPPORTED of the banded one
+ *   (nothing is written then) as in the single-length entries.  The launch shape is that of n_max: a tile of the
+ *   banded kernel that lies wholly behind a row's outputs stages and multiplies nothing and stores its zeros. */
+typedef struct mm_wav_rec {
+  int64_t byte_offset; /* of the file's first frame in d_raw */
+  int64_t n_frames;
+  int32_t fmt;         /* 1 = u8, 2 = s16, 3 = packed s24, 4 = s32, 5 = f32, 6 = f64 */
+  int32_t channels;
+  int64_t first_row;   /* output row of channel 0 */
+} mm_wav_rec;
+int mm_pcm_decode_ragged_f32(const void* d_raw, int64_t raw_bytes, const mm_wav_rec* d_recs, int64_t n_files,
+                             int64_t max_frames, float* d_out, int64_t out_rows, int64_t out_stride, void* stream);
+int mm_resample_ragged_f32(const float* d_x, int64_t rows, int64_t n_max, int64_t x_stride, const int64_t* d_lens,
+                           const float* d_taps, int32_t L, int32_t M, int32_t taps_per_phase, int64_t half_len,
+                           float* d_y, int64_t n_out_max, int64_t y_stride, void* stream);
+int mm_resample_banded_ragged_f32(const float* d_x, int64_t rows, int64_t n_max, int64_t x_stride, const int64_t* d_lens,
+                                  const float* d_atab, const int32_t* d_lo_off, int32_t F, int32_t S, int32_t NB,
+                                  int32_t ksteps, int32_t lo_min, int32_t win, float* d_y, int64_t n_out_max,
+                                  int64_t y_stride, void* stream);
 
 /* Measurement aid: float4 grid-stride device-to-device copy of n_floats (a multiple of 4; 16-byte
  * aligned pointers) on `stream` -- the practical HBM ceiling bench.py quotes beside the stage-isolated

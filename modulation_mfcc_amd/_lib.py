@@ -184,6 +184,11 @@ PROTOTYPES = {
                                         C.c_int32, _vp, _i64, _vp]),
     "mm_resample_banded_shape": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                           C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]),
+    "mm_pcm_decode_ragged_f32": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp]),
+    "mm_resample_ragged_f32": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _i64, _vp, _i64,
+                                        _i64, _vp]),
+    "mm_resample_banded_ragged_f32": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                               C.c_int32, C.c_int32, _vp, _i64, _i64, _vp]),
     "mm_devcopy_f32": (C.c_int, [_vp, _vp, _i64, _vp]),
     "mm_pyin_check": (C.c_int, [_pyp]),
     "mm_pyin_num_frames": (_i64, [_pyp, _i64]),

@@ -4,6 +4,8 @@ script/mfcc.py:284 and :373 -- decode the file to float32 in [-1, 1), convert it
 Here: a RIFF/WAVE parser on the host (header only), the PCM -> float32 conversion and the sample-rate
 conversion on the device (``mm_pcm_decode_f32``, ``mm_resample_f32``).  Both UI call sites of the reference
 pass a PATH (script/main.py:750-769, 1049-1066), so this is what the application actually exercises.
+For a LIST of files, ``load_audio_batch`` gives the padded batch and a length per row that the ragged calls take, in
+one decode launch and one resample launch per source rate, every row what ``load_audio`` gives.
 
 Deviation from the reference, stated once: librosa resamples with ``soxr_hq`` (libsoxr's "high quality"
 recipe: 20-bit precision, pass band to 0.913 of the lower Nyquist, linear phase, alias-free stop band from the
@@ -22,7 +24,10 @@ from fractions import Fraction
 
 import numpy as np
 
-__all__ = ["read_wav_header", "load_wav", "load_audio", "design_taps", "resample_batch", "resample_ratio", "banded_tables"]
+from . import ragged
+
+__all__ = ["read_wav_header", "load_wav", "load_audio", "design_taps", "resample_batch", "resample_ratio", "banded_tables",
+           "plan_wav_batch", "load_wav_batch", "decode_wav_batch", "resample_ragged_batch", "resample_out_lengths", "load_audio_batch"]
 
 _FMT = {("int", 8): 1, ("int", 16): 2, ("int", 24): 3, ("int", 32): 4, ("float", 32): 5, ("float", 64): 6}
 
@@ -300,3 +305,202 @@ def load_audio(path, sr=None, device=None):
     if sr is not None and float(sr) != file_sr and x.shape[1] > 0:
         x = resample_batch(x, file_sr, float(sr))
     return x
+
+
+# ---- a list of files: one padded batch with a length per row ---------------------------------------
+ALIGN = 16                       # every file's data starts at a multiple of 16 bytes in the raw buffer (16-byte loads)
+WAV_REC = np.dtype([("byte_offset", "<i8"), ("n_frames", "<i8"), ("fmt", "<i4"), ("channels", "<i4"), ("first_row", "<i8")])
+_BPS = {1: 1, 2: 2, 3: 3, 4: 4, 5: 4, 6: 8}
+
+
+def plan_wav_batch(headers):
+    """The layout of load_wav_batch for the ``read_wav_header`` dicts of B files, host arithmetic only (no GPU):
+    dict(offsets int64 [B] -- where each file's data chunk goes in the one raw buffer, multiples of 16 --, nbytes int64
+    [B], total_bytes, frames int64 [B], channels int64 [B], first_row int64 [B + 1] -- file i owns the rows
+    first_row[i] .. first_row[i + 1] - 1, one per channel, in file and channel order --, row_file / row_channel int64
+    [R], table -- one mm_wav_rec per file as a numpy structured array (WAV_REC) --, n_max).  A file without frames or
+    with an encoding the decoder does not know raises ValueError with the file's index."""
+    headers = list(headers)
+    if not headers:
+        raise ValueError("plan_wav_batch: no files")
+    B = len(headers)
+    table = np.zeros(B, dtype=WAV_REC)
+    for i, h in enumerate(headers):
+        fmt, ch, n = int(h["fmt"]), int(h["channels"]), int(h["n_frames"])
+        if fmt not in _BPS or ch < 1:
+            raise ragged.named(ValueError(f"unsupported WAVE encoding (format code {fmt}, {ch} channels)"), i, "file")
+        if n < 1:
+            raise ragged.named(ValueError("the WAVE file holds no frames"), i, "file")
+        table[i] = (0, n, fmt, ch, 0)
+    frames = table["n_frames"].astype(np.int64)
+    channels = table["channels"].astype(np.int64)
+    nbytes = frames * channels * np.array([_BPS[int(f)] for f in table["fmt"]], dtype=np.int64)
+    ends = np.cumsum(-(-nbytes // ALIGN) * ALIGN)
+    offsets = np.concatenate([[0], ends[:-1]]).astype(np.int64)
+    first_row = np.concatenate([[0], np.cumsum(channels)]).astype(np.int64)
+    table["byte_offset"], table["first_row"] = offsets, first_row[:-1]
+    row_file = np.repeat(np.arange(B, dtype=np.int64), channels)
+    return dict(offsets=offsets, nbytes=nbytes, total_bytes=int(ends[-1]), frames=frames, channels=channels,
+                first_row=first_row, row_file=row_file, row_channel=np.arange(int(first_row[-1]), dtype=np.int64) - first_row[row_file],
+                table=table, n_max=int(frames.max()))
+
+
+def _device(torch, device):
+    return torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+
+
+def load_wav_batch(paths, device=None):
+    """B WAVE files -> (x float32 [R, n_max] on the device, lengths int64 numpy [R], rates float64 numpy [R], first_row
+    int64 numpy [B + 1]): every channel of every file as one row, in file and channel order (file i owns rows
+    first_row[i] .. first_row[i + 1] - 1), each row bit for bit what ``load_wav`` gives and +0.0 behind its frames.
+    The data chunks are read into ONE pinned host buffer, go to the device in ONE copy and are decoded by ONE launch
+    (mm_pcm_decode_ragged_f32), whatever the mix of formats and channel counts.  A file that is no WAVE file, holds no
+    frames or has an unsupported encoding raises ValueError with its index."""
+    import torch
+    paths = list(paths)
+    headers = []
+    for i, p in enumerate(paths):
+        try:
+            headers.append(read_wav_header(p))
+        except ValueError as e:
+            raise ragged.named(e, i, "file")
+    pl = plan_wav_batch(headers)                     # (the files' own refusals come first: they need no device)
+    if not torch.cuda.is_available():
+        raise RuntimeError("modulation_mfcc_amd needs an AMD GPU (gfx950); there is no CPU fallback")
+    dev = _device(torch, device)
+    host = torch.empty(pl["total_bytes"], dtype=torch.uint8, pin_memory=True)
+    raw = host.numpy()
+    for i, (p, h) in enumerate(zip(paths, headers)):
+        o, nb = int(pl["offsets"][i]), int(pl["nbytes"][i])
+        with open(p, "rb", buffering=0) as f:
+            f.seek(h["data_offset"])
+            if f.readinto(memoryview(raw[o:o + nb])) != nb:
+                raise ragged.named(ValueError(f"{p}: the data chunk ends before its {nb} bytes"), i, "file")
+    d_raw = host.to(dev, non_blocking=True)
+    d_tab = torch.from_numpy(pl["table"].view(np.uint8)).to(dev, non_blocking=True)
+    rates = np.array([h["sr"] for h in headers], dtype=np.float64)[pl["row_file"]]
+    return decode_wav_batch(d_raw, d_tab, pl), pl["frames"][pl["row_file"]], rates, pl["first_row"]
+
+
+def decode_wav_batch(d_raw, d_tab, pl):
+    """The one decode launch of load_wav_batch: the raw buffer and the record table of plan_wav_batch ``pl``, both on the
+    device as uint8 tensors -> float32 [R, n_max] (a view of rows whose pitch is a multiple of 4)."""
+    import torch
+    from . import _lib
+    dev = d_raw.device
+    R, n_max = int(pl["first_row"][-1]), pl["n_max"]
+    pitch = -(-n_max // 4) * 4                                   # 16-byte aligned rows: vector stores here, vector staging later
+    out = torch.empty((R, pitch), dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        _lib.check(lib.mm_pcm_decode_ragged_f32(d_raw.data_ptr(), pl["total_bytes"], d_tab.data_ptr(), len(pl["frames"]), n_max,
+                                                out.data_ptr(), R, pitch, _stream(torch, dev)), "mm_pcm_decode_ragged_f32")
+    return out[:, :n_max]
+
+
+def resample_out_lengths(lengths, L, M):
+    """ceil(n L / M) per row, in 64-bit: what both resamplers return for n samples.  An int64 numpy array in, one out; an
+    int64 tensor in, a tensor on its device out (no read-back)."""
+    t = lengths * int(L)
+    t += int(M) - 1
+    t //= int(M)
+    return t
+
+
+def resample_ragged_batch(x, lengths, sr_in: float, sr_out: float, method: str = "auto"):
+    """``resample_batch`` for a padded batch [rows, n_max] with one length per row -> (y float32 [rows, n_out_max],
+    out_lengths): columns [0, out_lengths[b]) of row b are bit for bit ``resample_batch(x[b, :lengths[b]], ...)``,
+    +0.0 behind them; nothing behind a row's length is read.  One launch (mm_resample_banded_ragged_f32, or
+    mm_resample_ragged_f32 per 65535 rows), whatever the lengths.
+
+    ``lengths``: host integers (validated: every value in [1, n_max]; the call is cut to the longest row and
+    out_lengths is an int64 numpy array) or an int64 tensor on x's device (never read back: the kernels clamp it into
+    [1, n_max], out_lengths is a device tensor of the clamped values' ceil(n L / M)).  ``method`` as in resample_batch:
+    'auto' falls back to the float64 kernel where the banded one does not apply, 'mfma' raises NotImplementedError
+    there.  Equal rates return the valid parts copied, zeros behind them."""
+    import torch
+    from . import _lib
+    x = ragged.device_rows(x, (torch.float32,), "x must be a float32 CUDA(HIP) tensor", "x must be [rows, n_max] with rows, n_max >= 1")
+    if method not in ("auto", "mfma", "f64"):
+        raise ValueError("method must be 'auto', 'mfma' or 'f64'")
+    rows = x.shape[0]
+    lens = ragged.check_lengths(lengths, rows, x.shape[1], x.device)
+    if isinstance(lens, np.ndarray):
+        x = x[:, :int(lens.max())]
+        n_in = lens
+    else:
+        n_in = lens.clamp(1, x.shape[1])
+    n_max = x.shape[1]
+    L, M = resample_ratio(sr_in, sr_out)
+    d_lens = ragged.counts_on_device(lens, x.device)
+    if L == M:
+        keep = torch.arange(n_max, device=x.device)[None, :] < d_lens.clamp(1, n_max)[:, None]
+        return torch.where(keep, x, x.new_zeros(())), n_in
+    n_out = -(-n_max * L // M)
+    out = torch.empty((rows, n_out), dtype=torch.float32, device=x.device)
+    pitch = ragged.row_pitch(x)
+    lib = _lib.load()
+    done = False
+    if method != "f64":
+        tb = _device_banded(L, M, x.device)
+        with torch.cuda.device(x.device):
+            rc = lib.mm_resample_banded_ragged_f32(x.data_ptr(), rows, n_max, pitch, d_lens.data_ptr(), tb["d_atab"].data_ptr(),
+                                                   tb["d_lo_off"].data_ptr(), tb["F"], tb["S"], tb["NB"], tb["ksteps"],
+                                                   tb["lo_min"], tb["win"], out.data_ptr(), n_out, n_out, _stream(torch, x.device))
+        if not (rc == _lib.MM_ERR_UNSUPPORTED and method == "auto"):
+            _lib.check(rc, "mm_resample_banded_ragged_f32")
+            done = True
+    if not done:
+        taps, tpp, half = _device_taps(L, M, x.device)
+        with torch.cuda.device(x.device):
+            for r0 in range(0, rows, 65535):         # the kernel's grid takes the rows on its y axis
+                r = min(65535, rows - r0)
+                _lib.check(lib.mm_resample_ragged_f32(x[r0:].data_ptr(), r, n_max, pitch, d_lens[r0:].data_ptr(), taps.data_ptr(),
+                                                      L, M, tpp, half, out[r0:].data_ptr(), n_out, n_out,
+                                                      _stream(torch, x.device)), "mm_resample_ragged_f32")
+    return out, resample_out_lengths(n_in, L, M)
+
+
+def load_audio_batch(paths, sr=None, channel=0, device=None):
+    """``load_audio`` for a list of WAVE files -> (x float32 [R, n_max'] on the device, lengths int64 numpy [R]): row by
+    row bit for bit what ``load_audio(path, sr)`` gives for that file alone, in a fixed number of launches -- one decode
+    for all files (load_wav_batch) and one ragged resample per distinct source rate (resample_ragged_batch; files
+    already at ``sr`` are copied unchanged).  What lies behind a row's length is zero.
+
+    ``channel=k``: one row per file, its channel k as get_MFCCS_change picks ``channelN`` (a mono file gives its only
+    channel); R = B.  ``channel=None``: every channel, in file and channel order, and first_row (int64 [B + 1]: file i
+    owns rows first_row[i] .. first_row[i + 1] - 1) is returned as a third value.  ``sr=None`` keeps each file's rate
+    and returns the rates (float64 numpy [R]) after the lengths."""
+    import torch
+    x, lengths, rates, first_row = load_wav_batch(paths, device)
+    if channel is not None:
+        nch = np.diff(first_row)
+        k = int(channel)
+        bad = np.flatnonzero((nch > 1) & ((k >= nch) | (k < -nch)))
+        if bad.size:
+            raise ragged.named(IndexError(f"index {k} is out of bounds for a file of {int(nch[bad[0]])} channels"), bad[0], "file")
+        pick = first_row[:-1] + np.where(nch > 1, k % nch, 0)
+        lengths, rates = lengths[pick], rates[pick]
+        if pick.shape[0] != x.shape[0]:
+            x = x.index_select(0, torch.from_numpy(pick).to(x.device))
+        tail = ()
+    else:
+        tail = (first_row,)
+    if sr is None:
+        return (x[:, :int(lengths.max())], lengths, rates) + tail
+    groups = ragged.group_rows(rates)
+    out_len = lengths.copy()
+    for rate, idx in groups:
+        if float(rate) != float(sr):
+            out_len[idx] = resample_out_lengths(lengths[idx], *resample_ratio(float(rate), float(sr)))
+    if len(groups) == 1:
+        if float(groups[0][0]) == float(sr):
+            return (x[:, :int(lengths.max())], lengths) + tail
+        return (resample_ragged_batch(x, lengths, float(groups[0][0]), float(sr))[0], out_len) + tail
+    out = torch.zeros((x.shape[0], int(out_len.max())), dtype=torch.float32, device=x.device)
+    for rate, idx in groups:
+        d_idx = torch.from_numpy(idx).to(x.device)
+        xg = x.index_select(0, d_idx)[:, :int(lengths[idx].max())]
+        yg = xg if float(rate) == float(sr) else resample_ragged_batch(xg, lengths[idx], float(rate), float(sr))[0]
+        out[:, :yg.shape[1]].index_copy_(0, d_idx, yg)
+    return (out, out_len) + tail

@@ -27,12 +27,21 @@ struct RsmParams {
   int F, S, NB, ksteps, lo_min, QT, tile_floats;
   float* y;
   int64_t n_out, tiles_per_row, n_items;
+  const int64_t* lens;          // RAGGED: [rows] valid samples per row (device), clamped into [1, n_in] by the kernel
+  int64_t y_stride;             // RAGGED: output row pitch >= n_out (the uniform entry's rows are n_out apart)
 };
 
 // PAD: one pad word per 32 in the LDS tile (strides S that put the 16 periods of a read on few banks);
 // VEC: rows are 16-byte aligned (base pointer and pitch): the tile starts at a multiple of four samples and is staged
 // with 16-byte loads.
-template <bool PAD, bool VEC>
+// RAGGED (mm_resample_banded_ragged_f32): row b holds n_b = clamp(lens[b], 1, n_in) samples and gets n_out_b =
+// ceil(n_b F / S) (= ceil(n_b L / M): F / S is L / M) outputs, +0.0 behind them up to n_out.  n_b takes the place of
+// n_in in the staging bounds -- the tile geometry (q0, g0) does not depend on it, so the outputs are those of the row
+// called alone --; it is read once per item through `row`, which derives from blockIdx.x and the item counter alone:
+// a scalar load, the same value in every wave, so the branch around the two barriers of an item is taken by the whole
+// workgroup or by none of it.  A tile wholly behind n_out_b stages nothing, multiplies nothing and stores zeros; in
+// the last tile with outputs, a unit wholly behind n_out_b skips its multiplies.
+template <bool PAD, bool VEC, bool RAGGED = false>
 __global__ __launch_bounds__(256) void resample_mfma_kernel(RsmParams p) {
   extern __shared__ __attribute__((aligned(16))) float rsm_xs[];
   float* xs = rsm_xs;
@@ -48,8 +57,28 @@ __global__ __launch_bounds__(256) void resample_mfma_kernel(RsmParams p) {
   const int n_units = p.NB * p.QT;
   for (int64_t item = blockIdx.x; item < p.n_items; item += gridDim.x) {
     const int64_t row = item / p.tiles_per_row;
-    const int64_t q0 = (item - row * p.tiles_per_row) * periods;
+    int64_t tile = item - row * p.tiles_per_row;
+    if (RAGGED) {
+      // rotate the row's tiles by a hash of the row: workgroups land on the CUs round-robin, and with tile = item mod
+      // tiles_per_row a CU would meet the same tile of every row -- the CUs with the first tiles, which no row leaves
+      // empty, would do all the work.  A rotation per row: every (row, tile) still belongs to exactly one item.
+      tile = (tile + (int64_t)(((uint32_t)row * 2654435761u) >> 8)) % p.tiles_per_row;
+    }
+    const int64_t q0 = tile * periods;
     const float* xr = p.x + row * p.x_stride;
+    int64_t n_in = p.n_in, n_out_row = p.n_out;
+    if (RAGGED) {
+      const int64_t len = p.lens[row];
+      n_in = len < 1 ? 1 : (len > p.n_in ? p.n_in : len);
+      n_out_row = (n_in * p.F + p.S - 1) / p.S;
+      const int64_t m0 = q0 * p.F;
+      if (m0 >= n_out_row) {                            // workgroup-uniform: no barrier is skipped by a part of it
+        const int64_t m1 = m0 + (int64_t)periods * p.F < p.n_out ? m0 + (int64_t)periods * p.F : p.n_out;
+        float* yr = p.y + row * p.y_stride;
+        for (int64_t m = m0 + threadIdx.x; m < m1; m += 256) yr[m] = 0.0f;
+        continue;
+      }
+    }
     int64_t g0 = q0 * (int64_t)p.S + p.lo_min;
     const int sh = VEC ? (int)(g0 & 3) : 0;                // tile word i holds x[g0 + i] with g0 a multiple of 4
     g0 -= sh;
@@ -65,13 +94,13 @@ __global__ __launch_bounds__(256) void resample_mfma_kernel(RsmParams p) {
           const int64_t gi = g0 + 4 * (int64_t)c;
           v[u] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
           if (c < n4) {
-            if (gi >= 0 && gi + 3 < p.n_in) {
+            if (gi >= 0 && gi + 3 < n_in) {
               v[u] = *reinterpret_cast<const float4*>(xr + gi);
-            } else if (gi + 3 >= 0 && gi < p.n_in) {      // the vector straddles an end of the clip
-              v[u].x = (gi >= 0 && gi < p.n_in) ? xr[gi] : 0.0f;
-              v[u].y = (gi + 1 >= 0 && gi + 1 < p.n_in) ? xr[gi + 1] : 0.0f;
-              v[u].z = (gi + 2 >= 0 && gi + 2 < p.n_in) ? xr[gi + 2] : 0.0f;
-              v[u].w = (gi + 3 >= 0 && gi + 3 < p.n_in) ? xr[gi + 3] : 0.0f;
+            } else if (gi + 3 >= 0 && gi < n_in) {      // the vector straddles an end of the clip
+              v[u].x = (gi >= 0 && gi < n_in) ? xr[gi] : 0.0f;
+              v[u].y = (gi + 1 >= 0 && gi + 1 < n_in) ? xr[gi + 1] : 0.0f;
+              v[u].z = (gi + 2 >= 0 && gi + 2 < n_in) ? xr[gi + 2] : 0.0f;
+              v[u].w = (gi + 3 >= 0 && gi + 3 < n_in) ? xr[gi + 3] : 0.0f;
             }
           }
         }
@@ -96,7 +125,7 @@ __global__ __launch_bounds__(256) void resample_mfma_kernel(RsmParams p) {
         for (int u = 0; u < 32; ++u) {
           const int i = i0 + 256 * u;
           const int64_t gi = g0 + i;
-          v[u] = (i < p.tile_floats && gi >= 0 && gi < p.n_in) ? xr[gi] : 0.0f;
+          v[u] = (i < p.tile_floats && gi >= 0 && gi < n_in) ? xr[gi] : 0.0f;
         }
 #pragma unroll
         for (int u = 0; u < 32; ++u) {
@@ -153,32 +182,41 @@ __global__ __launch_bounds__(256) void resample_mfma_kernel(RsmParams p) {
       // of group g issue -- 512 cycles of this wave's matrix work (twice that with the SIMD's second wave) cover the
       // L2 round trip of the A loads and the LDS reads; the sched_barriers keep the compiler from sinking the
       // requests back to their uses.
-      load_ab(0, 0);
-      load_ab(1, 1);
-      for (int g = 0; g < G; g += 3) {
-        load_ab(g + 2, 2);
-        __builtin_amdgcn_sched_barrier(0);
-        mfma8(0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (g + 1 < G) {
-          load_ab(g + 3, 0);
+      // RAGGED: a unit whose first output lies behind the row's last one only stores zeros (wave-uniform; no barrier
+      // inside the unit loop)
+      if (!RAGGED || (q0 + qt * 16) * (int64_t)p.F + 16 * b < n_out_row) {
+        load_ab(0, 0);
+        load_ab(1, 1);
+        for (int g = 0; g < G; g += 3) {
+          load_ab(g + 2, 2);
           __builtin_amdgcn_sched_barrier(0);
-          mfma8(1);
+          mfma8(0);
           __builtin_amdgcn_sched_barrier(0);
+          if (g + 1 < G) {
+            load_ab(g + 3, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            mfma8(1);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+          if (g + 2 < G) {
+            load_ab(g + 4, 1);
+            __builtin_amdgcn_sched_barrier(0);
+            mfma8(2);
+            __builtin_amdgcn_sched_barrier(0);
+          }
         }
-        if (g + 2 < G) {
-          load_ab(g + 4, 1);
-          __builtin_amdgcn_sched_barrier(0);
-          mfma8(2);
-          __builtin_amdgcn_sched_barrier(0);
-        }
+        acc += acc1;
       }
-      acc += acc1;
       // D[i = 4 kq + v][j = n]: four consecutive outputs of period q0 + 16 qt + n; rows past the period's F outputs
       // (the last block of a period that is not a multiple of 16) belong to the next period's first block
       const int r0 = 16 * b + 4 * kq;
       const int64_t m = (q0 + qt * 16 + n) * (int64_t)p.F + r0;
-      float* yo = p.y + row * p.n_out + m;
+      float* yo = p.y + row * (RAGGED ? p.y_stride : p.n_out) + m;
+      if (RAGGED) {                                     // +0.0 behind the row's own outputs
+#pragma unroll
+        for (int v = 0; v < 4; ++v)
+          if (m + v >= n_out_row) acc[v] = 0.0f;
+      }
       if (r0 + 3 < p.F && m + 3 < p.n_out && ((reinterpret_cast<uintptr_t>(yo) & 15) == 0)) {
         *reinterpret_cast<float4*>(yo) = make_float4(acc[0], acc[1], acc[2], acc[3]);
       } else {

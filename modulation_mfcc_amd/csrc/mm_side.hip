@@ -170,12 +170,8 @@ int mm_rms_ragged_f32(const float* d_audio, int64_t batch, int64_t n_max, int64_
 // interleaved PCM frames -> planar float32 [channels][n]; fmt: 1 = u8, 2 = s16, 3 = s24 (packed), 4 = s32,
 // 5 = f32, 6 = f64 (little endian; scaling as libsndfile / soundfile: s16 / 32768, s24 / 2^23, s32 / 2^31,
 // u8 (x - 128) / 128)
-__global__ __launch_bounds__(256) void pcm_decode_kernel(const unsigned char* __restrict__ raw, int fmt, int channels,
-                                                         int64_t n, float* __restrict__ out, int64_t out_stride) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= n * channels) return;
-  const int64_t fr = idx / channels;
-  const int ch = (int)(idx - fr * channels);
+// sample idx (frame * channels + channel) of the interleaved data: the one conversion of both decode entries
+__device__ __forceinline__ float pcm_sample(const unsigned char* __restrict__ raw, int fmt, int64_t idx) {
   float v;
   switch (fmt) {
     case 1: v = ((float)raw[idx] - 128.0f) * (1.0f / 128.0f); break;
@@ -192,7 +188,16 @@ __global__ __launch_bounds__(256) void pcm_decode_kernel(const unsigned char* __
                for (int b = 0; b < 8; ++b) u |= (unsigned long long)raw[8 * idx + b] << (8 * b);
                v = (float)__longlong_as_double((long long)u); break; }
   }
-  out[(int64_t)ch * out_stride + fr] = v;
+  return v;
+}
+
+__global__ __launch_bounds__(256) void pcm_decode_kernel(const unsigned char* __restrict__ raw, int fmt, int channels,
+                                                         int64_t n, float* __restrict__ out, int64_t out_stride) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= n * channels) return;
+  const int64_t fr = idx / channels;
+  const int ch = (int)(idx - fr * channels);
+  out[(int64_t)ch * out_stride + fr] = pcm_sample(raw, fmt, idx);
 }
 
 // 16-bit PCM, mono or stereo (what almost every WAVE file is): a thread takes 16 bytes = 8 samples with ONE load and
@@ -272,6 +277,97 @@ int mm_pcm_decode_f32(const void* d_raw, int32_t fmt, int32_t channels, int64_t 
   return MM_OK;
 }
 
+// The data chunks of many files in one buffer, one record per file (mm_wav_rec): ONE launch for any mix of formats and
+// channel counts.  An item is (file, chunk of MM_PCMR_CHUNK frames); its workgroup writes those frames of every channel
+// row of the file -- +0.0 from the file's last frame up to max_frames, so the batch needs no memset.  A chunk that lies
+// wholly inside a 16-bit or float32 mono / stereo file on 16-byte aligned addresses takes 8 frames per thread with
+// 16-byte loads and stores (the arithmetic of pcm_decode_s16_kernel / pcm_decode_f32_kernel); every other chunk goes
+// sample by sample through pcm_sample, a frame per thread (coalesced stores).  Both choices depend on the item alone:
+// workgroup-uniform.  A record that points outside the buffer, or names no format, decodes as an empty file.
+#define MM_PCMR_CHUNK 2048
+__global__ __launch_bounds__(256) void pcm_decode_ragged_kernel(const unsigned char* __restrict__ raw, int64_t raw_bytes,
+                                                                const mm_wav_rec* __restrict__ recs, int64_t n_files,
+                                                                int64_t chunks, int64_t max_frames, float* __restrict__ out,
+                                                                int64_t out_rows, int64_t out_stride, int vec_ok) {
+  const int64_t n_items = n_files * chunks;
+  for (int64_t item = blockIdx.x; item < n_items; item += gridDim.x) {
+    const int64_t file = item / chunks;
+    const int64_t f0 = (item - file * chunks) * MM_PCMR_CHUNK;
+    const mm_wav_rec rec = recs[file];
+    const int fmt = rec.fmt, channels = rec.channels;
+    if (channels < 1 || rec.first_row < 0 || rec.first_row + channels > out_rows) continue;
+    const int bps = fmt == 1 ? 1 : fmt == 2 ? 2 : fmt == 3 ? 3 : fmt == 6 ? 8 : 4;
+    int64_t n = rec.n_frames < max_frames ? rec.n_frames : max_frames;
+    if (fmt < 1 || fmt > 6 || n < 0 || rec.byte_offset < 0 || rec.byte_offset > raw_bytes ||
+        n > (raw_bytes - rec.byte_offset) / ((int64_t)channels * bps))
+      n = 0;
+    const unsigned char* src = raw + rec.byte_offset;
+    float* o = out + rec.first_row * out_stride;
+    if (vec_ok && (fmt == 2 || fmt == 5) && channels <= 2 && f0 + MM_PCMR_CHUNK <= n && (rec.byte_offset & 15) == 0) {
+      const int64_t fr = f0 + 8 * threadIdx.x;         // this thread's 8 frames
+      if (fmt == 2) {
+        float f[16];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          if (h < channels) {
+            const uint4 w = *reinterpret_cast<const uint4*>(src + 2 * (fr * channels + 8 * h));
+            const unsigned u[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              f[8 * h + 2 * i] = (float)(short)(u[i] & 0xFFFFu) * (1.0f / 32768.0f);
+              f[8 * h + 2 * i + 1] = (float)(short)(u[i] >> 16) * (1.0f / 32768.0f);
+            }
+          }
+        }
+        if (channels == 1) {
+          *reinterpret_cast<float4*>(o + fr) = make_float4(f[0], f[1], f[2], f[3]);
+          *reinterpret_cast<float4*>(o + fr + 4) = make_float4(f[4], f[5], f[6], f[7]);
+        } else {
+          *reinterpret_cast<float4*>(o + fr) = make_float4(f[0], f[2], f[4], f[6]);
+          *reinterpret_cast<float4*>(o + fr + 4) = make_float4(f[8], f[10], f[12], f[14]);
+          *reinterpret_cast<float4*>(o + out_stride + fr) = make_float4(f[1], f[3], f[5], f[7]);
+          *reinterpret_cast<float4*>(o + out_stride + fr + 4) = make_float4(f[9], f[11], f[13], f[15]);
+        }
+      } else {
+        const float4* s4 = reinterpret_cast<const float4*>(src + 4 * fr * channels);
+        if (channels == 1) {
+          const float4 a = s4[0], b = s4[1];
+          *reinterpret_cast<float4*>(o + fr) = a;
+          *reinterpret_cast<float4*>(o + fr + 4) = b;
+        } else {
+          const float4 a = s4[0], b = s4[1], c = s4[2], d = s4[3];
+          *reinterpret_cast<float4*>(o + fr) = make_float4(a.x, a.z, b.x, b.z);
+          *reinterpret_cast<float4*>(o + fr + 4) = make_float4(c.x, c.z, d.x, d.z);
+          *reinterpret_cast<float4*>(o + out_stride + fr) = make_float4(a.y, a.w, b.y, b.w);
+          *reinterpret_cast<float4*>(o + out_stride + fr + 4) = make_float4(c.y, c.w, d.y, d.w);
+        }
+      }
+      continue;
+    }
+    for (int ch = 0; ch < channels; ++ch) {
+#pragma unroll
+      for (int u = 0; u < MM_PCMR_CHUNK / 256; ++u) {
+        const int64_t fr = f0 + 256 * u + threadIdx.x;
+        if (fr < max_frames) o[ch * out_stride + fr] = fr < n ? pcm_sample(src, fmt, fr * channels + ch) : 0.0f;
+      }
+    }
+  }
+}
+
+int mm_pcm_decode_ragged_f32(const void* d_raw, int64_t raw_bytes, const mm_wav_rec* d_recs, int64_t n_files,
+                             int64_t max_frames, float* d_out, int64_t out_rows, int64_t out_stride, void* stream) {
+  if (!d_raw || !d_recs || !d_out || raw_bytes < 1 || n_files < 1 || max_frames < 1 || out_rows < 1 || out_stride < max_frames)
+    return MM_ERR_INVALID_ARG;
+  const int64_t chunks = (max_frames + MM_PCMR_CHUNK - 1) / MM_PCMR_CHUNK;
+  if (n_files > 0x7FFFFFFF / chunks) return MM_ERR_INVALID_ARG;
+  const int vec_ok = (((uintptr_t)d_raw | (uintptr_t)d_out) & 15) == 0 && (out_stride & 3) == 0;
+  hipLaunchKernelGGL(pcm_decode_ragged_kernel, dim3((unsigned)(n_files * chunks)), dim3(256), 0, (hipStream_t)stream,
+                     (const unsigned char*)d_raw, raw_bytes, d_recs, n_files, chunks, max_frames, d_out, out_rows, out_stride,
+                     vec_ok);
+  HIP_TRY(hipGetLastError());
+  return MM_OK;
+}
+
 // Rational-ratio polyphase FIR sample-rate conversion: output m = sum_j h[ph + j L] x[ih - j] with t = m M + c,
 // ih = t div L, ph = t mod L, zero signal outside the clip -- upfirdn with the filter delay c removed, n_out =
 // ceil(n L / M) (what scipy.signal.resample_poly and librosa.resample return); float64 accumulation.
@@ -283,14 +379,32 @@ int mm_pcm_decode_f32(const void* d_raw, int32_t fmt, int32_t channels, int64_t 
 // thread per output, taps in polyphase order [L][tpp], i.e. a 2 KB stride between lanes -- ran at 0.3 T
 // multiply-adds per second: 66 ms for 256 ten-second clips 44.1 -> 16 kHz.)
 #define MM_RS_P 4
+// kRagged (mm_resample_ragged_f32): row r holds n_r = clamp(lens[r], 1, n_in) samples -- n_r takes the place of n_in in
+// the jlo / jhi window, so the unaligned 16-byte loads stay inside the row's valid part -- and gets ceil(n_r L / M)
+// outputs, +0.0 behind them up to n_out.  An output is its own k-ordered fma chain: it does not depend on F.
 struct __attribute__((packed, aligned(4))) MmRsFloat4U { float x, y, z, w; };
+extern "C++" {
+template <bool kRagged>
 __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__ x, int64_t n_in, int64_t in_stride,
                                                        const float* __restrict__ hq, int L, int M, int tpp4, int64_t c,
-                                                       int64_t n_out, int64_t F, float* __restrict__ y) {
+                                                       int64_t n_out, int64_t F, float* __restrict__ y,
+                                                       const int64_t* __restrict__ lens, int64_t y_stride) {
   const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (f >= F) return;
   const int64_t r = blockIdx.y;
   const float* xr = x + r * in_stride;
+  int64_t n_out_row = n_out;
+  if (kRagged) {
+    const int64_t len = lens[r];
+    n_in = len < 1 ? 1 : (len > n_in ? n_in : len);
+    n_out_row = (n_in * L + M - 1) / M;
+    if (f >= n_out_row) {                           // every output of this thread lies behind the row's last one
+#pragma unroll
+      for (int i = 0; i < MM_RS_P; ++i)
+        if (f + i * F < n_out) y[r * y_stride + f + i * F] = 0.0f;
+      return;
+    }
+  }
   const int t = (int)(f % L);
   const int64_t t0 = f * M + c;                   // F is a multiple of L: output f + i F has the phase of output f
   const int64_t ih0 = t0 / L, step = (F / L) * M;
@@ -342,13 +456,20 @@ __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__
 #pragma unroll
   for (int i = 0; i < MM_RS_P; ++i) {
     const int64_t m = f + i * F;
-    if (m < n_out) y[r * n_out + m] = (float)acc[i];
+    if (kRagged) {
+      if (m < n_out) y[r * y_stride + m] = m < n_out_row ? (float)acc[i] : 0.0f;
+    } else {
+      if (m < n_out) y[r * n_out + m] = (float)acc[i];
+    }
   }
 }
+}  // extern "C++"
 
-int mm_resample_f32(const float* d_x, int64_t rows, int64_t n_in, int64_t x_stride, const float* d_taps, int32_t L, int32_t M,
-                    int32_t taps_per_phase, int64_t half_len, float* d_y, int64_t n_out, void* stream) {
-  if (!d_x || !d_taps || !d_y || rows < 1 || n_in < 1 || x_stride < n_in || L < 1 || M < 1 || taps_per_phase < 4 ||
+// mm_resample_f32 (d_lens null, rows n_out apart) and mm_resample_ragged_f32: the same launch shape, that of n_in
+static int resample_launch(const float* d_x, int64_t rows, int64_t n_in, int64_t x_stride, const int64_t* d_lens,
+                           const float* d_taps, int32_t L, int32_t M, int32_t taps_per_phase, int64_t half_len, float* d_y,
+                           int64_t n_out, int64_t y_stride, void* stream) {
+  if (!d_x || !d_taps || !d_y || y_stride < n_out || rows < 1 || n_in < 1 || x_stride < n_in || L < 1 || M < 1 || taps_per_phase < 4 ||
       (taps_per_phase & 3) || half_len < 0 || n_out < 1 || rows > 65535 || (((uintptr_t)d_taps) & 15))
     return MM_ERR_INVALID_ARG;
   if (n_out != (n_in * L + M - 1) / M) return MM_ERR_INVALID_ARG;
@@ -356,10 +477,28 @@ int mm_resample_f32(const float* d_x, int64_t rows, int64_t n_in, int64_t x_stri
   const int64_t per = (n_out + MM_RS_P - 1) / MM_RS_P;
   const int64_t F = (per + L - 1) / L * L;
   if ((F + 255) / 256 > 0x7FFFFFFF) return MM_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(resample_kernel, dim3((unsigned)((F + 255) / 256), (unsigned)rows), dim3(256), 0, (hipStream_t)stream, d_x,
-                     n_in, x_stride, d_taps, L, M, taps_per_phase / 4, half_len, n_out, F, d_y);
+  const dim3 gd((unsigned)((F + 255) / 256), (unsigned)rows), bd(256);
+  if (d_lens)
+    hipLaunchKernelGGL(resample_kernel<true>, gd, bd, 0, (hipStream_t)stream, d_x, n_in, x_stride, d_taps, L, M,
+                       taps_per_phase / 4, half_len, n_out, F, d_y, d_lens, y_stride);
+  else
+    hipLaunchKernelGGL(resample_kernel<false>, gd, bd, 0, (hipStream_t)stream, d_x, n_in, x_stride, d_taps, L, M,
+                       taps_per_phase / 4, half_len, n_out, F, d_y, d_lens, y_stride);
   HIP_TRY(hipGetLastError());
   return MM_OK;
+}
+
+int mm_resample_f32(const float* d_x, int64_t rows, int64_t n_in, int64_t x_stride, const float* d_taps, int32_t L, int32_t M,
+                    int32_t taps_per_phase, int64_t half_len, float* d_y, int64_t n_out, void* stream) {
+  return resample_launch(d_x, rows, n_in, x_stride, nullptr, d_taps, L, M, taps_per_phase, half_len, d_y, n_out, n_out, stream);
+}
+
+int mm_resample_ragged_f32(const float* d_x, int64_t rows, int64_t n_max, int64_t x_stride, const int64_t* d_lens,
+                           const float* d_taps, int32_t L, int32_t M, int32_t taps_per_phase, int64_t half_len, float* d_y,
+                           int64_t n_out_max, int64_t y_stride, void* stream) {
+  if (!d_lens) return MM_ERR_INVALID_ARG;
+  return resample_launch(d_x, rows, n_max, x_stride, d_lens, d_taps, L, M, taps_per_phase, half_len, d_y, n_out_max, y_stride,
+                         stream);
 }
 
 // Launch shape of the banded resampler for one set of tables (pure host arithmetic, no HIP call): pad = the LDS tile
@@ -410,10 +549,12 @@ int mm_resample_banded_shape(int32_t F, int32_t S, int32_t NB, int32_t ksteps, i
 // F = c L >= 16 outputs per period (the host picks the smallest multiple of L that wastes <= 13 % of its last block of 16),
 // S = F M / L input samples per period, lo_min = first input sample (relative to a
 // period's origin, may be negative) of the first block's window, win = floats of one period's window union.
-int mm_resample_banded_f32(const float* d_x, int64_t rows, int64_t n_in, int64_t x_stride, const float* d_atab,
-                           const int32_t* d_lo_off, int32_t F, int32_t S, int32_t NB, int32_t ksteps, int32_t lo_min,
-                           int32_t win, float* d_y, int64_t n_out, void* stream) {
-  if (!d_x || !d_atab || !d_lo_off || !d_y || rows < 1 || n_in < 1 || x_stride < n_in || n_out < 1 || (((uintptr_t)d_atab) & 15))
+// mm_resample_banded_f32 (d_lens null, rows n_out apart) and mm_resample_banded_ragged_f32: the same launch shape
+static int rsm_banded_launch(const float* d_x, int64_t rows, int64_t n_in, int64_t x_stride, const int64_t* d_lens,
+                             const float* d_atab, const int32_t* d_lo_off, int32_t F, int32_t S, int32_t NB, int32_t ksteps,
+                             int32_t lo_min, int32_t win, float* d_y, int64_t n_out, int64_t y_stride, void* stream) {
+  if (!d_x || !d_atab || !d_lo_off || !d_y || rows < 1 || n_in < 1 || x_stride < n_in || n_out < 1 || (((uintptr_t)d_atab) & 15) ||
+      y_stride < n_out)
     return MM_ERR_INVALID_ARG;
   int QT = 0;
   bool pad = false;
@@ -426,16 +567,20 @@ int mm_resample_banded_f32(const float* d_x, int64_t rows, int64_t n_in, int64_t
   q.x = d_x; q.rows = rows; q.n_in = n_in; q.x_stride = x_stride; q.atab = d_atab; q.lo_off = d_lo_off;
   q.F = F; q.S = S; q.NB = NB; q.ksteps = ksteps; q.lo_min = lo_min; q.QT = QT;
   q.tile_floats = (int)((int64_t)(16 * QT - 1) * S + win);
-  q.y = d_y; q.n_out = n_out;
+  q.y = d_y; q.n_out = n_out; q.lens = d_lens; q.y_stride = y_stride;
+  // the ragged kernel derives a row's output count as ceil(n F / S): n_out must be that of n_in, or rows would overrun it
+  if (d_lens && n_out != (n_in * F + S - 1) / S) return MM_ERR_INVALID_ARG;
   const int64_t periods = (n_out + F - 1) / F;
   q.tiles_per_row = (periods + 16 * QT - 1) / (16 * QT);
   q.n_items = rows * q.tiles_per_row;
   static PerDeviceOnce attr_once;
   {
     const int rc = per_device_once(attr_once, "resample_mfma_kernel", [] {
-      const void* kf[4] = {(const void*)resample_mfma_kernel<false, false>, (const void*)resample_mfma_kernel<false, true>,
-                           (const void*)resample_mfma_kernel<true, false>, (const void*)resample_mfma_kernel<true, true>};
-      for (int i = 0; i < 4; ++i)
+      const void* kf[8] = {(const void*)resample_mfma_kernel<false, false>, (const void*)resample_mfma_kernel<false, true>,
+                           (const void*)resample_mfma_kernel<true, false>, (const void*)resample_mfma_kernel<true, true>,
+                           (const void*)resample_mfma_kernel<false, false, true>, (const void*)resample_mfma_kernel<false, true, true>,
+                           (const void*)resample_mfma_kernel<true, false, true>, (const void*)resample_mfma_kernel<true, true, true>};
+      for (int i = 0; i < 8; ++i)
         if (hipFuncSetAttribute(kf[i], hipFuncAttributeMaxDynamicSharedMemorySize, MM_LM_LDS_MAX) != hipSuccess) return false;
       return true;
     });
@@ -450,10 +595,30 @@ int mm_resample_banded_f32(const float* d_x, int64_t rows, int64_t n_in, int64_t
   const bool vec = (((uintptr_t)d_x) & 15) == 0 && (x_stride & 3) == 0;
   const dim3 gd((unsigned)grid), bd(256);
   hipStream_t st = (hipStream_t)stream;
-  if (pad) { if (vec) hipLaunchKernelGGL((resample_mfma_kernel<true, true>), gd, bd, lds, st, q); else hipLaunchKernelGGL((resample_mfma_kernel<true, false>), gd, bd, lds, st, q); }
-  else { if (vec) hipLaunchKernelGGL((resample_mfma_kernel<false, true>), gd, bd, lds, st, q); else hipLaunchKernelGGL((resample_mfma_kernel<false, false>), gd, bd, lds, st, q); }
+  if (d_lens) {
+    if (pad) { if (vec) hipLaunchKernelGGL((resample_mfma_kernel<true, true, true>), gd, bd, lds, st, q); else hipLaunchKernelGGL((resample_mfma_kernel<true, false, true>), gd, bd, lds, st, q); }
+    else { if (vec) hipLaunchKernelGGL((resample_mfma_kernel<false, true, true>), gd, bd, lds, st, q); else hipLaunchKernelGGL((resample_mfma_kernel<false, false, true>), gd, bd, lds, st, q); }
+  } else {
+    if (pad) { if (vec) hipLaunchKernelGGL((resample_mfma_kernel<true, true>), gd, bd, lds, st, q); else hipLaunchKernelGGL((resample_mfma_kernel<true, false>), gd, bd, lds, st, q); }
+    else { if (vec) hipLaunchKernelGGL((resample_mfma_kernel<false, true>), gd, bd, lds, st, q); else hipLaunchKernelGGL((resample_mfma_kernel<false, false>), gd, bd, lds, st, q); }
+  }
   HIP_TRY(hipGetLastError());
   return MM_OK;
+}
+
+int mm_resample_banded_f32(const float* d_x, int64_t rows, int64_t n_in, int64_t x_stride, const float* d_atab,
+                           const int32_t* d_lo_off, int32_t F, int32_t S, int32_t NB, int32_t ksteps, int32_t lo_min,
+                           int32_t win, float* d_y, int64_t n_out, void* stream) {
+  return rsm_banded_launch(d_x, rows, n_in, x_stride, nullptr, d_atab, d_lo_off, F, S, NB, ksteps, lo_min, win, d_y, n_out, n_out,
+                           stream);
+}
+
+int mm_resample_banded_ragged_f32(const float* d_x, int64_t rows, int64_t n_max, int64_t x_stride, const int64_t* d_lens,
+                                  const float* d_atab, const int32_t* d_lo_off, int32_t F, int32_t S, int32_t NB, int32_t ksteps,
+                                  int32_t lo_min, int32_t win, float* d_y, int64_t n_out_max, int64_t y_stride, void* stream) {
+  if (!d_lens) return MM_ERR_INVALID_ARG;
+  return rsm_banded_launch(d_x, rows, n_max, x_stride, d_lens, d_atab, d_lo_off, F, S, NB, ksteps, lo_min, win, d_y, n_out_max,
+                           y_stride, stream);
 }
 
 // Measurement aid (bench.py): float4 grid-stride device-to-device copy on the caller's stream -- the

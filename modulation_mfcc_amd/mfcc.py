@@ -135,7 +135,8 @@ def get_MFCCS_change_batch(clips, sigSr, /, *, channelN: int = 0, tStep: float =
     each what ``get_MFCCS_change`` returns for that clip alone (its own last frame, its own time anchors).
 
     ``clips``: paths, arrays or device tensors ([n] or [channels, n]; ``channelN`` picks as in the single call).  The
-    clips are packed into one padded batch (``pack_clips``) and run through the ragged MFCC and the ragged change tail in
+    clips are packed into one padded batch (``pack_clips``; a list of paths only is decoded and resampled as one batch by
+    ``audio_io.load_audio_batch``) and run through the ragged MFCC and the ragged change tail in
     a few launches (``mfcc_change_ragged_batch``); one copy brings the curves back.  A clip with too few frames for the
     filters raises scipy's ValueError, as the single call does, with the clip's index in the message.
     """
@@ -149,8 +150,16 @@ def get_MFCCS_change_batch(clips, sigSr, /, *, channelN: int = 0, tStep: float =
     cfg = MfccConfig.from_reference_call(sigSr, tStep=tStep, winLen=winLen, n_mfcc=n_mfcc,
                                          n_fft=n_fft, minFreq=minFreq, maxFreq=maxFreq)
     plan = get_plan(cfg)
-    audio, lengths = pack_clips([_signal_row(c, sigSr, channelN, plan.device) for c in clips])
-    change, _ = mfcc_change_ragged_batch(audio, lengths, cfg, tStep=tStep, removeFirst=removeFirst, filtCutoff=filtCutoff,
+    if all(isinstance(c, str) for c in clips):
+        # a list of files: one decode launch and one ragged resample per source rate instead of a load per file; the
+        # rows are bit for bit those of the route below (audio_io.load_audio_batch)
+        import torch
+        from .audio_io import load_audio_batch
+        audio, lengths = load_audio_batch(clips, sigSr, channel=channelN, device=plan.device)
+        lengths = torch.from_numpy(lengths)
+    else:
+        audio, lengths = pack_clips([_signal_row(c, sigSr, channelN, plan.device) for c in clips])
+    change, _ =mfcc_change_ragged_batch(audio, lengths, cfg, tStep=tStep, removeFirst=removeFirst, filtCutoff=filtCutoff,
                                          filtOrd=filtOrd, diffMethod=diffMethod, outFilter=outFilter,
                                          outFiltType=outFiltType, outFiltCutOff=outFiltCutOff, outFiltLen=outFiltLen,
                                          outFiltPolyOrd=outFiltPolyOrd)
