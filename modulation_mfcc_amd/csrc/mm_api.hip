@@ -1350,7 +1350,7 @@ int mm_logmel_f32(mm_plan* p, const float* d_audio, int64_t batch, int64_t n_sam
   int rc = check_audio_args(p, d_audio, batch, n_samples, stride);
   if (rc || !d_logmel || !d_clipmax) return rc ? rc : MM_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(hipMemsetAsync(d_clipmax, 0x80, (size_t)batch * 4, st));
+  fill_words(d_clipmax, MM_KEY_UNSET, batch, st);
   {
     StageTimer tm(p, MM_STAGE_LOGMEL, st);
     const CallShape c{true, d_audio, n_samples, stride, batch, 0};
@@ -1388,7 +1388,7 @@ int mm_mfcc_f32(mm_plan* p, const float* d_audio, int64_t batch, int64_t n_sampl
   }
   {
     StageTimer tm(p, MM_STAGE_INIT, st);
-    HIP_TRY(hipMemsetAsync(keys, 0x80, (size_t)batch * 8, st));   // max keys | keys of -min
+    fill_words(keys, MM_KEY_UNSET, 2 * batch, st);   // max keys | keys of -min
   }
   {
     StageTimer tm(p, MM_STAGE_LOGMEL, st);

@@ -46,6 +46,21 @@ static int per_device_once(PerDeviceOnce& o, const char* what, F set) {
   return MM_OK;
 }
 
+// The compute entries set their few words of device scratch (clip-maximum keys, segment counts, row flags) with this
+// kernel, not with hipMemsetAsync: every entry may be captured into a hipGraph (include/modmfcc.h), and a captured
+// hipMemsetAsync becomes a memset NODE, which the HIP runtime has been seen to replay with other bytes than the call
+// named from the second replay on (tests/test_gpu_streams.py: stale words in the keys of mm_mfcc_f32 and in the row flags
+// of mm_hilbert_envelope_ragged, the eager calls right).  A kernel node carries its value in its own arguments.
+static __global__ void fill_words_kernel(uint32_t* __restrict__ p, uint32_t v, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = v;
+}
+static inline void fill_words(void* p, uint32_t v, int64_t n_words, hipStream_t st) {
+  if (n_words < 1) return;
+  hipLaunchKernelGGL(fill_words_kernel, dim3((unsigned)std::min<int64_t>((n_words + 255) / 256, 1024)), dim3(256), 0, st,
+                     (uint32_t*)p, v, n_words);
+}
+#define MM_KEY_UNSET 0x80808080u   // every byte 0x80: below the key of any float
+
 // sample i of a clip, zero outside [0, n) (the centred frames are zero-padded), with optional pre-emphasis
 __device__ __forceinline__ float load_sample(const float* __restrict__ a, int64_t i, int64_t n,
                                              float pre) {

@@ -1033,7 +1033,7 @@ static int hb_envelope_ragged(const mm_hilbert* h, const T* d_x, int64_t rows, i
   hb_c<T>* spare = (hb_c<T>*)(p + buf);
   hb_c<T>* third = (hb_c<T>*)(p + 2 * buf);
   const hb_c<double>*lo = (const hb_c<double>*)h->lo, *hi = (const hb_c<double>*)h->hi;
-  HIP_TRY(hipMemsetAsync(bad, 0, (size_t)rows * sizeof(int), st));
+  fill_words(bad, 0u, rows, st);
   // every row's chirp at its own length, and the chirps' spectra: one batched transform in the clips' precision
   hipLaunchKernelGGL(hb_chirp_ragged_kernel<T>, dim3((unsigned)((M + 255) / 256), (unsigned)rows), dim3(256), 0, st, d_x, x_stride,
                      d_lens, n_max, M, w, bhat, bad);

@@ -591,7 +591,7 @@ int pk_run(const mm_peaks_opts* o, const mm_peaks_ext* e, bool staged, const PkA
                          ws.csegcount);
     }));
   } else {
-    HIP_TRY(hipMemsetAsync(ws.csegcount, 0, (size_t)rows * ncseg * sizeof(int32_t), st));
+    fill_words(ws.csegcount, 0u, (int64_t)rows * ncseg, st);
   }
   hipLaunchKernelGGL(pk_scan_kernel, dim3((unsigned)rows), thr, 0, st, ws.csegcount, ncseg, out.count, f, cap);
   HIP_TRY(hipGetLastError());

@@ -237,7 +237,7 @@ int mm_mfcc_ragged_f32(mm_plan* p, const float* d_audio, int64_t batch, int64_t 
   {
     StageTimer tm(p, MM_STAGE_DCT, st);
     if (c.top_db >= 0.0f) {
-      HIP_TRY(hipMemsetAsync(key, 0x80, (size_t)batch * 4, st));
+      fill_words(key, MM_KEY_UNSET, batch, st);
       hipLaunchKernelGGL(ragged_max_kernel, dim3((unsigned)(batch * max_chunks)), dim3(256), 0, st, g, d_lengths, logmel,
                          c.n_mels, key);
       HIP_TRY(hipGetLastError());
