@@ -8,6 +8,8 @@ from .plan import MfccConfig, MfccPlan, get_plan, butter_sos  # noqa: F401
 from .batch import mfcc_batch, modspec_batch, mfcc_modspec_batch, rfft_batch, rms_batch  # noqa: F401
 from .batch import mfcc_ragged_batch, mfcc_modspec_ragged_batch, mfcc_change_ragged_batch, pack_clips  # noqa: F401
 from .batch import rms_ragged_batch, rms_ragged_frames  # noqa: F401
+from .batch import mfcc_modpsd_batch, mfcc_modpsd_ragged_batch  # noqa: F401
+from .modpsd import modulation_psd_batch, modulation_psd_ragged_batch, modpsd_nfft, modpsd_segments  # noqa: F401
 from .mfcc import get_MFCCS_change, get_MFCCS_change_batch, load_channel, applyFilter, get_amplitude  # noqa: F401
 from .mfcc import get_amplitude_batch  # noqa: F401
 from .calc import (get_velocity, calculate_amplitude_envelope, velocity_batch, amplitude_envelope_batch,  # noqa: F401

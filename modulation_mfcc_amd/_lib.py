@@ -1,4 +1,4 @@
-"""ctypes binding of libmodmfcc.so (include/modmfcc.h).
+"""ctypes binding of libmodmfcc.so (include/modmfcc.h and, for the Welch modulation power spectrum, include/modmfcc_modpsd.h).
 
 There is NO CPU fallback: when the shared library cannot be loaded, or a plan cannot be created
 because no MI355X is visible, the calls raise.  Build the library with
@@ -218,6 +218,29 @@ PROTOTYPES = {
     "mm_timing_read": (C.c_int, [_vp, _vp, _vp]),
 }
 
+
+class mm_modpsd_params(C.Structure):
+    _fields_ = [
+        ("fs", C.c_double),
+        ("nperseg", C.c_int32), ("noverlap", C.c_int32), ("nfft", C.c_int32),
+        ("detrend", C.c_int32), ("scaling", C.c_int32), ("reserved", C.c_int32 * 3),
+    ]
+
+
+_mpp = C.POINTER(mm_modpsd_params)
+
+# name -> (restype, argtypes); every symbol include/modmfcc_modpsd.h declares (the second header: the Welch modulation
+# power spectrum, versioned by mm_modpsd_version apart from mm_version)
+PROTOTYPES_MODPSD = {
+    "mm_modpsd_version": (C.c_int, []),
+    "mm_modpsd_check": (C.c_int, [_mpp]),
+    "mm_modpsd_num_segments": (_i64, [_mpp, _i64]),
+    "mm_modpsd_create": (C.c_int, [_mpp, _vp, C.POINTER(_vp)]),
+    "mm_modpsd_destroy": (None, [_vp]),
+    "mm_modpsd_workspace_bytes": (C.c_size_t, [_vp, _i64, _i64]),
+    "mm_modpsd_f32": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, C.c_size_t, _vp]),
+}
+
 _lib = None
 
 
@@ -239,10 +262,11 @@ def load():
             "`make -C modulation_mfcc_amd/csrc` (needs hipcc, --offload-arch=gfx950). "
             "modulation_mfcc_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in PROTOTYPES.items():
-        fn = getattr(lib, name)  # AttributeError when the .so is stale
-        fn.restype = res
-        fn.argtypes = args
+    for table in (PROTOTYPES, PROTOTYPES_MODPSD):
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name)  # AttributeError when the .so is stale
+            fn.restype = res
+            fn.argtypes = args
     if lib.mm_version() < 121:
         raise ImportError("libmodmfcc.so is older than the Python binding; rebuild it")
     _lib = lib

@@ -37,6 +37,19 @@ def mfcc_modspec_ragged_batch(audio, lengths, cfg: MfccConfig, mfcc_out=None, mo
     return get_plan(cfg).mfcc_modspec_ragged(audio, lengths, out=mfcc_out, out_mod=mod_out)
 
 
+def mfcc_modpsd_batch(audio, cfg: MfccConfig, **welch):
+    """[B, n] device tensor -> (MFCC [B, n_mfcc, T], f [bins] numpy, Pxx [B, n_mfcc, bins]): the MFCC and the Welch modulation
+    power spectrum of every coefficient trajectory (scipy.signal.welch at fs = sr / hop_length; the keywords of
+    modpsd.modulation_psd_batch).  See MfccPlan.mfcc_modpsd."""
+    return get_plan(cfg).mfcc_modpsd(audio, **welch)
+
+
+def mfcc_modpsd_ragged_batch(audio, lengths, cfg: MfccConfig, **welch):
+    """mfcc_modpsd_batch for a padded batch [B, n_max] + one length per clip: every clip's spectrum is that of the clip
+    alone, all on one frequency grid."""
+    return get_plan(cfg).mfcc_modpsd(audio, lengths, **welch)
+
+
 def mfcc_change_ragged_batch(audio, lengths, cfg: MfccConfig, *, tStep=None, **tail):
     """Padded batch [B, n_max] + one length per clip -> (change [B, T_max] float64, frames [B] int64 on the device): the
     amount-of-change curve of every clip as get_MFCCS_change computes it for that clip alone, in the columns

@@ -10,3 +10,4 @@
 #include "mm_interp.hip"
 #include "mm_longfilt.hip"
 #include "mm_ragged.hip"
+#include "mm_modpsd.hip"

@@ -359,6 +359,32 @@ class MfccPlan:
         batch; bit for bit modspec() of the ragged MFCC."""
         return self._ragged(audio, lengths, out, out_mod, True)
 
+    def mfcc_modpsd(self, audio, lengths=None, **welch):
+        """MFCC and the Welch modulation power spectrum of every coefficient's trajectory at the frame rate
+        fs = sr / hop_length -> (MFCC [B, n_mfcc, T], f [bins] numpy float64, Pxx [B, n_mfcc, bins] float32): mfcc() -- with
+        ``lengths`` mfcc_ragged(), each clip's own frame count -- followed by modpsd.modulation_psd_batch /
+        modulation_psd_ragged_batch on its rows, bit for bit; ``welch`` are their keywords (window, nperseg, noverlap, nfft,
+        detrend, scaling).  Every clip lands on the same frequency grid whatever its length.  A clip with fewer than nperseg
+        frames: ValueError (host lengths: the clip named), a NaN spectrum with device lengths."""
+        from . import modpsd
+        fs = self.cfg.sr / self.cfg.hop_length
+        n_mfcc = self.cfg.n_mfcc
+        if lengths is None:
+            mfcc = self.mfcc(audio)
+            f, pxx = modpsd.modulation_psd_batch(mfcc, fs, **welch)
+            return mfcc, f, pxx
+        audio = self._check_audio(audio)
+        B, n = audio.shape
+        lens = ragged.check_lengths(lengths, B, n, self.device)
+        nperseg = int(welch.get("nperseg", 256))
+        if isinstance(lens, np.ndarray):          # refused before any launch
+            ragged.refuse_short(ragged.stft_frames(lens, self.cfg.n_fft, self.cfg.hop_length), self.cfg.num_frames(n), nperseg,
+                                lambda short: modpsd.SHORT_TEXT.format(nperseg, short), "clip", "frames")
+        mfcc, frames = self.mfcc_ragged(audio, lens)
+        rows_frames = frames.unsqueeze(1).expand(B, n_mfcc).reshape(B * n_mfcc)       # every coefficient row has its clip's count
+        f, pxx = modpsd.modulation_psd_ragged_batch(mfcc.reshape(B * n_mfcc, mfcc.shape[2]), rows_frames, fs, **welch)
+        return mfcc, f, pxx.reshape(B, n_mfcc, pxx.shape[1])
+
     def logmel(self, audio):
         """Unclamped 10*log10(max(amin, mel)) [B, n_mels, T] and the per-clip max [B]."""
         torch = _torch()
