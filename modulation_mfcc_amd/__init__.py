@@ -10,6 +10,10 @@ from .batch import mfcc_ragged_batch, mfcc_modspec_ragged_batch, mfcc_change_rag
 from .batch import rms_ragged_batch, rms_ragged_frames  # noqa: F401
 from .batch import mfcc_modpsd_batch, mfcc_modpsd_ragged_batch  # noqa: F401
 from .modpsd import modulation_psd_batch, modulation_psd_ragged_batch, modpsd_nfft, modpsd_segments  # noqa: F401
+from .batch import mfcc_modcsd_batch, mfcc_modcsd_ragged_batch  # noqa: F401
+from .modcsd import modulation_cross_spectra_batch, modulation_csd_batch, modulation_coherence_batch  # noqa: F401
+from .modcsd import (modulation_cross_spectra_ragged_batch, modulation_csd_ragged_batch,  # noqa: F401
+                     modulation_coherence_ragged_batch)
 from .mfcc import get_MFCCS_change, get_MFCCS_change_batch, load_channel, applyFilter, get_amplitude  # noqa: F401
 from .mfcc import get_amplitude_batch  # noqa: F401
 from .calc import (get_velocity, calculate_amplitude_envelope, velocity_batch, amplitude_envelope_batch,  # noqa: F401

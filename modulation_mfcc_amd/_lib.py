@@ -1,4 +1,5 @@
-"""ctypes binding of libmodmfcc.so (include/modmfcc.h and, for the Welch modulation power spectrum, include/modmfcc_modpsd.h).
+"""ctypes binding of libmodmfcc.so (include/modmfcc.h and, for the Welch modulation power spectrum, include/modmfcc_modpsd.h;
+for the Welch cross spectrum and coherence, include/modmfcc_modcsd.h).
 
 There is NO CPU fallback: when the shared library cannot be loaded, or a plan cannot be created
 because no MI355X is visible, the calls raise.  Build the library with
@@ -241,6 +242,16 @@ PROTOTYPES_MODPSD = {
     "mm_modpsd_f32": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, C.c_size_t, _vp]),
 }
 
+# every symbol include/modmfcc_modcsd.h declares (the third header: the Welch cross spectrum and coherence, on the handle of
+# the second header; versioned by mm_modcsd_version)
+PROTOTYPES_MODCSD = {
+    "mm_modcsd_version": (C.c_int, []),
+    "mm_modcsd_check": (C.c_int, [_mpp]),
+    "mm_modcsd_workspace_bytes": (C.c_size_t, [_vp, _i64, _i64]),
+    "mm_modcsd_f32": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, C.c_size_t,
+                                _vp]),
+}
+
 _lib = None
 
 
@@ -262,7 +273,7 @@ def load():
             "`make -C modulation_mfcc_amd/csrc` (needs hipcc, --offload-arch=gfx950). "
             "modulation_mfcc_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for table in (PROTOTYPES, PROTOTYPES_MODPSD):
+    for table in (PROTOTYPES, PROTOTYPES_MODPSD, PROTOTYPES_MODCSD):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError when the .so is stale
             fn.restype = res

@@ -50,6 +50,21 @@ def mfcc_modpsd_ragged_batch(audio, lengths, cfg: MfccConfig, **welch):
     return get_plan(cfg).mfcc_modpsd(audio, lengths, **welch)
 
 
+def mfcc_modcsd_batch(audio, ref, cfg: MfccConfig, **welch):
+    """[B, n] device tensor and one reference curve per clip on the frame grid, ``ref`` [B, T] (e.g. rms_batch at the
+    configuration's hop) -> (MFCC [B, n_mfcc, T], f [bins] numpy, Pxx, Pyy, Pxy complex64, Cxy, each [B, n_mfcc, bins]): the
+    Welch auto spectra, cross spectrum and coherence of every coefficient trajectory against its clip's curve
+    (scipy.signal.welch / csd / coherence at fs = sr / hop_length; the keywords of
+    modcsd.modulation_cross_spectra_batch).  See MfccPlan.mfcc_modcsd."""
+    return get_plan(cfg).mfcc_modcsd(audio, ref, **welch)
+
+
+def mfcc_modcsd_ragged_batch(audio, ref, lengths, cfg: MfccConfig, **welch):
+    """mfcc_modcsd_batch for a padded batch [B, n_max] + one length per clip: every clip's spectra are those of the clip
+    alone, all on one frequency grid."""
+    return get_plan(cfg).mfcc_modcsd(audio, ref, lengths, **welch)
+
+
 def mfcc_change_ragged_batch(audio, lengths, cfg: MfccConfig, *, tStep=None, **tail):
     """Padded batch [B, n_max] + one length per clip -> (change [B, T_max] float64, frames [B] int64 on the device): the
     amount-of-change curve of every clip as get_MFCCS_change computes it for that clip alone, in the columns

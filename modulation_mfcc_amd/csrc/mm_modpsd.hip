@@ -17,19 +17,10 @@
 // or the other rows.  No atomics.  A row without a segment (shorter than nperseg) is NaN.
 #include "mm_common.h"
 #include "../../include/modmfcc_modpsd.h"
+#include "mm_welch.hip.inc"   // the handle, row length, segment count, wave sum, chunk count: shared with mm_modcsd.hip
 
-#define MPSD_WAVES 4
 #define MPSD_MIN_LOG2N 5
 #define MPSD_MAX_LOG2N 12
-
-struct mm_modpsd {
-  mm_modpsd_params p;
-  int device;
-  int log2n;
-  double scale;          // 1 / (fs sum w^2) or 1 / (sum w)^2
-  float* d_window;       // [nfft], zeros behind nperseg
-  float2* d_tw;          // [MM_TW_N] exp(-2 pi i k / MM_TW_N)
-};
 
 struct ModpsdArgs {
   const float* x;
@@ -43,26 +34,10 @@ struct ModpsdArgs {
   int nperseg, step, noverlap, detrend;
 };
 
-__device__ __forceinline__ int64_t mpsd_row_len(const int64_t* lens, int64_t row, int64_t n_max) {
-  if (!lens) return n_max;
-  const int64_t l = lens[row];
-  return l < 1 ? 1 : (l > n_max ? n_max : l);
-}
-
-__device__ __forceinline__ int64_t mpsd_segments(int64_t len, int nperseg, int noverlap, int step) {
-  return len < nperseg ? 0 : (len - noverlap) / step;
-}
-
 // P[k] of a row from the float64 sum over its K segments
 __device__ __forceinline__ float mpsd_value(double sum, int k, int nc, double scale, int64_t K) {
   const double d = (k == 0 || k == nc) ? 1.0 : 2.0;
   return (float)(sum * (scale * d / (double)K));
-}
-
-__device__ __forceinline__ double mpsd_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 template <int LOG2N>
@@ -214,15 +189,6 @@ static ModpsdKernel mpsd_kernel_of(int log2n) {
     case 12: return modpsd_kernel<12>;
   }
   return nullptr;
-}
-
-static int64_t mpsd_host_segments(const mm_modpsd_params& p, int64_t n) {
-  return n < p.nperseg ? 0 : (n - p.noverlap) / (p.nperseg - p.noverlap);
-}
-
-static int64_t mpsd_max_chunks(const mm_modpsd* h, int64_t n_max) {
-  const int64_t K = mpsd_host_segments(h->p, n_max);
-  return K < 1 ? 1 : (K + MM_MODPSD_CHUNK - 1) / MM_MODPSD_CHUNK;
 }
 
 extern "C" {

@@ -11,3 +11,4 @@
 #include "mm_longfilt.hip"
 #include "mm_ragged.hip"
 #include "mm_modpsd.hip"
+#include "mm_modcsd.hip"

@@ -385,6 +385,35 @@ class MfccPlan:
         f, pxx = modpsd.modulation_psd_ragged_batch(mfcc.reshape(B * n_mfcc, mfcc.shape[2]), rows_frames, fs, **welch)
         return mfcc, f, pxx.reshape(B, n_mfcc, pxx.shape[1])
 
+    def mfcc_modcsd(self, audio, ref, lengths=None, **welch):
+        """MFCC and the Welch cross spectra of every coefficient's trajectory against one reference curve per clip on the
+        plan's frame grid, ``ref`` [B, T] float32 on the device (e.g. rms_batch at the plan's hop), at fs = sr / hop_length
+        -> (MFCC [B, n_mfcc, T], f [bins] numpy float64, Pxx, Pyy, Pxy complex64, Cxy, each [B, n_mfcc, bins]): mfcc() -- with
+        ``lengths`` mfcc_ragged(), each clip's own frame count -- followed by modcsd.modulation_cross_spectra_batch /
+        ..._ragged_batch with x the MFCC rows and y = ref shared by the n_mfcc rows of its clip (y_group = n_mfcc, no
+        copy), bit for bit; ``welch`` are their keywords.  A clip with fewer than nperseg frames: ValueError (host lengths:
+        the clip named), NaN spectra with device lengths."""
+        from . import modcsd, modpsd
+        fs = self.cfg.sr / self.cfg.hop_length
+        n_mfcc = self.cfg.n_mfcc
+        audio = self._check_audio(audio)
+        B, n = audio.shape
+        T = self.cfg.num_frames(n)
+        if not ragged.is_device_tensor(ref) or ref.dim() != 2 or tuple(ref.shape) != (B, T):
+            raise ValueError(f"ref must be a device tensor [{B}, {T}]: one curve per clip on the plan's frame grid")
+        if lengths is None:
+            mfcc = self.mfcc(audio)
+            return (mfcc,) + modcsd.modulation_cross_spectra_batch(mfcc, ref, fs, **welch)
+        lens = ragged.check_lengths(lengths, B, n, self.device)
+        nperseg = int(welch.get("nperseg", 256))
+        if isinstance(lens, np.ndarray):          # refused before any launch
+            ragged.refuse_short(ragged.stft_frames(lens, self.cfg.n_fft, self.cfg.hop_length), T, nperseg,
+                                lambda short: modpsd.SHORT_TEXT.format(nperseg, short), "clip", "frames")
+        mfcc, frames = self.mfcc_ragged(audio, lens)
+        rows_frames = frames.unsqueeze(1).expand(B, n_mfcc).reshape(B * n_mfcc)       # every coefficient row has its clip's count
+        f, *spectra = modcsd.modulation_cross_spectra_ragged_batch(mfcc.reshape(B * n_mfcc, T), ref, rows_frames, fs, **welch)
+        return (mfcc, f) + tuple(s.reshape(B, n_mfcc, s.shape[1]) for s in spectra)
+
     def logmel(self, audio):
         """Unclamped 10*log10(max(amin, mel)) [B, n_mels, T] and the per-clip max [B]."""
         torch = _torch()
