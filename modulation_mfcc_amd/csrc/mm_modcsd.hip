@@ -20,7 +20,8 @@
 // Which wave adds which segment in which order is a function of the segment's index alone, the chunk sums are added in
 // ascending order whichever kernel does it, and the two kernels finish a bin with the same function (explicit fma: no
 // contraction the compiler could choose differently in either): a pair's bits do not depend on rows, n_max, y_group or
-// the other pairs.  No atomics.  A pair without a segment is NaN.
+// the other pairs.  No atomics.  A pair without a segment is NaN.  The plan, the trend, the hand-off, the chunk sum, the
+// shared refusals and the launch are mm_welch.hip.inc's: the code modpsd_kernel and mm_modpsd_f32 run.
 #include "mm_common.h"
 #include "../../include/modmfcc_modcsd.h"
 #include "mm_welch.hip.inc"
@@ -29,26 +30,21 @@
 #define MCSD_MAX_LOG2N 11       // 17 bins x 4 float64 sums = 136 VGPRs per lane; nfft 4096 would need 264
 
 struct ModcsdArgs {
+  WelchArgs w;           // part: [rows][max_chunks][4][bins]
   const float* x;
   const float* y;
-  const int64_t* lens;
-  const float* window;
-  const float2* tw;
   float* pxx;            // any of the four may be nullptr
   float* pyy;
   float* pxy;            // [rows][out_stride][2]
   float* coh;
-  double* part;          // [rows][max_chunks][4][bins] chunk sums, or nullptr: one chunk per pair, finished directly
-  int64_t n_max, x_stride, y_stride, y_group, out_stride, max_chunks;
-  double scale;
-  int nperseg, step, noverlap, detrend;
+  int64_t x_stride, y_stride, y_group, out_stride;
 };
 
 // bin k of a pair from its float64 sums over the K segments: sxx = sum |X|^2, syy = sum |Y|^2, (sre, sim) = sum conj(X) Y
 __device__ __forceinline__ void mcsd_finish_bin(const ModcsdArgs& p, int64_t row, int k, int nh, double sxx, double syy,
                                                 double sre, double sim, int64_t K) {
   const double d = (k == 0 || k == nh) ? 1.0 : 2.0;
-  const double f = p.scale * d / (double)K;
+  const double f = p.w.scale * d / (double)K;
   const int64_t o = row * p.out_stride + k;
   if (p.pxx) p.pxx[o] = (float)(sxx * f);
   if (p.pyy) p.pyy[o] = (float)(syy * f);
@@ -108,22 +104,14 @@ __global__ __launch_bounds__(64 * MPSD_WAVES) void modcsd_kernel(ModcsdArgs p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float2* z = reinterpret_cast<float2*>(smem) + (size_t)wave * N;
 
-  const int64_t row = blockIdx.x / p.max_chunks, chunk = blockIdx.x % p.max_chunks;
-  const int64_t len = mpsd_row_len(p.lens, row, p.n_max);
-  const int64_t K = mpsd_segments(len, p.nperseg, p.noverlap, p.step);
-  const int64_t seg0 = chunk * MM_MODPSD_CHUNK;
-  if (K == 0) {                                        // (workgroup-uniform)
-    if (!p.part && chunk == 0)
-      for (int k = threadIdx.x; k <= NH; k += 64 * MPSD_WAVES) mcsd_nan_bin(p, row, k);
-    return;
-  }
-  if (seg0 >= K) return;                               // (workgroup-uniform)
-  const int n_seg = (int)(K - seg0 < MM_MODPSD_CHUNK ? K - seg0 : MM_MODPSD_CHUNK);
-  const float* ax = p.x + row * p.x_stride;
-  const float* ay = p.y + (row / p.y_group) * p.y_stride;
-  const double centre = 0.5 * (double)(p.nperseg - 1);
-  // sum (j - centre)^2 = n (n^2 - 1) / 12
-  const double sxx = (double)p.nperseg * ((double)p.nperseg * (double)p.nperseg - 1.0) / 12.0;
+  const WelchArgs& w = p.w;
+  const WelchPlan g = welch_plan(w, blockIdx.x);
+  if (g.state == WELCH_NAN && !w.part && g.chunk == 0)
+    for (int k = threadIdx.x; k <= NH; k += 64 * MPSD_WAVES) mcsd_nan_bin(p, g.row, k);
+  if (g.state != WELCH_WORK) return;                   // (workgroup-uniform)
+  const float* ax = p.x + g.row * p.x_stride;
+  const float* ay = p.y + (g.row / p.y_group) * p.y_stride;
+  const WelchDetrend d = welch_detrend(w.nperseg);
 
   double acc[4][NB];                                   // |X|^2, |Y|^2, Re conj(X) Y, Im conj(X) Y
 #pragma unroll
@@ -131,31 +119,29 @@ __global__ __launch_bounds__(64 * MPSD_WAVES) void modcsd_kernel(ModcsdArgs p) {
 #pragma unroll
     for (int i = 0; i < NB; ++i) acc[q][i] = 0.0;
 
-  for (int s = wave; s < n_seg; s += MPSD_WAVES) {     // (wave-uniform)
-    const float* xs = ax + (seg0 + s) * (int64_t)p.step;   // samples xs[0 .. nperseg), ys[0 .. nperseg): all below len
-    const float* ys = ay + (seg0 + s) * (int64_t)p.step;
+  for (int s = wave; s < g.n_seg; s += MPSD_WAVES) {   // (wave-uniform)
+    const float* xs = ax + (g.seg0 + s) * (int64_t)w.step; // samples xs[0 .. nperseg), ys[0 .. nperseg): all below len
+    const float* ys = ay + (g.seg0 + s) * (int64_t)w.step;
     // as in modpsd_kernel the segment is read once for the detrend statistics and once more (from the cache) to be
     // transformed
-    double mx = 0.0, my = 0.0, slx = 0.0, sly = 0.0;
-    if (p.detrend) {
+    WelchTrend tx = {0.0, 0.0}, ty = {0.0, 0.0};
+    if (w.detrend) {
       double s0x = 0.0, s1x = 0.0, s0y = 0.0, s1y = 0.0;
 #pragma unroll 4
       for (int i = 0; i < NP; ++i) {
         const int j = lane + 64 * i;
-        const double x0 = j < p.nperseg ? (double)xs[j] : 0.0, y0 = j < p.nperseg ? (double)ys[j] : 0.0;
+        const double x0 = j < w.nperseg ? (double)xs[j] : 0.0, y0 = j < w.nperseg ? (double)ys[j] : 0.0;
         s0x += x0;
         s0y += y0;
-        if (p.detrend == 2) {
-          s1x += ((double)j - centre) * x0;
-          s1y += ((double)j - centre) * y0;
+        if (w.detrend == 2) {
+          s1x += ((double)j - d.centre) * x0;
+          s1y += ((double)j - d.centre) * y0;
         }
       }
-      mx = mpsd_wave_sum(s0x) / (double)p.nperseg;
-      my = mpsd_wave_sum(s0y) / (double)p.nperseg;
-      if (p.detrend == 2 && p.nperseg > 1) {
-        slx = mpsd_wave_sum(s1x) / sxx;
-        sly = mpsd_wave_sum(s1y) / sxx;
-      }
+      tx.mean = welch_mean(s0x, w);
+      ty.mean = welch_mean(s0y, w);
+      tx.slope = welch_slope(s1x, w, d);
+      ty.slope = welch_slope(s1y, w, d);
     }
     double ssx = 0.0, ssy = 0.0;                       // the energy either side puts into the transform
 #pragma unroll 4
@@ -163,17 +149,16 @@ __global__ __launch_bounds__(64 * MPSD_WAVES) void modcsd_kernel(ModcsdArgs p) {
       const int j = lane + 64 * i;
       if (j < N) {
         float x0 = 0.0f, y0 = 0.0f;
-        if (j < p.nperseg) {
+        if (j < w.nperseg) {
           x0 = xs[j];
           y0 = ys[j];
-          if (p.detrend) {
-            const double tj = (double)j - centre;
-            x0 = (float)((double)x0 - (mx + slx * tj));
-            y0 = (float)((double)y0 - (my + sly * tj));
+          if (w.detrend) {
+            x0 = welch_subtract(x0, j, tx, d);
+            y0 = welch_subtract(y0, j, ty, d);
           }
         }
-        const float w = p.window[j];
-        const float vx = x0 * w, vy = y0 * w;
+        const float wj = w.window[j];
+        const float vx = x0 * wj, vy = y0 * wj;
         ssx = fma((double)vx, (double)vx, ssx);
         ssy = fma((double)vy, (double)vy, ssy);
         z[__brev((unsigned)j) >> (32 - LOG2N)] = make_float2(vx, vy);
@@ -201,7 +186,7 @@ __global__ __launch_bounds__(64 * MPSD_WAVES) void modcsd_kernel(ModcsdArgs p) {
     // conj Z[N - k] of a real row differ in their last bits) must not become a power of the zero row.  (NaN != 0.)
     const double ux = ssx == 0.0 ? 0.0 : ldexp(1.0, hx), uy = ssy == 0.0 ? 0.0 : ldexp(1.0, hy);
     wave_lds_sync();
-    mcsd_cfft_lds(z, LOG2N, p.tw, lane);
+    mcsd_cfft_lds(z, LOG2N, w.tw, lane);
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
       const int k = lane + 64 * i;
@@ -218,73 +203,42 @@ __global__ __launch_bounds__(64 * MPSD_WAVES) void modcsd_kernel(ModcsdArgs p) {
     wave_lds_sync();
   }
 
-  // (w0 + w1) + (w2 + w3) through LDS, one accumulator kind at a time: the odd waves hand theirs to the even ones, then
-  // wave 2 to wave 0.  The two slots of NH + 1 float64 lie over the transform buffers of other waves: a barrier in front
-  // of each hand-off.
-  double* ex = reinterpret_cast<double*>(smem);
+  // every (bin, accumulator of kind q) of this lane
+  auto kind = [&](int q, auto f) {
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-#pragma unroll
-    for (int round = 0; round < 2; ++round) {
-      const bool gives = round == 0 ? (wave & 1) : wave == 2;
-      const bool takes = round == 0 ? !(wave & 1) : wave == 0;
-      double* slot = ex + (size_t)(round == 0 ? (wave >> 1) : 0) * (NH + 1);
-      __syncthreads();
-      if (gives) {
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {
-          const int k = lane + 64 * i;
-          if (k <= NH) slot[k] = acc[q][i];
-        }
-      }
-      __syncthreads();
-      if (takes) {
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {
-          const int k = lane + 64 * i;
-          if (k <= NH) acc[q][i] += slot[k];
-        }
-      }
+    for (int i = 0; i < NB; ++i) {
+      const int k = lane + 64 * i;
+      if (k <= NH) f(k, acc[q][i]);
     }
-  }
+  };
+  // the four waves' sums meet one kind at a time: two slots of NH + 1 float64 are all that lies over the transform buffers
+#pragma unroll
+  for (int q = 0; q < 4; ++q) welch_handoff(reinterpret_cast<double*>(smem), NH + 1, wave, [&](auto f) { kind(q, f); });
   if (wave != 0) return;
-  if (p.part) {
-    double* o = p.part + (row * p.max_chunks + chunk) * (int64_t)(4 * (NH + 1));
+  if (w.part) {
+    double* o = w.part + (g.row * w.max_chunks + g.chunk) * (int64_t)(4 * (NH + 1));
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int i = 0; i < NB; ++i) {
-        const int k = lane + 64 * i;
-        if (k <= NH) o[q * (NH + 1) + k] = acc[q][i];
-      }
+    for (int q = 0; q < 4; ++q) kind(q, [&](int k, double& sum) { o[q * (NH + 1) + k] = sum; });
   } else {
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
       const int k = lane + 64 * i;
-      if (k <= NH) mcsd_finish_bin(p, row, k, NH, acc[0][i], acc[1][i], acc[2][i], acc[3][i], K);
+      if (k <= NH) mcsd_finish_bin(p, g.row, k, NH, acc[0][i], acc[1][i], acc[2][i], acc[3][i], g.K);
     }
   }
 }
 
 // ceil(bins / 256) workgroups per pair: a thread per bin adds the pair's chunk sums in ascending order
 static __global__ __launch_bounds__(256) void modcsd_finish_kernel(ModcsdArgs p, int nh) {
-  const int per_row = (nh + 1 + 255) / 256;
-  const int k = (int)(blockIdx.x % per_row) * 256 + threadIdx.x;
-  if (k > nh) return;
-  const int64_t row = blockIdx.x / per_row;
-  const int64_t K = mpsd_segments(mpsd_row_len(p.lens, row, p.n_max), p.nperseg, p.noverlap, p.step);
-  if (K == 0) { mcsd_nan_bin(p, row, k); return; }
-  const int64_t chunks = (K + MM_MODPSD_CHUNK - 1) / MM_MODPSD_CHUNK;
+  const WelchFinish f = welch_finish_plan(p.w, nh);
+  if (f.state == WELCH_IDLE) return;
+  if (f.state == WELCH_NAN) { mcsd_nan_bin(p, f.row, f.k); return; }
   const int64_t bins = nh + 1;
-  const double* q = p.part + row * p.max_chunks * (4 * bins) + k;
+  const double* q = p.w.part + f.row * p.w.max_chunks * (4 * bins) + f.k;
   double s[4];
 #pragma unroll
-  for (int a = 0; a < 4; ++a) s[a] = q[a * bins];
-  for (int64_t c = 1; c < chunks; ++c) {
-#pragma unroll
-    for (int a = 0; a < 4; ++a) s[a] += q[c * (4 * bins) + a * bins];
-  }
-  mcsd_finish_bin(p, row, k, nh, s[0], s[1], s[2], s[3], K);
+  for (int a = 0; a < 4; ++a) s[a] = welch_chunk_sum(q + a * bins, f.chunks, 4 * bins);
+  mcsd_finish_bin(p, f.row, f.k, nh, s[0], s[1], s[2], s[3], f.K);
 }
 
 using ModcsdKernel = void (*)(ModcsdArgs);
@@ -313,10 +267,7 @@ int mm_modcsd_check(const mm_modpsd_params* p) {
 }
 
 size_t mm_modcsd_workspace_bytes(const mm_modpsd* h, int64_t rows, int64_t n_max) {
-  if (!h || rows < 1 || n_max < 1 || mm_modcsd_check(&h->p) != MM_OK) return 0;
-  const int64_t chunks = mpsd_max_chunks(h, n_max);
-  if (chunks <= 1) return 0;
-  return (size_t)rows * (size_t)chunks * 4 * (size_t)(h->p.nfft / 2 + 1) * sizeof(double);
+  return h && mm_modcsd_check(&h->p) == MM_OK ? welch_workspace_bytes(h, rows, n_max, 4) : 0;
 }
 
 int mm_modcsd_f32(const mm_modpsd* h, const float* d_x, int64_t rows, int64_t n_max, int64_t x_stride, const float* d_y,
@@ -329,30 +280,14 @@ int mm_modcsd_f32(const mm_modpsd* h, const float* d_x, int64_t rows, int64_t n_
   if (rc != MM_OK) return rc;
   const int nh = h->p.nfft / 2;
   if (out_stride < nh + 1) return MM_ERR_INVALID_ARG;
-  if (!d_lens && n_max < h->p.nperseg) return MM_ERR_INVALID_ARG;
-  const int64_t chunks = mpsd_max_chunks(h, n_max);
-  const size_t need = mm_modcsd_workspace_bytes(h, rows, n_max);
-  if (need && (!d_ws || ((uintptr_t)d_ws & 7))) return MM_ERR_INVALID_ARG;
-  if (ws_bytes < need) return MM_ERR_WORKSPACE;
-  const int64_t finish_per_row = (nh + 1 + 255) / 256;
-  if (rows > 0x7FFFFFFF / chunks || rows > 0x7FFFFFFF / finish_per_row) return MM_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  ModcsdArgs a;
-  a.x = d_x; a.y = d_y; a.lens = d_lens; a.window = h->d_window; a.tw = h->d_tw;
-  a.pxx = d_pxx; a.pyy = d_pyy; a.pxy = d_pxy; a.coh = d_coh;
-  a.part = chunks > 1 ? (double*)d_ws : nullptr;
-  a.n_max = n_max; a.x_stride = x_stride; a.y_stride = y_stride; a.y_group = y_group; a.out_stride = out_stride;
-  a.max_chunks = chunks;
-  a.scale = h->scale;
-  a.nperseg = h->p.nperseg; a.step = h->p.nperseg - h->p.noverlap; a.noverlap = h->p.noverlap; a.detrend = h->p.detrend;
+  const WelchLaunch l = welch_launch_plan(h, rows, n_max, nh + 1, 4, d_lens, d_ws, ws_bytes);
+  if (l.rc != MM_OK) return l.rc;
+  const ModcsdArgs a = {welch_args(h, d_lens, n_max, l.chunks, d_ws), d_x, d_y, d_pxx, d_pyy, d_pxy, d_coh,
+                        x_stride, y_stride, y_group, out_stride};
   // LDS: the four transform buffers, 8 nfft bytes each (64 KiB at nfft 2048); the two hand-off slots of nfft / 2 + 1
   // float64 lie over them
   const size_t lds = (size_t)MPSD_WAVES * h->p.nfft * sizeof(float2);
-  hipLaunchKernelGGL(mcsd_kernel_of(h->log2n), dim3((unsigned)(rows * chunks)), dim3(64 * MPSD_WAVES), lds, st, a);
-  if (chunks > 1)
-    hipLaunchKernelGGL(modcsd_finish_kernel, dim3((unsigned)(rows * finish_per_row)), dim3(256), 0, st, a, nh);
-  HIP_TRY(hipGetLastError());
-  return MM_OK;
+  return welch_launch(mcsd_kernel_of(h->log2n), modcsd_finish_kernel, a, l, rows, nh + 1, lds, stream);
 }
 
 }  // extern "C"

@@ -4,34 +4,30 @@
 //                          belongs to chunk i / 32 and, inside it, to wave i % 4, which takes its segments in ascending
 //                          order.  A wave reads its segment for the detrend statistics (float64 sums over the wave) and again,
 //                          from the cache, to subtract the trend in float64, writes the windowed values bit-reversed into
-//                          its LDS buffer,
-//                          transforms them there (the packed real transform of rfft_generic_kernel: wave_cfft_lds +
-//                          real_split of mm_common.h) and adds |X[k]|^2 to float64 accumulators its lanes hold for their
-//                          bins.  The four waves' sums meet through LDS as (w0 + w1) + (w2 + w3).  A batch whose rows
-//                          have one chunk each ends here: scale, round, store.  Otherwise every chunk stores its float64
-//                          sums to the workspace and
+//                          its LDS buffer, transforms them there (the packed real transform of rfft_generic_kernel:
+//                          wave_cfft_lds + real_split of mm_common.h) and adds |X[k]|^2 to float64 accumulators its lanes
+//                          hold for their bins.  The four waves' sums meet through LDS as (w0 + w1) + (w2 + w3).  A batch
+//                          whose rows have one chunk each ends here: scale, round, store.  Otherwise every chunk stores
+//                          its float64 sums to the workspace and
 //   modpsd_finish_kernel   adds a row's chunks in ascending order, scales, rounds and stores.
 //
 // Which wave adds which segment in which order is a function of the segment's index alone, and the chunk sums are added in
 // ascending order whichever kernel does it (one chunk: the sum is that chunk's): a row's bits do not depend on rows, n_max
-// or the other rows.  No atomics.  A row without a segment (shorter than nperseg) is NaN.
+// or the other rows.  No atomics.  A row without a segment (shorter than nperseg) is NaN.  That plan (welch_plan), the
+// trend, the hand-off (welch_handoff) and the chunk sum are mm_welch.hip.inc's, one copy for this unit and mm_modcsd.hip;
+// the order in which a lane adds up its samples and squares its bins is this kernel's own.
 #include "mm_common.h"
 #include "../../include/modmfcc_modpsd.h"
-#include "mm_welch.hip.inc"   // the handle, row length, segment count, wave sum, chunk count: shared with mm_modcsd.hip
+#include "mm_welch.hip.inc"   // shared with mm_modcsd.hip: handle, workgroup plan, detrend, hand-off, chunk sum, launch
 
 #define MPSD_MIN_LOG2N 5
 #define MPSD_MAX_LOG2N 12
 
 struct ModpsdArgs {
+  WelchArgs w;           // part: [rows][max_chunks][bins]
   const float* x;
-  const int64_t* lens;
-  const float* window;
-  const float2* tw;
   float* psd;
-  double* part;          // [rows][max_chunks][bins] chunk sums, or nullptr: one chunk per row, stored directly
-  int64_t n_max, x_stride, psd_stride, max_chunks;
-  double scale;
-  int nperseg, step, noverlap, detrend;
+  int64_t x_stride, psd_stride;
 };
 
 // P[k] of a row from the float64 sum over its K segments
@@ -50,65 +46,56 @@ __global__ __launch_bounds__(64 * MPSD_WAVES) void modpsd_kernel(ModpsdArgs p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float2* z = reinterpret_cast<float2*>(smem) + (size_t)wave * NC;
 
-  const int64_t row = blockIdx.x / p.max_chunks, chunk = blockIdx.x % p.max_chunks;
-  const int64_t len = mpsd_row_len(p.lens, row, p.n_max);
-  const int64_t K = mpsd_segments(len, p.nperseg, p.noverlap, p.step);
-  const int64_t seg0 = chunk * MM_MODPSD_CHUNK;
-  float* out = p.psd + row * p.psd_stride;
-  if (K == 0) {                                        // (workgroup-uniform)
-    if (!p.part && chunk == 0)
-      for (int k = threadIdx.x; k <= NC; k += 64 * MPSD_WAVES) out[k] = __builtin_nanf("");
-    return;
-  }
-  if (seg0 >= K) return;                               // (workgroup-uniform)
-  const int n_seg = (int)(K - seg0 < MM_MODPSD_CHUNK ? K - seg0 : MM_MODPSD_CHUNK);
-  const float* a = p.x + row * p.x_stride;
+  const WelchArgs& w = p.w;
+  const WelchPlan g = welch_plan(w, blockIdx.x);
+  float* out = p.psd + g.row * p.psd_stride;
+  if (g.state == WELCH_NAN && !w.part && g.chunk == 0)
+    for (int k = threadIdx.x; k <= NC; k += 64 * MPSD_WAVES) out[k] = __builtin_nanf("");
+  if (g.state != WELCH_WORK) return;                   // (workgroup-uniform)
+  const float* a = p.x + g.row * p.x_stride;
   const int tw_stride = MM_TW_N >> LOG2N;
-  const double centre = 0.5 * (double)(p.nperseg - 1);
-  // sum (j - centre)^2 = n (n^2 - 1) / 12
-  const double sxx = (double)p.nperseg * ((double)p.nperseg * (double)p.nperseg - 1.0) / 12.0;
+  const WelchDetrend d = welch_detrend(w.nperseg);
 
   double accA[NA], accB[NA];
 #pragma unroll
   for (int i = 0; i < NA; ++i) accA[i] = accB[i] = 0.0;
 
-  for (int s = wave; s < n_seg; s += MPSD_WAVES) {     // (wave-uniform)
-    const float* as = a + (seg0 + s) * (int64_t)p.step;  // samples as[0 .. nperseg): all below len
+  for (int s = wave; s < g.n_seg; s += MPSD_WAVES) {   // (wave-uniform)
+    const float* as = a + (g.seg0 + s) * (int64_t)w.step;  // samples as[0 .. nperseg): all below len
     // the segment is read once for the detrend statistics and once more (from the cache) to be transformed: held in
     // registers between the two, the 64 samples per lane of nfft 4096 would spill beside the accumulators
-    double mean = 0.0, slope = 0.0;
-    if (p.detrend) {
+    WelchTrend t = {0.0, 0.0};
+    if (w.detrend) {
       double s0 = 0.0, s1 = 0.0;
 #pragma unroll 4
       for (int i = 0; i < NP; ++i) {
         const int j = 2 * (lane + 64 * i);
-        const double x0 = j < p.nperseg ? (double)as[j] : 0.0, x1 = j + 1 < p.nperseg ? (double)as[j + 1] : 0.0;
+        const double x0 = j < w.nperseg ? (double)as[j] : 0.0, x1 = j + 1 < w.nperseg ? (double)as[j + 1] : 0.0;
         s0 += x0 + x1;
-        if (p.detrend == 2) s1 += ((double)j - centre) * x0 + ((double)(j + 1) - centre) * x1;
+        if (w.detrend == 2) s1 += ((double)j - d.centre) * x0 + ((double)(j + 1) - d.centre) * x1;
       }
-      mean = mpsd_wave_sum(s0) / (double)p.nperseg;
-      if (p.detrend == 2 && p.nperseg > 1) slope = mpsd_wave_sum(s1) / sxx;
+      t = {welch_mean(s0, w), welch_slope(s1, w, d)};
     }
 #pragma unroll 4
     for (int i = 0; i < NP; ++i) {
       const int n = lane + 64 * i, j = 2 * n;
       if (n < NC) {
-        float y0 = j < p.nperseg ? as[j] : 0.0f, y1 = j + 1 < p.nperseg ? as[j + 1] : 0.0f;
-        if (p.detrend) {
-          y0 = j < p.nperseg ? (float)((double)y0 - (mean + slope * ((double)j - centre))) : 0.0f;
-          y1 = j + 1 < p.nperseg ? (float)((double)y1 - (mean + slope * ((double)(j + 1) - centre))) : 0.0f;
+        float y0 = j < w.nperseg ? as[j] : 0.0f, y1 = j + 1 < w.nperseg ? as[j + 1] : 0.0f;
+        if (w.detrend) {
+          y0 = j < w.nperseg ? welch_subtract(y0, j, t, d) : 0.0f;
+          y1 = j + 1 < w.nperseg ? welch_subtract(y1, j + 1, t, d) : 0.0f;
         }
-        z[__brev((unsigned)n) >> (32 - LOG2NC)] = make_float2(y0 * p.window[j], y1 * p.window[j + 1]);
+        z[__brev((unsigned)n) >> (32 - LOG2NC)] = make_float2(y0 * w.window[j], y1 * w.window[j + 1]);
       }
     }
     wave_lds_sync();
-    wave_cfft_lds(z, LOG2NC, p.tw, lane);
+    wave_cfft_lds(z, LOG2NC, w.tw, lane);
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
       const int k = lane + 64 * i;
       if (k <= NC / 2) {
         float2 xa, xb;
-        real_split(z, k, NC, p.tw, tw_stride, xa, xb);
+        real_split(z, k, NC, w.tw, tw_stride, xa, xb);
         accA[i] += (double)(xa.x * xa.x + xa.y * xa.y);
         accB[i] += (double)(xb.x * xb.x + xb.y * xb.y);
       }
@@ -116,64 +103,32 @@ __global__ __launch_bounds__(64 * MPSD_WAVES) void modpsd_kernel(ModpsdArgs p) {
     wave_lds_sync();
   }
 
-  // (w0 + w1) + (w2 + w3) through LDS: the odd waves hand theirs to the even ones, then wave 2 to wave 0.  The buffers
-  // lie over the transform buffers of other waves: a barrier in front of each hand-off.
-  double* ex = reinterpret_cast<double*>(smem);
-  for (int round = 0; round < 2; ++round) {
-    const bool gives = round == 0 ? (wave & 1) : wave == 2;
-    const bool takes = round == 0 ? !(wave & 1) : wave == 0;
-    double* slot = ex + (size_t)(round == 0 ? (wave >> 1) : 0) * (NC + 1);
-    __syncthreads();
-    if (gives) {
+  // every (bin, accumulator) of this lane, in the order of the stores: k = NC - k = NC / 2 ends as accB's
+  auto bins = [&](auto f) {
 #pragma unroll
-      for (int i = 0; i < NA; ++i) {
-        const int k = lane + 64 * i;
-        if (k <= NC / 2) { slot[k] = accA[i]; slot[NC - k] = accB[i]; }
-      }
+    for (int i = 0; i < NA; ++i) {
+      const int k = lane + 64 * i;
+      if (k <= NC / 2) { f(k, accA[i]); f(NC - k, accB[i]); }
     }
-    __syncthreads();
-    if (takes) {
-#pragma unroll
-      for (int i = 0; i < NA; ++i) {
-        const int k = lane + 64 * i;
-        if (k <= NC / 2) { accA[i] += slot[k]; accB[i] += slot[NC - k]; }
-      }
-    }
-  }
+  };
+  welch_handoff(reinterpret_cast<double*>(smem), NC + 1, wave, bins);
   if (wave != 0) return;
-  if (p.part) {
-    double* o = p.part + (row * p.max_chunks + chunk) * (int64_t)(NC + 1);
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      const int k = lane + 64 * i;
-      if (k <= NC / 2) { o[k] = accA[i]; o[NC - k] = accB[i]; }
-    }
+  if (w.part) {
+    double* o = w.part + (g.row * w.max_chunks + g.chunk) * (int64_t)(NC + 1);
+    bins([o](int k, double& sum) { o[k] = sum; });
   } else {
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      const int k = lane + 64 * i;
-      if (k <= NC / 2) {
-        out[k] = mpsd_value(accA[i], k, NC, p.scale, K);
-        out[NC - k] = mpsd_value(accB[i], NC - k, NC, p.scale, K);
-      }
-    }
+    bins([&](int k, double& sum) { out[k] = mpsd_value(sum, k, NC, w.scale, g.K); });
   }
 }
 
 // ceil(bins / 256) workgroups per row: a thread per bin adds the row's chunk sums in ascending order
 static __global__ __launch_bounds__(256) void modpsd_finish_kernel(ModpsdArgs p, int nc) {
-  const int per_row = (nc + 1 + 255) / 256;
-  const int k = (int)(blockIdx.x % per_row) * 256 + threadIdx.x;
-  if (k > nc) return;
-  const int64_t row = blockIdx.x / per_row;
-  const int64_t K = mpsd_segments(mpsd_row_len(p.lens, row, p.n_max), p.nperseg, p.noverlap, p.step);
-  float* out = p.psd + row * p.psd_stride;
-  if (K == 0) { out[k] = __builtin_nanf(""); return; }
-  const int64_t chunks = (K + MM_MODPSD_CHUNK - 1) / MM_MODPSD_CHUNK;
-  const double* q = p.part + row * p.max_chunks * (int64_t)(nc + 1) + k;
-  double sum = q[0];
-  for (int64_t c = 1; c < chunks; ++c) sum += q[c * (int64_t)(nc + 1)];
-  out[k] = mpsd_value(sum, k, nc, p.scale, K);
+  const WelchFinish f = welch_finish_plan(p.w, nc);
+  if (f.state == WELCH_IDLE) return;
+  float* out = p.psd + f.row * p.psd_stride;
+  if (f.state == WELCH_NAN) { out[f.k] = __builtin_nanf(""); return; }
+  const double* q = p.w.part + f.row * p.w.max_chunks * (int64_t)(nc + 1) + f.k;
+  out[f.k] = mpsd_value(welch_chunk_sum(q, f.chunks, nc + 1), f.k, nc, p.w.scale, f.K);
 }
 
 using ModpsdKernel = void (*)(ModpsdArgs);
@@ -255,10 +210,7 @@ int mm_modpsd_create(const mm_modpsd_params* p, const float* window_host, mm_mod
 }
 
 size_t mm_modpsd_workspace_bytes(const mm_modpsd* h, int64_t rows, int64_t n_max) {
-  if (!h || rows < 1 || n_max < 1) return 0;
-  const int64_t chunks = mpsd_max_chunks(h, n_max);
-  if (chunks <= 1) return 0;
-  return (size_t)rows * (size_t)chunks * (size_t)(h->p.nfft / 2 + 1) * sizeof(double);
+  return welch_workspace_bytes(h, rows, n_max, 1);
 }
 
 int mm_modpsd_f32(const mm_modpsd* h, const float* d_x, int64_t rows, int64_t n_max, int64_t x_stride, const int64_t* d_lens,
@@ -266,28 +218,13 @@ int mm_modpsd_f32(const mm_modpsd* h, const float* d_x, int64_t rows, int64_t n_
   if (!h || !d_x || !d_psd || rows < 1 || n_max < 1 || x_stride < n_max) return MM_ERR_INVALID_ARG;
   const int nc = h->p.nfft / 2;
   if (psd_stride < nc + 1) return MM_ERR_INVALID_ARG;
-  if (!d_lens && n_max < h->p.nperseg) return MM_ERR_INVALID_ARG;
-  const int64_t chunks = mpsd_max_chunks(h, n_max);
-  const size_t need = mm_modpsd_workspace_bytes(h, rows, n_max);
-  if (need && (!d_ws || ((uintptr_t)d_ws & 7))) return MM_ERR_INVALID_ARG;
-  if (ws_bytes < need) return MM_ERR_WORKSPACE;
-  const int64_t finish_per_row = (nc + 1 + 255) / 256;
-  if (rows > 0x7FFFFFFF / chunks || rows > 0x7FFFFFFF / finish_per_row) return MM_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  ModpsdArgs a;
-  a.x = d_x; a.lens = d_lens; a.window = h->d_window; a.tw = h->d_tw; a.psd = d_psd;
-  a.part = chunks > 1 ? (double*)d_ws : nullptr;
-  a.n_max = n_max; a.x_stride = x_stride; a.psd_stride = psd_stride; a.max_chunks = chunks;
-  a.scale = h->scale;
-  a.nperseg = h->p.nperseg; a.step = h->p.nperseg - h->p.noverlap; a.noverlap = h->p.noverlap; a.detrend = h->p.detrend;
+  const WelchLaunch l = welch_launch_plan(h, rows, n_max, nc + 1, 1, d_lens, d_ws, ws_bytes);
+  if (l.rc != MM_OK) return l.rc;
+  const ModpsdArgs a = {welch_args(h, d_lens, n_max, l.chunks, d_ws), d_x, d_psd, x_stride, psd_stride};
   // LDS: the four transform buffers, 8 nc bytes each (64 KiB at nfft 4096); the two hand-off buffers of (nc + 1) float64
   // lie over them
   const size_t lds = std::max((size_t)MPSD_WAVES * nc * sizeof(float2), (size_t)2 * (nc + 1) * sizeof(double));
-  hipLaunchKernelGGL(mpsd_kernel_of(h->log2n), dim3((unsigned)(rows * chunks)), dim3(64 * MPSD_WAVES), lds, st, a);
-  if (chunks > 1)
-    hipLaunchKernelGGL(modpsd_finish_kernel, dim3((unsigned)(rows * finish_per_row)), dim3(256), 0, st, a, nc);
-  HIP_TRY(hipGetLastError());
-  return MM_OK;
+  return welch_launch(mpsd_kernel_of(h->log2n), modpsd_finish_kernel, a, l, rows, nc + 1, lds, stream);
 }
 
 }  // extern "C"

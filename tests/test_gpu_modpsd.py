@@ -379,37 +379,14 @@ def _ctypes_case():
 STREAM_CASES = [_wrapper_case(False), _wrapper_case(True), _ctypes_case()]
 
 
-class _Session(TS.Session):
-    """test_gpu_streams.Session over STREAM_CASES instead of the registry: the entries, the calibrated gate, the side stream."""
-
-    def __init__(self, gpu):
-        import torch
-        self.gpu = gpu
-        self.entries = {c.name: TS.Entry(c, gpu) for c in STREAM_CASES}
-        torch.cuda._sleep(1_000_000)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        cycles = 20_000_000
-        e0.record()
-        torch.cuda._sleep(cycles)
-        e1.record()
-        torch.cuda.synchronize()
-        self.cycles_per_ms = cycles / e0.elapsed_time(e1)
-        for e in self.entries.values():
-            if e.error is not None:
-                raise e.error
-        self.gate_ms = max(TS.GATE_FLOOR_MS, TS.GATE_FACTOR * max(e.host_ms for e in self.entries.values()))
-        self.capture_stuck = None
-        self.side = self.pick_side_stream()
-
-
 _SESSION = []
 
 
 @pytest.fixture(scope="module")
 def stream_session(gpu):
+    """test_gpu_streams.Session over STREAM_CASES instead of the registry: the entries, the calibrated gate, the side stream."""
     if not _SESSION:
-        _SESSION.append(_Session(gpu))
+        _SESSION.append(TS.Session(gpu, cases=STREAM_CASES))
     return _SESSION[0]
 
 

@@ -128,10 +128,10 @@ class Entry:
 
 
 class Session:
-    def __init__(self, gpu):
+    def __init__(self, gpu, cases=None):
         import torch
         self.gpu = gpu
-        self.entries = {c.name: Entry(c, gpu) for c in S.CASES}
+        self.entries = {c.name: Entry(c, gpu) for c in (S.CASES if cases is None else cases)}
         torch.cuda._sleep(1_000_000)                    # (the sleep kernel's own first launch)
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

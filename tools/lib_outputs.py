@@ -9,7 +9,8 @@ Case set `s16`: the smallest shapes that reach each code path of the staged n_ff
 matrix-pipe kernel.  n_fft 512, 16 kHz, win 400, 40 mel / 13 MFCC unless said otherwise.
 Case set `tail`: every kernel of mm_tail.hip and its includes (tail_cases).
 Case set `ragged`: every public *_ragged_batch function with host and with device lengths, and the four list front ends
-(ragged_cases) -- for a change of the host code, run on two checkouts with the same library."""
+(ragged_cases) -- for a change of the host code, run on two checkouts with the same library.
+Case set `welch`: every instantiation and path of the Welch power and cross spectrum kernels (welch_cases)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -293,7 +294,75 @@ def ragged_cases():
     return out
 
 
-CASESETS = {"s16": s16_cases, "tail": tail_cases, "ragged": ragged_cases}
+def welch_cases():
+    """Case set `welch`: every instantiation and path of mm_modpsd.hip / mm_modcsd.hip (and what mm_welch.hip.inc holds for
+    both) at the smallest shape that reaches it.  Float32 noise, device lengths throughout."""
+    import torch
+    import modulation_mfcc_amd as M
+    dev = torch.device("cuda", 0)
+    out = {}
+    FS = 200.0
+
+    def keep(name, result):
+        for k, t in enumerate(result[1:]):                         # (result[0] is the host frequency grid)
+            out["%s.%d" % (name, k)] = t.cpu().numpy()
+
+    def noise(seed, rows, n):
+        return torch.from_numpy(np.random.default_rng(seed).standard_normal((rows, n), dtype=np.float32)).to(dev)
+
+    def lengths(*lens):
+        return torch.tensor(lens, dtype=torch.int64, device=dev)
+
+    def one_launch(nperseg):
+        """no segment (a NaN row), one segment, five (half overlap): wave 0 takes a second segment, wave 1 .. 3 one each"""
+        return 3 * nperseg, (nperseg - 1, nperseg, 3 * nperseg)
+
+    # nperseg 8, noverlap 7: a segment per sample from the 8th on; 32 segments end the first chunk, 33 put one into the
+    # second, 65 make three chunks -- the workspace and the finish kernels
+    TWO = dict(nperseg=8, noverlap=7)
+    TWO_N, TWO_LENS = 72, (39, 40, 72)
+
+    def cross(name, x, y, ld, **kw):
+        """all four outputs in one call, Pxy alone, Cxy alone"""
+        keep(name + ".all", M.modulation_cross_spectra_ragged_batch(x, y, ld, FS, **kw))
+        keep(name + ".csd", M.modulation_csd_ragged_batch(x, y, ld, FS, **kw))
+        keep(name + ".coh", M.modulation_coherence_ragged_batch(x, y, ld, FS, **kw))
+
+    for log2n in range(5, 13):
+        nfft = 1 << log2n
+        n, lens = one_launch(nfft)
+        x, y = noise(log2n, 6, n), noise(100 + log2n, 3, n)
+        keep("psd.n%d" % nfft, M.modulation_psd_ragged_batch(x[:3], lengths(*lens), FS, nperseg=nfft, nfft=nfft))
+        if nfft <= 2048:
+            cross("csd.n%d" % nfft, x[:3], y, lengths(*lens), nperseg=nfft, nfft=nfft)
+            cross("csd.n%d.group3" % nfft, x, y[:2], lengths(*(lens + lens)), nperseg=nfft, nfft=nfft)
+        if nfft in (32, 2048, 4096):
+            x, y = noise(200 + log2n, 6, TWO_N), noise(300 + log2n, 3, TWO_N)
+            if nfft != 2048:
+                keep("psd2.n%d" % nfft, M.modulation_psd_ragged_batch(x[:3], lengths(*TWO_LENS), FS, nfft=nfft, **TWO))
+            if nfft != 4096:
+                cross("csd2.n%d" % nfft, x[:3], y, lengths(*TWO_LENS), nfft=nfft, **TWO)
+                cross("csd2.n%d.group3" % nfft, x, y[:2], lengths(*(TWO_LENS + TWO_LENS)), nfft=nfft, **TWO)
+    # nfft 64 over a segment of 50 samples (zeros behind it): the detrends and scalings, and a window given as an array
+    n, lens = one_launch(50)
+    x = noise(400, 3, n)
+    for detrend in (False, "constant", "linear"):
+        for scaling in ("density", "spectrum"):
+            keep("psd.n64.%s.%s" % (detrend, scaling), M.modulation_psd_ragged_batch(
+                x, lengths(*lens), FS, nperseg=50, nfft=64, detrend=detrend, scaling=scaling))
+    keep("psd.n64.window", M.modulation_psd_ragged_batch(x, lengths(*lens), FS, window=np.hamming(50).astype(np.float32),
+                                                         nperseg=50, nfft=64, detrend="linear"))
+    # the cross kernel's factor 0 (a side of zeros), its half exponents (a side at 1e-6) and what lies behind a length
+    y = torch.stack([torch.zeros(n, device=dev), 1e-6 * noise(401, 1, n)[0], noise(402, 1, n)[0]])
+    y[2, 120:] = float("nan")
+    x = x.clone()
+    x[2, 120:] = float("nan")
+    cross("csd.n64.sides", x, y, lengths(n, n, 120), nperseg=50, nfft=64, detrend="linear")
+    torch.cuda.synchronize()
+    return out
+
+
+CASESETS = {"s16": s16_cases, "tail": tail_cases, "ragged": ragged_cases, "welch": welch_cases}
 
 if __name__ == "__main__":
     if len(sys.argv) == 4 and sys.argv[1] == "--compare":
