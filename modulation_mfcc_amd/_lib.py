@@ -1,5 +1,6 @@
 """ctypes binding of libmodmfcc.so (include/modmfcc.h and, for the Welch modulation power spectrum, include/modmfcc_modpsd.h;
-for the Welch cross spectrum and coherence, include/modmfcc_modcsd.h).
+for the Welch cross spectrum and coherence, include/modmfcc_modcsd.h; for the quadratic and cubic spline gap filling,
+include/modmfcc_spline.h).
 
 There is NO CPU fallback: when the shared library cannot be loaded, or a plan cannot be created
 because no MI355X is visible, the calls raise.  Build the library with
@@ -252,6 +253,14 @@ PROTOTYPES_MODCSD = {
                                 _vp]),
 }
 
+# every symbol include/modmfcc_spline.h declares (the fourth header: interp_NAN's 'quadratic' and 'cubic' kinds)
+MM_SPLINE_QUADRATIC, MM_SPLINE_CUBIC = 2, 3
+PROTOTYPES_SPLINE = {
+    "mm_interp_spline_workspace_bytes": (C.c_size_t, [C.c_int32, _i64, _i64]),
+    "mm_interp_spline_f64": (C.c_int, [C.c_int32, _vp, _i64, _i64, _i64, _vp, _i64, _vp, C.c_size_t, _vp]),
+    "mm_interp_spline_ragged_f64": (C.c_int, [C.c_int32, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, C.c_size_t, _vp]),
+}
+
 _lib = None
 
 
@@ -273,7 +282,7 @@ def load():
             "`make -C modulation_mfcc_amd/csrc` (needs hipcc, --offload-arch=gfx950). "
             "modulation_mfcc_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for table in (PROTOTYPES, PROTOTYPES_MODPSD, PROTOTYPES_MODCSD):
+    for table in (PROTOTYPES, PROTOTYPES_MODPSD, PROTOTYPES_MODCSD, PROTOTYPES_SPLINE):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError when the .so is stale
             fn.restype = res

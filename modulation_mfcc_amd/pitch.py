@@ -6,6 +6,7 @@
     get_f0_batch(clips, sr, method='pyin', ...)                           -> [(f0, f0t), ...]: get_f0 of a list of clips
     pyin(y, fmin=, fmax=, sr=22050, ...)                                  -> librosa.pyin's signature: numpy in, numpy out
     interp_NAN(X, method='linear')                                        -> 'linear' on the device, other kinds via scipy
+    interp_nan_spline_batch(x, 'quadratic' | 'cubic')                     -> scipy's spline gap filling on the device
     get_f0(x, sr, method='pyin', ...)                                     -> (f0, f0t), the reference's signature
 
 The device path is three kernels (csrc/mm_pitch.hip): the cumulative-mean-normalised difference of every frame, the
@@ -29,7 +30,7 @@ from . import ragged
 from .filters import applyFilter, apply_filter_ragged_batch
 
 __all__ = ["pyin_batch", "pyin_ragged_batch", "pyin_ragged_frames", "pyin", "interp_NAN", "interp_nan_batch",
-           "interp_nan_ragged_batch", "get_f0", "get_f0_batch", "pyin_sizes", "beta_tables", "boltzmann_table",
+           "interp_nan_ragged_batch", "interp_nan_spline_batch", "interp_nan_spline_ragged_batch", "get_f0", "get_f0_batch", "pyin_sizes", "beta_tables", "boltzmann_table",
            "transition_matrix", "banded_log_transitions", "pitch_freqs", "pyin_params", "pyin_cmnd", "pyin_records"]
 
 TINY = np.finfo(np.float64).tiny
@@ -585,6 +586,102 @@ def interp_nan_ragged_batch(x, counts, method: str = "linear"):
             ws = torch.empty(int(lib.mm_interp_nan_workspace_bytes(kind, rows, n)), dtype=torch.uint8, device=dev)
             _lib.check(lib.mm_interp_nan_ragged_f64(kind, xd.data_ptr(), rows, n, pitch_, cd.data_ptr(), y.data_ptr(), n,
                                                     ws.data_ptr(), ws.numel(), stream), "mm_interp_nan_ragged_f64")
+    return y.to(x.dtype)
+
+
+SPLINE_CHUNK = 1024         # knots per workgroup of the spline solve (kSpChunk of csrc/mm_spline.hip): longer rows are cut
+# interp_NAN methods of mm_interp_spline_f64 (MM_SPLINE_* of include/modmfcc_spline.h): the kind is the spline's degree
+_SPLINE_KINDS = {"quadratic": 2, "cubic": 3}
+_MSG_SPLINE_FEW = "The number of derivatives at boundaries does not match: expected {}, got 0+0"   # make_interp_spline's
+
+
+def _spline_kind(method, who):
+    if method not in _SPLINE_KINDS:
+        raise ValueError(f"{who}: method must be 'quadratic' or 'cubic', got {method!r}")
+    return _SPLINE_KINDS[method]
+
+
+def _spline_refuse(kind, fewest):
+    """scipy's ValueError for the row with the fewest valid samples among the rows that have a NaN."""
+    if fewest < 1:
+        raise ValueError("cannot reshape array of size 0 into shape (0,newaxis)")          # scipy interp1d of empty x
+    if fewest <= kind:
+        raise ValueError(_MSG_SPLINE_FEW.format(kind + 1 - fewest))
+
+
+def interp_nan_spline_batch(x, method: str = "cubic"):
+    """interp_NAN's 'quadratic' and 'cubic' kinds along the last axis of a CUDA(HIP) tensor [n] or [rows, n] of any float
+    dtype, on the device only (mm_interp_spline_f64): computed in float64 and cast back.  scipy's
+    interp1d(valid indices, valid values, method, fill_value='extrapolate') at the NaN samples -- the not-a-knot cubic
+    spline, the quadratic spline with its knots at the midpoints -- within a few of scipy's own roundings, not bit for
+    bit; samples before the first and behind the last valid one are extrapolated with the end pieces.  The valid samples
+    of a row are compacted by rank, the tridiagonal system of a row is solved in LDS, in chunks of SPLINE_CHUNK knots
+    for a longer row.  A row without a NaN is returned as it is; a row with a NaN and fewer than 3 ('quadratic') or 4
+    ('cubic') valid samples raises scipy's ValueError, after one read-back of the smallest count.  Another method name
+    is a ValueError, a host array a TypeError.  interp_NAN and interp_nan_batch do not route here."""
+    import torch
+    from . import _lib
+    kind = _spline_kind(method, "interp_nan_spline_batch")
+    if not ragged.is_device_tensor(x):
+        raise TypeError("interp_nan_spline_batch takes a CUDA(HIP) tensor")
+    squeeze = x.dim() == 1
+    xs = x.unsqueeze(0) if squeeze else x
+    if xs.dim() != 2:
+        raise ValueError("x must be [n] or [rows, n]")
+    if not xs.is_floating_point():
+        raise TypeError("x must be a floating-point tensor")
+    rows, n = xs.shape
+    if rows == 0 or n == 0:
+        return x.clone()
+    xd = xs.to(torch.float64)
+    if xd.stride(1) != 1 or xd.stride(0) < n:
+        xd = xd.contiguous()
+    fewest = int((~torch.isnan(xd)).sum(dim=1).min())   # the one read-back: what scipy would raise for
+    if fewest == n:
+        return x.clone()
+    _spline_refuse(kind, fewest)
+    y = torch.empty((rows, n), dtype=torch.float64, device=xd.device)
+    lib = _lib.load()
+    with torch.cuda.device(xd.device):
+        ws = torch.empty(int(lib.mm_interp_spline_workspace_bytes(kind, rows, n)), dtype=torch.uint8, device=xd.device)
+        _lib.check(lib.mm_interp_spline_f64(kind, xd.data_ptr(), rows, n, ragged.row_pitch(xd), y.data_ptr(), n, ws.data_ptr(),
+                                            ws.numel(), C.c_void_p(torch.cuda.current_stream(xd.device).cuda_stream)),
+                   "mm_interp_spline_f64")
+    y = y.to(x.dtype)
+    return y[0] if squeeze else y
+
+
+def interp_nan_spline_ragged_batch(x, counts, method: str = "cubic"):
+    """interp_nan_spline_batch with a count per row: ``x`` [rows, n_max] on the device, ``counts`` [rows] (host integers,
+    validated: ValueError outside [1, n_max]; or an int64 device tensor, clamped by the kernels) -> [rows, n_max] of x's
+    dtype.  Row b holds interp_nan_spline_batch(x[b, :counts[b]], method) in the columns [0, counts[b]), bit for bit, and
+    zeros behind them; what x holds behind a row's count never matters.  The errors are interp_nan_spline_batch's, taken
+    from the smallest number of valid samples below a row's count, in one read-back."""
+    import torch
+    from . import _lib
+    kind = _spline_kind(method, "interp_nan_spline_ragged_batch")
+    xd = ragged.device_rows(x, (torch.float64,), "interp_nan_spline_ragged_batch takes a CUDA(HIP) tensor",
+                            "x must be [rows, n_max]", widen=torch.float64, nonempty=False)
+    if not x.is_floating_point():
+        raise TypeError("x must be a floating-point tensor")
+    rows, n = x.shape
+    if rows == 0 or n == 0:
+        return x.clone()
+    dev = x.device
+    cnt = ragged.check_counts(counts, rows, n, dev, "counts")
+    with torch.cuda.device(dev):
+        cd = ragged.counts_on_device(cnt, dev)
+        c = cd.clamp(1, n)
+        valid = ((~torch.isnan(xd)) & (torch.arange(n, device=dev)[None, :] < c[:, None])).sum(dim=1)
+        # a row without a NaN below its count is returned as it is, however few samples it has
+        _spline_refuse(kind, int(torch.where(valid < c, valid, torch.full_like(valid, kind + 1)).min()))
+        y = torch.empty((rows, n), dtype=torch.float64, device=dev)
+        lib = _lib.load()
+        ws = torch.empty(int(lib.mm_interp_spline_workspace_bytes(kind, rows, n)), dtype=torch.uint8, device=dev)
+        _lib.check(lib.mm_interp_spline_ragged_f64(kind, xd.data_ptr(), rows, n, ragged.row_pitch(xd), cd.data_ptr(),
+                                                   y.data_ptr(), n, ws.data_ptr(), ws.numel(),
+                                                   C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                   "mm_interp_spline_ragged_f64")
     return y.to(x.dtype)
 
 
