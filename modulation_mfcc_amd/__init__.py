@@ -28,6 +28,7 @@ from .audio_io import plan_wav_batch, load_wav_batch, resample_ragged_batch, loa
 from .pitch import pyin_batch, pyin, interp_NAN, interp_nan_batch, get_f0  # noqa: F401
 from .pitch import pyin_ragged_batch, pyin_ragged_frames, interp_nan_ragged_batch, get_f0_batch  # noqa: F401
 from .pitch import interp_nan_spline_batch, interp_nan_spline_ragged_batch  # noqa: F401
+from .lomb import modulation_lombscargle_batch, modulation_lombscargle_ragged_batch, modulation_lombscargle_list  # noqa: F401
 from .ema import read_AG50x, read_AG50x_arrays, read_pos_header  # noqa: F401
 
 __version__ = "0.2.0"

@@ -1,6 +1,6 @@
 """ctypes binding of libmodmfcc.so (include/modmfcc.h and, for the Welch modulation power spectrum, include/modmfcc_modpsd.h;
 for the Welch cross spectrum and coherence, include/modmfcc_modcsd.h; for the quadratic and cubic spline gap filling,
-include/modmfcc_spline.h).
+include/modmfcc_spline.h; for the Lomb-Scargle periodogram of rows with holes, include/modmfcc_lomb.h).
 
 There is NO CPU fallback: when the shared library cannot be loaded, or a plan cannot be created
 because no MI355X is visible, the calls raise.  Build the library with
@@ -261,6 +261,17 @@ PROTOTYPES_SPLINE = {
     "mm_interp_spline_ragged_f64": (C.c_int, [C.c_int32, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, C.c_size_t, _vp]),
 }
 
+# every symbol include/modmfcc_lomb.h declares (the fifth header: the Lomb-Scargle periodogram of rows with holes)
+MM_LOMB_PRECENTER, MM_LOMB_FLOATING_MEAN = 1, 2
+MM_LOMB_POWER, MM_LOMB_NORMALIZE, MM_LOMB_AMPLITUDE = 0 << 2, 1 << 2, 2 << 2
+MM_LOMB_CHUNK = 512
+PROTOTYPES_LOMB = {
+    "mm_lomb_version": (C.c_int, []),
+    "mm_lombscargle_workspace_bytes": (C.c_size_t, [_i64, _i64, _i64]),
+    "mm_lombscargle_f64": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, C.c_int32, _vp, _i64, _vp, _vp, C.c_size_t,
+                                     _vp]),
+}
+
 _lib = None
 
 
@@ -282,7 +293,7 @@ def load():
             "`make -C modulation_mfcc_amd/csrc` (needs hipcc, --offload-arch=gfx950). "
             "modulation_mfcc_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for table in (PROTOTYPES, PROTOTYPES_MODPSD, PROTOTYPES_MODCSD, PROTOTYPES_SPLINE):
+    for table in (PROTOTYPES, PROTOTYPES_MODPSD, PROTOTYPES_MODCSD, PROTOTYPES_SPLINE, PROTOTYPES_LOMB):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError when the .so is stale
             fn.restype = res
