@@ -25,9 +25,10 @@ from .filters import (sosfiltfilt_ragged_batch, fir_filtfilt_ragged_batch, savgo
                       apply_filter_ragged_batch, applyFilter_batch)
 from .audio_io import load_audio, load_wav, resample_batch  # noqa: F401
 from .audio_io import plan_wav_batch, load_wav_batch, resample_ragged_batch, load_audio_batch  # noqa: F401
-from .pitch import pyin_batch, pyin, interp_NAN, interp_nan_batch, get_f0  # noqa: F401
-from .pitch import pyin_ragged_batch, pyin_ragged_frames, interp_nan_ragged_batch, get_f0_batch  # noqa: F401
-from .pitch import interp_nan_spline_batch, interp_nan_spline_ragged_batch  # noqa: F401
+from .pitch import pyin_batch, pyin, get_f0  # noqa: F401
+from .pitch import pyin_ragged_batch, pyin_ragged_frames, get_f0_batch  # noqa: F401
+from .interp import interp_NAN, interp_nan_batch, interp_nan_ragged_batch  # noqa: F401
+from .interp import interp_nan_spline_batch, interp_nan_spline_ragged_batch  # noqa: F401
 from .lomb import modulation_lombscargle_batch, modulation_lombscargle_ragged_batch, modulation_lombscargle_list  # noqa: F401
 from .ema import read_AG50x, read_AG50x_arrays, read_pos_header  # noqa: F401
 

@@ -3,7 +3,7 @@
 script/calc.py holds no MFCC arithmetic; what the north star names as the
 drop-in surface is ``applyFilter`` (script/calc.py:23-129), ``get_velocity`` (:593-650, applied by
 the UI to the MFCC-change curve, script/main.py:668-713) and the RMS / Hilbert amplitude envelope
-(:221-343), the pYIN branch of ``get_f0`` with its ``interp_NAN`` (:345-592; modulation_mfcc_amd.pitch) and
+(:221-343), the pYIN branch of ``get_f0`` with its ``interp_NAN`` (:345-592; modulation_mfcc_amd.pitch, .interp) and
 ``MinMaxFinder`` (:651-686: the peaks and troughs of a drawn curve, scipy.signal.find_peaks on the device --
 ``find_peaks_batch`` for [rows, n] device curves, ``find_peaks_ex_batch`` with scipy's remaining conditions).  Praat-backed
 functions (f0 by 'praatac' / 'praatcc', formants, RMSpraat) are out of scope.  ``read_AG50x`` (:173-219), the
@@ -16,7 +16,8 @@ from scipy.signal import savgol_filter
 
 from . import ragged
 from .filters import applyFilter
-from .pitch import get_f0, get_f0_batch, interp_NAN, interp_nan_batch, interp_nan_ragged_batch  # noqa: F401
+from .interp import interp_NAN, interp_nan_batch, interp_nan_ragged_batch  # noqa: F401
+from .pitch import get_f0, get_f0_batch  # noqa: F401
 from .ema import read_AG50x, read_AG50x_arrays, read_pos_header  # noqa: F401
 
 __all__ = ["applyFilter", "get_f0", "get_f0_batch", "interp_NAN", "interp_nan_batch", "interp_nan_ragged_batch",

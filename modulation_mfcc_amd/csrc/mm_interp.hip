@@ -1,8 +1,10 @@
 // libmodmfcc: the two places where the reference's script/calc.py calls scipy.interpolate.  gfx950 only.
-//   interp_NAN (script/calc.py:345-385) for the kinds that need no solve over all knots: pchip (PchipInterpolator after
-//   the reference's end fix), nearest, nearest-up, previous, next, zero and slinear (interp1d, fill_value='extrapolate').
+//   interp_NAN (script/calc.py:345-385) for the kinds that need no solve over all knots: linear, pchip (PchipInterpolator
+//   after the reference's end fix), nearest, nearest-up, previous, next, zero and slinear (interp1d,
+//   fill_value='extrapolate').  ('quadratic' and 'cubic' are mm_spline.hip.)
 //   read_AG50x (script/calc.py:173-219): interp1d(t_in, float32 column, 'linear') of every column of a .pos file.
 // The kernels:
+//   interp_linear_kernel   'linear': a workgroup per row, a thread per contiguous piece of it
 //   ip_summary_kernel   a workgroup per segment of kIpSeg samples: the validity of its samples as sixteen wave ballots,
 //                       from them the first two and the last two valid samples of the segment
 //   ip_scan_kernel      a wave per row: the last two valid samples before and the first two after every segment (a scan of
@@ -215,6 +217,80 @@ __global__ __launch_bounds__(kIpThreads) void ip_eval_kernel(const double* __res
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// interp_NAN(method='linear'): scipy.interpolate.interp1d(valid idx, valid values, 'linear', fill_value='extrapolate')
+// at the NaN positions -- slope = (y_hi - y_lo) / (x_hi - x_lo), y = slope * (x - x_lo) + y_lo with (lo, hi) the
+// neighbouring valid samples inside, the first two / last two valid samples beyond the ends.  A workgroup per row;
+// thread t walks the contiguous segment t, with the valid neighbours of its segment from a scan of per-segment ends.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int kInterpThreads = 256;
+
+// counts (or nullptr): row b is the curve of its first c_b = clamp(counts[b], 1, n_max) samples -- whatever lies behind
+// is no sample of it, and columns [c_b, n_max) of the output are 0.
+__global__ __launch_bounds__(kInterpThreads) void interp_linear_kernel(const double* __restrict__ x, int64_t n_max,
+                                                                       int64_t stride, const int64_t* __restrict__ counts,
+                                                                       double* __restrict__ y, int64_t y_stride) {
+#pragma clang fp contract(off)
+  __shared__ int64_t s_first[kInterpThreads][2], s_last[kInterpThreads][2];
+  __shared__ int64_t s_ends[4];
+  const double* xr = x + blockIdx.x * stride;
+  double* yr = y + blockIdx.x * y_stride;
+  const int t = threadIdx.x;
+  const int64_t n = counts ? min<int64_t>(max<int64_t>(counts[blockIdx.x], 1), n_max) : n_max;
+  for (int64_t i = n + t; i < n_max; i += kInterpThreads) yr[i] = 0.0;
+  const int64_t L = (n + kInterpThreads - 1) / kInterpThreads;
+  const int64_t b = min<int64_t>(n, t * L), e = min<int64_t>(n, b + L);
+  int64_t f1 = -1, f2 = -1, l1 = -1, l2 = -1;     // first two / last two valid samples of the segment
+  for (int64_t i = b; i < e; ++i) {
+    if (!isnan(xr[i])) {
+      if (f1 < 0) f1 = i; else if (f2 < 0) f2 = i;
+      l2 = l1; l1 = i;
+    }
+  }
+  s_first[t][0] = f1; s_first[t][1] = f2; s_last[t][0] = l1; s_last[t][1] = l2;
+  __syncthreads();
+  if (t == 0) {
+    int64_t a0 = -1, a1 = -1, z0 = -1, z1 = -1;
+    for (int s = 0; s < kInterpThreads && a1 < 0; ++s)
+      for (int q = 0; q < 2; ++q) {
+        const int64_t v = s_first[s][q];
+        if (v >= 0 && a1 < 0) { if (a0 < 0) a0 = v; else if (v != a0) a1 = v; }
+      }
+    for (int s = kInterpThreads - 1; s >= 0 && z1 < 0; --s)
+      for (int q = 0; q < 2; ++q) {
+        const int64_t v = s_last[s][q];
+        if (v >= 0 && z1 < 0) { if (z0 < 0) z0 = v; else if (v != z0) z1 = v; }
+      }
+    s_ends[0] = a0; s_ends[1] = a1; s_ends[2] = z1; s_ends[3] = z0;
+  }
+  __syncthreads();
+  const int64_t a0 = s_ends[0], a1 = s_ends[1], z1 = s_ends[2], z0 = s_ends[3];
+  if (a1 < 0) {                                   // fewer than two valid samples: scipy raises; the host checks first
+    for (int64_t i = b; i < e; ++i) yr[i] = xr[i];
+    return;
+  }
+  int64_t p = -1;                                 // last valid sample before the segment
+  for (int s = t - 1; s >= 0 && p < 0; --s) p = s_last[s][0];
+  int64_t q = -1;                                 // next valid sample at or after i (searched once per NaN run)
+  for (int64_t i = b; i < e; ++i) {
+    const double v = xr[i];
+    if (!isnan(v)) { yr[i] = v; p = i; continue; }
+    if (q <= i) {
+      q = -1;
+      for (int64_t k = i + 1; k < e && q < 0; ++k) if (!isnan(xr[k])) q = k;
+      for (int s = t + 1; s < kInterpThreads && q < 0; ++s) q = s_first[s][0];
+      if (q < 0) q = n;                           // none: extrapolation from the last two
+    }
+    int64_t lo_i, hi_i;
+    if (p < 0) { lo_i = a0; hi_i = a1; }
+    else if (q >= n) { lo_i = z1; hi_i = z0; }
+    else { lo_i = p; hi_i = q; }
+    const double ylo = xr[lo_i], yhi = xr[hi_i];
+    const double slope = (yhi - ylo) / ((double)hi_i - (double)lo_i);
+    yr[i] = slope * ((double)i - (double)lo_i) + ylo;
+  }
+}
+
 // out[j][c] = interp1d(t_in, y[:, c], 'linear')(t_out[j]) with y float32: scipy's searchsorted index clipped to [1, n - 1],
 // the float32 difference of the two samples over the float64 step, slope * (t - t_lo) + y_lo in float64
 __global__ __launch_bounds__(kIpThreads) void regrid_linear_kernel(const float* __restrict__ yv, int64_t n, int64_t cols,
@@ -239,10 +315,6 @@ __global__ __launch_bounds__(kIpThreads) void regrid_linear_kernel(const float* 
   out[j * out_stride + c] = slope * (t - t_lo) + (double)y_lo;
 }
 
-size_t ip_align(size_t v) { return (v + 255) / 256 * 256; }
-
-int64_t ip_nseg(int64_t n) { return (n + kIpSeg - 1) / kIpSeg; }
-
 template <int KIND>
 void ip_launch_eval(unsigned blocks, hipStream_t st, const double* d_x, int64_t n, int64_t x_stride, const int64_t* d_counts,
                     double* d_y, int64_t y_stride, int32_t nseg, const int4* carry, const int4* rowinfo) {
@@ -252,11 +324,9 @@ void ip_launch_eval(unsigned blocks, hipStream_t st, const double* d_x, int64_t 
 
 int ip_run(int32_t kind, const double* d_x, int64_t rows, int64_t n, int64_t x_stride, const int64_t* d_counts, double* d_y,
            int64_t y_stride, void* d_ws, size_t ws_bytes, void* stream) {
-  if (kind < 0 || kind >= IP_KINDS || !d_x || !d_y || !d_ws || rows < 1 || rows > 0x7fffffff || n < 1 || n > kIpMaxN ||
-      x_stride < n || y_stride < n)
+  if (kind < 0 || kind >= IP_KINDS || !ip_shape_ok(rows, n) || !d_x || !d_y || !d_ws || x_stride < n || y_stride < n)
     return MM_ERR_INVALID_ARG;
   const int64_t nseg = ip_nseg(n);
-  if (rows * nseg > 0x7fffffff) return MM_ERR_INVALID_ARG;
   if (ws_bytes < mm_interp_nan_workspace_bytes(kind, rows, n)) return MM_ERR_WORKSPACE;
   char* w = (char*)d_ws;
   int4* summary = (int4*)w;  w += ip_align((size_t)rows * nseg * sizeof(int4));
@@ -289,9 +359,8 @@ int ip_run(int32_t kind, const double* d_x, int64_t rows, int64_t n, int64_t x_s
 extern "C" {
 
 size_t mm_interp_nan_workspace_bytes(int32_t kind, int64_t rows, int64_t n) {
-  if (kind < 0 || kind >= IP_KINDS || rows < 1 || rows > 0x7fffffff || n < 1 || n > kIpMaxN) return 0;
+  if (kind < 0 || kind >= IP_KINDS || !ip_shape_ok(rows, n)) return 0;
   const int64_t nseg = ip_nseg(n);
-  if (rows * nseg > 0x7fffffff) return 0;
   return 2 * ip_align((size_t)rows * nseg * sizeof(int4)) + ip_align((size_t)rows * sizeof(int4));
 }
 
@@ -305,6 +374,25 @@ int mm_interp_nan_ragged_f64(int32_t kind, const double* d_x, int64_t rows, int6
                              void* stream) {
   if (!d_counts) return MM_ERR_INVALID_ARG;
   return ip_run(kind, d_x, rows, n_max, x_stride, d_counts, d_y, y_stride, d_ws, ws_bytes, stream);
+}
+
+int mm_interp_nan_linear_f64(const double* d_x, int64_t rows, int64_t n, int64_t x_stride, double* d_y, int64_t y_stride,
+                             void* stream) {
+  if (!d_x || !d_y || rows < 1 || rows > 0x7fffffff || n < 1 || x_stride < n || y_stride < n) return MM_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(interp_linear_kernel, dim3((unsigned)rows), dim3(kInterpThreads), 0, (hipStream_t)stream, d_x, n,
+                     x_stride, (const int64_t*)nullptr, d_y, y_stride);
+  HIP_TRY(hipGetLastError());
+  return MM_OK;
+}
+
+int mm_interp_nan_linear_ragged_f64(const double* d_x, int64_t rows, int64_t n_max, int64_t x_stride,
+                                    const int64_t* d_counts, double* d_y, int64_t y_stride, void* stream) {
+  if (!d_x || !d_y || !d_counts || rows < 1 || rows > 0x7fffffff || n_max < 1 || x_stride < n_max || y_stride < n_max)
+    return MM_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(interp_linear_kernel, dim3((unsigned)rows), dim3(kInterpThreads), 0, (hipStream_t)stream, d_x, n_max,
+                     x_stride, d_counts, d_y, y_stride);
+  HIP_TRY(hipGetLastError());
+  return MM_OK;
 }
 
 int mm_regrid_linear_f32_f64(const float* d_y, int64_t n, int64_t cols, int64_t y_stride, const double* d_t_in,

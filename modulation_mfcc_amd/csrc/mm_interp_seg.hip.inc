@@ -1,12 +1,13 @@
 // What the segmented NaN-interpolation units share (mm_interp.hip, mm_spline.hip): the segment size, the load of a
-// segment with its validity ballots, the sample count of a row, the search of the ballots for a valid neighbour.
+// segment with its validity ballots, the sample count of a row, the search of the ballots for a valid neighbour; on the
+// host the workspace alignment, the segment count and the shape limit.
 #pragma once
 
 namespace {
 
 constexpr int kIpThreads = 256;
 constexpr int kIpPer = 4;                               // samples per thread, strided by the workgroup
-constexpr int kIpSeg = kIpThreads * kIpPer;             // samples per segment = workgroup (pitch.INTERP_SEGMENT)
+constexpr int kIpSeg = kIpThreads * kIpPer;             // samples per segment = workgroup (interp.INTERP_SEGMENT)
 constexpr int kIpWords = kIpSeg / 64;                   // ballots per segment
 constexpr int64_t kIpMaxN = 0x7fffffff - kIpSeg;        // indices are int32, the segment's end included
 
@@ -42,6 +43,14 @@ __device__ __forceinline__ int ip_seg_next(const uint64_t* s_m, int j) {
   uint64_t bits = b == 63 ? 0ull : s_m[w] & (~0ull << (b + 1));
   while (bits == 0 && w < kIpWords - 1) bits = s_m[++w];
   return bits ? (w << 6) + __ffsll((unsigned long long)bits) - 1 : -1;
+}
+
+// host: a workspace part's size (parts start on 256 bytes), the segments of a row, and the shapes the units take -- rows
+// and rows x segments are grid sizes, a sample's index is an int32
+size_t ip_align(size_t v) { return (v + 255) / 256 * 256; }
+int64_t ip_nseg(int64_t n) { return (n + kIpSeg - 1) / kIpSeg; }
+bool ip_shape_ok(int64_t rows, int64_t n) {
+  return rows >= 1 && rows <= 0x7fffffff && n >= 1 && n <= kIpMaxN && rows * ip_nseg(n) <= 0x7fffffff;
 }
 
 }  // namespace

@@ -1,5 +1,5 @@
-// libmodmfcc: pYIN f0 tracking (librosa.pyin as get_f0(method='pyin') calls it, script/calc.py:386-592) and the linear
-// NaN interpolation of interp_NAN (:345-385).  gfx950 only.  Three kernels make the path ("Pitch"):
+// libmodmfcc: pYIN f0 tracking (librosa.pyin as get_f0(method='pyin') calls it, script/calc.py:386-592).  gfx950 only.
+// Three kernels make the path ("Pitch"):
 //   pyin_cmnd_kernel   frames -> cumulative-mean-normalised difference rows (float64; the energy terms in the input type)
 //   pyin_cand_kernel   CMND row -> troughs, threshold / Boltzmann probabilities, pitch-bin candidates (a wave per frame)
 //   pyin_viterbi_kernel candidates -> banded Viterbi over the 2 n_bins states (a workgroup per clip) + backtrack
@@ -7,7 +7,7 @@
 // transition matrix of librosa.sequence with numpy's own operations); the device never re-derives them.
 #include "mm_common.h"
 
-// numpy neither fuses a product into a sum nor re-associates: every square, sum and interpolation below is computed
+// numpy neither fuses a product into a sum nor re-associates: every square and sum below is computed
 // as written (hipcc would otherwise contract y * y + c into an fma).  The autocorrelation, which numpy takes through a
 // float64 FFT, uses explicit fma (rounding at 1e-16 relative either way).
 #pragma clang fp contract(off)
@@ -482,79 +482,6 @@ __global__ __launch_bounds__(kVitThreads) void pyin_viterbi_kernel(VitArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// interp_NAN(method='linear'): scipy.interpolate.interp1d(valid idx, valid values, 'linear', fill_value='extrapolate')
-// at the NaN positions -- slope = (y_hi - y_lo) / (x_hi - x_lo), y = slope * (x - x_lo) + y_lo with (lo, hi) the
-// neighbouring valid samples inside, the first two / last two valid samples beyond the ends.  A workgroup per row;
-// thread t walks the contiguous segment t, with the valid neighbours of its segment from a scan of per-segment ends.
-// ---------------------------------------------------------------------------------------------------------------------
-constexpr int kInterpThreads = 256;
-
-// counts (or nullptr): row b is the curve of its first c_b = clamp(counts[b], 1, n_max) samples -- whatever lies behind
-// is no sample of it, and columns [c_b, n_max) of the output are 0.
-__global__ __launch_bounds__(kInterpThreads) void interp_linear_kernel(const double* __restrict__ x, int64_t n_max,
-                                                                       int64_t stride, const int64_t* __restrict__ counts,
-                                                                       double* __restrict__ y, int64_t y_stride) {
-  __shared__ int64_t s_first[kInterpThreads][2], s_last[kInterpThreads][2];
-  __shared__ int64_t s_ends[4];
-  const double* xr = x + blockIdx.x * stride;
-  double* yr = y + blockIdx.x * y_stride;
-  const int t = threadIdx.x;
-  const int64_t n = counts ? min<int64_t>(max<int64_t>(counts[blockIdx.x], 1), n_max) : n_max;
-  for (int64_t i = n + t; i < n_max; i += kInterpThreads) yr[i] = 0.0;
-  const int64_t L = (n + kInterpThreads - 1) / kInterpThreads;
-  const int64_t b = min<int64_t>(n, t * L), e = min<int64_t>(n, b + L);
-  int64_t f1 = -1, f2 = -1, l1 = -1, l2 = -1;     // first two / last two valid samples of the segment
-  for (int64_t i = b; i < e; ++i) {
-    if (!isnan(xr[i])) {
-      if (f1 < 0) f1 = i; else if (f2 < 0) f2 = i;
-      l2 = l1; l1 = i;
-    }
-  }
-  s_first[t][0] = f1; s_first[t][1] = f2; s_last[t][0] = l1; s_last[t][1] = l2;
-  __syncthreads();
-  if (t == 0) {
-    int64_t a0 = -1, a1 = -1, z0 = -1, z1 = -1;
-    for (int s = 0; s < kInterpThreads && a1 < 0; ++s)
-      for (int q = 0; q < 2; ++q) {
-        const int64_t v = s_first[s][q];
-        if (v >= 0 && a1 < 0) { if (a0 < 0) a0 = v; else if (v != a0) a1 = v; }
-      }
-    for (int s = kInterpThreads - 1; s >= 0 && z1 < 0; --s)
-      for (int q = 0; q < 2; ++q) {
-        const int64_t v = s_last[s][q];
-        if (v >= 0 && z1 < 0) { if (z0 < 0) z0 = v; else if (v != z0) z1 = v; }
-      }
-    s_ends[0] = a0; s_ends[1] = a1; s_ends[2] = z1; s_ends[3] = z0;
-  }
-  __syncthreads();
-  const int64_t a0 = s_ends[0], a1 = s_ends[1], z1 = s_ends[2], z0 = s_ends[3];
-  if (a1 < 0) {                                   // fewer than two valid samples: scipy raises; the host checks first
-    for (int64_t i = b; i < e; ++i) yr[i] = xr[i];
-    return;
-  }
-  int64_t p = -1;                                 // last valid sample before the segment
-  for (int s = t - 1; s >= 0 && p < 0; --s) p = s_last[s][0];
-  int64_t q = -1;                                 // next valid sample at or after i (searched once per NaN run)
-  for (int64_t i = b; i < e; ++i) {
-    const double v = xr[i];
-    if (!isnan(v)) { yr[i] = v; p = i; continue; }
-    if (q <= i) {
-      q = -1;
-      for (int64_t k = i + 1; k < e && q < 0; ++k) if (!isnan(xr[k])) q = k;
-      for (int s = t + 1; s < kInterpThreads && q < 0; ++s) q = s_first[s][0];
-      if (q < 0) q = n;                           // none: extrapolation from the last two
-    }
-    int64_t lo_i, hi_i;
-    if (p < 0) { lo_i = a0; hi_i = a1; }
-    else if (q >= n) { lo_i = z1; hi_i = z0; }
-    else { lo_i = p; hi_i = q; }
-    const double ylo = xr[lo_i], yhi = xr[hi_i];
-    const double slope = (yhi - ylo) / ((double)hi_i - (double)lo_i);
-    yr[i] = slope * ((double)i - (double)lo_i) + ylo;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
 int cmnd_tile_frames(const mm_pyin_params* p, int* span_out, size_t* lds_out) {
@@ -799,25 +726,6 @@ int mm_pyin_ragged_f64(const mm_pyin_params* p, const mm_pyin_tables* t, const d
                        int32_t* d_states, int64_t* d_frames, void* d_ws, size_t ws_bytes, void* stream) {
   return pyin_whole<double>(p, t, d_x, rows, n_max, x_stride, true, d_lengths, d_frames, d_f0, d_voiced, d_voiced_prob,
                             d_states, d_ws, ws_bytes, stream);
-}
-
-int mm_interp_nan_linear_f64(const double* d_x, int64_t rows, int64_t n, int64_t x_stride, double* d_y, int64_t y_stride,
-                             void* stream) {
-  if (!d_x || !d_y || rows < 1 || rows > 0x7fffffff || n < 1 || x_stride < n || y_stride < n) return MM_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(interp_linear_kernel, dim3((unsigned)rows), dim3(kInterpThreads), 0, (hipStream_t)stream, d_x, n,
-                     x_stride, (const int64_t*)nullptr, d_y, y_stride);
-  HIP_TRY(hipGetLastError());
-  return MM_OK;
-}
-
-int mm_interp_nan_linear_ragged_f64(const double* d_x, int64_t rows, int64_t n_max, int64_t x_stride,
-                                    const int64_t* d_counts, double* d_y, int64_t y_stride, void* stream) {
-  if (!d_x || !d_y || !d_counts || rows < 1 || rows > 0x7fffffff || n_max < 1 || x_stride < n_max || y_stride < n_max)
-    return MM_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(interp_linear_kernel, dim3((unsigned)rows), dim3(kInterpThreads), 0, (hipStream_t)stream, d_x, n_max,
-                     x_stride, d_counts, d_y, y_stride);
-  HIP_TRY(hipGetLastError());
-  return MM_OK;
 }
 
 }  // extern "C"

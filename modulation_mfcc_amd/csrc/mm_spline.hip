@@ -37,7 +37,7 @@
 
 namespace {
 
-constexpr int kSpChunk = 1024;                          // unknowns per chunk = workgroup (pitch.SPLINE_CHUNK)
+constexpr int kSpChunk = 1024;                          // unknowns per chunk = workgroup (interp.SPLINE_CHUNK)
 constexpr int kSpPer = kSpChunk / kIpThreads;           // rows of the system per thread
 static_assert(kSpChunk <= kIpSeg, "the chunks of a row must not outnumber its segments (grid limit)");
 
@@ -414,14 +414,10 @@ __global__ __launch_bounds__(kIpThreads) void sp_eval_kernel(const double* __res
   }
 }
 
-size_t sp_align(size_t v) { return (v + 255) / 256 * 256; }
-int64_t sp_nseg(int64_t n) { return (n + kIpSeg - 1) / kIpSeg; }
 int64_t sp_nchunk(int64_t n) { return (std::max<int64_t>(n - 2, 1) + kSpChunk - 1) / kSpChunk; }
 
 bool sp_shape_ok(int32_t kind, int64_t rows, int64_t n) {
-  if ((kind != MM_SPLINE_QUADRATIC && kind != MM_SPLINE_CUBIC) || rows < 1 || rows > 0x7fffffff || n < 1 || n > kIpMaxN)
-    return false;
-  return rows * sp_nseg(n) <= 0x7fffffff;
+  return (kind == MM_SPLINE_QUADRATIC || kind == MM_SPLINE_CUBIC) && ip_shape_ok(rows, n);
 }
 
 template <int KIND, bool MULTI>
@@ -435,21 +431,21 @@ int sp_run(int32_t kind, const double* d_x, int64_t rows, int64_t n, int64_t x_s
            int64_t y_stride, void* d_ws, size_t ws_bytes, void* stream) {
   if (!sp_shape_ok(kind, rows, n) || !d_x || !d_y || !d_ws || x_stride < n || y_stride < n) return MM_ERR_INVALID_ARG;
   if (ws_bytes < mm_interp_spline_workspace_bytes(kind, rows, n)) return MM_ERR_WORKSPACE;
-  const int64_t nseg = sp_nseg(n), nchunk = sp_nchunk(n);
+  const int64_t nseg = ip_nseg(n), nchunk = sp_nchunk(n);
   const bool multi = nchunk > 1;
   const size_t cells = (size_t)rows * (size_t)n;
   char* w = (char*)d_ws;
-  int32_t* segoff = (int32_t*)w;  w += sp_align((size_t)rows * nseg * sizeof(int32_t));
-  int32_t* rowK = (int32_t*)w;    w += sp_align((size_t)rows * sizeof(int32_t));
-  int32_t* kpos = (int32_t*)w;    w += sp_align(cells * sizeof(int32_t));
-  double* kval = (double*)w;      w += sp_align(cells * sizeof(double));
-  double* sol = (double*)w;       w += sp_align(cells * sizeof(double));
+  int32_t* segoff = (int32_t*)w;  w += ip_align((size_t)rows * nseg * sizeof(int32_t));
+  int32_t* rowK = (int32_t*)w;    w += ip_align((size_t)rows * sizeof(int32_t));
+  int32_t* kpos = (int32_t*)w;    w += ip_align(cells * sizeof(int32_t));
+  double* kval = (double*)w;      w += ip_align(cells * sizeof(double));
+  double* sol = (double*)w;       w += ip_align(cells * sizeof(double));
   double *spl = nullptr, *spr = nullptr;
   double2 *red = nullptr, *ext = nullptr;
   if (multi) {
-    spl = (double*)w;             w += sp_align(cells * sizeof(double));
-    spr = (double*)w;             w += sp_align(cells * sizeof(double));
-    red = (double2*)w;            w += sp_align((size_t)rows * nchunk * sizeof(double2));
+    spl = (double*)w;             w += ip_align(cells * sizeof(double));
+    spr = (double*)w;             w += ip_align(cells * sizeof(double));
+    red = (double2*)w;            w += ip_align((size_t)rows * nchunk * sizeof(double2));
     ext = (double2*)w;
   }
   hipStream_t st = (hipStream_t)stream;
@@ -491,11 +487,11 @@ extern "C" {
 
 size_t mm_interp_spline_workspace_bytes(int32_t kind, int64_t rows, int64_t n) {
   if (!sp_shape_ok(kind, rows, n)) return 0;
-  const int64_t nseg = sp_nseg(n), nchunk = sp_nchunk(n);
+  const int64_t nseg = ip_nseg(n), nchunk = sp_nchunk(n);
   const size_t cells = (size_t)rows * (size_t)n;
-  size_t b = sp_align((size_t)rows * nseg * sizeof(int32_t)) + sp_align((size_t)rows * sizeof(int32_t)) +
-             sp_align(cells * sizeof(int32_t)) + 2 * sp_align(cells * sizeof(double));
-  if (nchunk > 1) b += 2 * sp_align(cells * sizeof(double)) + 2 * sp_align((size_t)rows * nchunk * sizeof(double2));
+  size_t b = ip_align((size_t)rows * nseg * sizeof(int32_t)) + ip_align((size_t)rows * sizeof(int32_t)) +
+             ip_align(cells * sizeof(int32_t)) + 2 * ip_align(cells * sizeof(double));
+  if (nchunk > 1) b += 2 * ip_align(cells * sizeof(double)) + 2 * ip_align((size_t)rows * nchunk * sizeof(double2));
   return b;
 }
 

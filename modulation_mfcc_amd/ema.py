@@ -13,6 +13,8 @@ import ctypes as C
 
 import numpy as np
 
+from . import ragged
+
 DIMENSIONS = ["x", "z", "y", "phi", "theta", "rms", "extra"]
 # float32 values per record, by channel count: the reference's table.  Its entry for 32 channels is no multiple of 7,
 # so such a file fails in numpy's reshape there, and here.
@@ -48,7 +50,6 @@ def read_AG50x_arrays(path, target_sample_rate=200, device=None):
     header that announces 32 channels raises numpy's ValueError, as it does in the reference."""
     import torch
     from . import _lib
-    from .pitch import _gpu
     with open(path, "rb") as f:
         content = f.read()
     h = _parse_header(content)
@@ -60,7 +61,7 @@ def read_AG50x_arrays(path, target_sample_rate=200, device=None):
     new_time = np.arange(0, original_time[-1], 1 / target_sample_rate)
     if n < 2:
         raise ValueError("x and y arrays must have at least 2 entries")      # interp1d's, for a file of one record
-    dev = torch.device(device) if device is not None else _gpu()
+    dev = torch.device(device) if device is not None else ragged.gpu()
     m, cols = len(new_time), channels * 7
     out = torch.empty((m, channels, 7), dtype=torch.float64, device=dev)
     if m > 0:

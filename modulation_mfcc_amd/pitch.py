@@ -1,12 +1,10 @@
 """pYIN f0 tracking on the GPU: librosa.pyin as the reference's ``get_f0(method='pyin')`` calls it
-(script/calc.py:386-592), and its ``interp_NAN`` (:345-385).
+(script/calc.py:386-592).
 
     pyin_batch(audio [B, n] | [n] device tensor, sr, fmin=, fmax=, ...)  -> (f0, voiced_flag, voiced_prob) on the device
     pyin_ragged_batch(audio [B, n_max], lengths [B], sr, ...)             -> the same with a length per clip (+ frames [B])
     get_f0_batch(clips, sr, method='pyin', ...)                           -> [(f0, f0t), ...]: get_f0 of a list of clips
     pyin(y, fmin=, fmax=, sr=22050, ...)                                  -> librosa.pyin's signature: numpy in, numpy out
-    interp_NAN(X, method='linear')                                        -> 'linear' on the device, other kinds via scipy
-    interp_nan_spline_batch(x, 'quadratic' | 'cubic')                     -> scipy's spline gap filling on the device
     get_f0(x, sr, method='pyin', ...)                                     -> (f0, f0t), the reference's signature
 
 The device path is three kernels (csrc/mm_pitch.hip): the cumulative-mean-normalised difference of every frame, the
@@ -24,14 +22,18 @@ import inspect
 import numpy as np
 import scipy.signal
 import scipy.stats
-from scipy import interpolate
 
 from . import ragged
 from .filters import applyFilter, apply_filter_ragged_batch
+from .interp import _INTERP_KINDS, interp_NAN, interp_nan_ragged_batch
+# gap filling lived in this module before interp.py: its names stay importable from here
+from .interp import (INTERP_SEGMENT, SPLINE_CHUNK, _INTERP_HOST_KINDS, _SPLINE_KINDS, _interp_nan_host,  # noqa: F401
+                     _spline_refuse, interp_nan_batch, interp_nan_spline_batch, interp_nan_spline_ragged_batch)
 
 __all__ = ["pyin_batch", "pyin_ragged_batch", "pyin_ragged_frames", "pyin", "interp_NAN", "interp_nan_batch",
-           "interp_nan_ragged_batch", "interp_nan_spline_batch", "interp_nan_spline_ragged_batch", "get_f0", "get_f0_batch", "pyin_sizes", "beta_tables", "boltzmann_table",
-           "transition_matrix", "banded_log_transitions", "pitch_freqs", "pyin_params", "pyin_cmnd", "pyin_records"]
+           "interp_nan_ragged_batch", "interp_nan_spline_batch", "interp_nan_spline_ragged_batch", "get_f0", "get_f0_batch",
+           "pyin_sizes", "beta_tables", "boltzmann_table", "transition_matrix", "banded_log_transitions", "pitch_freqs",
+           "pyin_params", "pyin_cmnd", "pyin_records"]
 
 TINY = np.finfo(np.float64).tiny
 PYIN_WS_BYTES = 512 << 20      # scratch bound of one device call (back-pointers + per-frame records): batches are cut to fit
@@ -402,20 +404,13 @@ def pyin_records(cmnd, sr, *, fmin, fmax, frame_length=2048, win_length=None, ho
     return count, bins, probs, vp
 
 
-def _gpu():
-    import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("modulation_mfcc_amd needs an AMD GPU (gfx950); there is no CPU fallback")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def _to_device_signal(y):
     """numpy -> device tensor: float32 and float64 keep their type, integer PCM (and anything else) becomes float64."""
     import torch
     a = np.asarray(y)
     if a.dtype not in (np.float32, np.float64):
         a = a.astype(np.float64)
-    return torch.from_numpy(np.ascontiguousarray(a)).to(_gpu())
+    return torch.from_numpy(np.ascontiguousarray(a)).to(ragged.gpu())
 
 
 def pyin(y, *, fmin, fmax, sr=22050, frame_length=2048, win_length=None, hop_length=None, n_thresholds=100,
@@ -432,287 +427,8 @@ def pyin(y, *, fmin, fmax, sr=22050, frame_length=2048, win_length=None, hop_len
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# interp_NAN / get_f0 (script/calc.py:345-592)
+# get_f0 (script/calc.py:386-592)
 # ---------------------------------------------------------------------------------------------------------------------
-def _interp_linear_device(X):
-    import torch
-    from . import _lib
-    squeeze = X.dim() == 1
-    x = X.unsqueeze(0) if squeeze else X
-    if x.dim() != 2:
-        raise ValueError("X must be [n] or [rows, n]")
-    xd = x.to(torch.float64).contiguous()
-    valid = (~torch.isnan(xd)).sum(dim=1)
-    if bool((valid < 2).any()):         # scipy.interpolate.interp1d needs two points
-        raise ValueError("x and y arrays must have at least 2 entries")
-    y = torch.empty_like(xd)
-    rows, n = xd.shape
-    with torch.cuda.device(xd.device):
-        _lib.check(_lib.load().mm_interp_nan_linear_f64(xd.data_ptr(), rows, n, n, y.data_ptr(), n,
-                                                         C.c_void_p(torch.cuda.current_stream(xd.device).cuda_stream)),
-                   "mm_interp_nan_linear_f64")
-    y = y.to(X.dtype)
-    return y[0] if squeeze else y
-
-
-def _interp_nan_host(X, method):
-    # script/calc.py:345-385 as written
-    import copy
-    newX = copy.copy(X)
-    mynans = np.isnan(newX)
-    if np.sum(mynans) == 0:
-        return newX
-    justnans = np.empty(np.size(X))
-    justnans[:] = np.nan
-    if method == "pchip":
-        if np.argwhere(mynans)[0] == 0:
-            newX[0] = newX[np.argwhere(np.isnan(newX) == 0)[0]]
-        if np.argwhere(mynans)[-1] == len(X) - 1:
-            newX[-1] = newX[np.argwhere(np.isnan(newX) == 0)[-1]]
-        mynans = np.isnan(newX)
-        f = interpolate.PchipInterpolator(np.where(mynans == 0)[0], newX[mynans == 0], extrapolate=False)
-    else:
-        f = interpolate.interp1d(np.where(mynans == 0)[0], newX[mynans == 0], method, fill_value="extrapolate")
-    justnans[mynans] = f(np.squeeze(np.where(mynans)))
-    newX[mynans] = justnans[mynans]
-    return newX
-
-
-INTERP_SEGMENT = 1024       # samples per workgroup of the segmented interp_NAN kernels (kIpSeg of csrc/mm_interp.hip)
-# interp_NAN methods of mm_interp_nan_f64 (MM_INTERP_* of include/modmfcc.h)
-_INTERP_KINDS = {"pchip": 0, "nearest": 1, "nearest-up": 2, "previous": 3, "next": 4, "zero": 5, "slinear": 6}
-_INTERP_HOST_KINDS = ("quadratic", "cubic")     # a banded solve over all knots: scipy on the host
-
-
-def _interp_kind_device(X, method):
-    import torch
-    from . import _lib
-    kind = _INTERP_KINDS[method]
-    squeeze = X.dim() == 1
-    x = X.unsqueeze(0) if squeeze else X
-    if x.dim() != 2:
-        raise ValueError("X must be [n] or [rows, n]")
-    if not x.is_floating_point():
-        raise TypeError("X must be a floating-point tensor")
-    rows, n = x.shape
-    if rows == 0 or n == 0:
-        return X.clone()
-    xd = x.to(torch.float64)
-    if xd.stride(1) != 1 or xd.stride(0) < n:
-        xd = xd.contiguous()
-    fewest = int((~torch.isnan(xd)).sum(dim=1).min())   # the one read-back: what scipy would raise for
-    if fewest == n:
-        return X.clone()
-    if method == "slinear" and fewest < 2:
-        raise ValueError("x and y arrays must have at least 2 entries")
-    if fewest < 1:
-        if method == "pchip":                            # the reference's np.argwhere(...)[0] of an empty array
-            raise IndexError("index 0 is out of bounds for axis 0 with size 0")
-        raise ValueError("cannot reshape array of size 0 into shape (0,newaxis)")     # scipy interp1d of empty x
-    y = torch.empty((rows, n), dtype=torch.float64, device=xd.device)
-    lib = _lib.load()
-    with torch.cuda.device(xd.device):
-        ws = torch.empty(int(lib.mm_interp_nan_workspace_bytes(kind, rows, n)), dtype=torch.uint8, device=xd.device)
-        _lib.check(lib.mm_interp_nan_f64(kind, xd.data_ptr(), rows, n, xd.stride(0), y.data_ptr(), n, ws.data_ptr(),
-                                         ws.numel(), C.c_void_p(torch.cuda.current_stream(xd.device).cuda_stream)),
-                   "mm_interp_nan_f64")
-    y = y.to(X.dtype)
-    return y[0] if squeeze else y
-
-
-def interp_nan_batch(x, method: str = "linear"):
-    """interp_NAN along the last axis of a CUDA(HIP) tensor [n] or [rows, n] of any float dtype, on the device only:
-    computed in float64 and cast back.  ``method``: 'linear' (mm_interp_nan_linear_f64) or one of 'pchip', 'nearest',
-    'nearest-up', 'previous', 'next', 'zero', 'slinear' (mm_interp_nan_f64; rows are cut into segments of INTERP_SEGMENT
-    samples, one workgroup each).  'quadratic' and 'cubic' need a solve over all knots: NotImplementedError here
-    (interp_NAN runs them through scipy on the host); any other name is a ValueError.  Rows with too few valid samples
-    raise what the reference raises (interp_NAN's doc string), after one read-back of the smallest count."""
-    if not ragged.is_device_tensor(x):
-        raise TypeError("interp_nan_batch takes a CUDA(HIP) tensor; interp_NAN also takes numpy curves")
-    if method == "linear":
-        return _interp_linear_device(x)
-    if method in _INTERP_KINDS:
-        return _interp_kind_device(x, method)
-    if method in _INTERP_HOST_KINDS:
-        raise NotImplementedError(f"method={method!r} needs a banded solve over all knots; not on the device")
-    raise ValueError(f"interp_nan_batch: unknown method {method!r}")
-
-
-def interp_nan_ragged_batch(x, counts, method: str = "linear"):
-    """interp_nan_batch with a count per row: ``x`` [rows, n_max] on the device, ``counts`` [rows] (host integers,
-    validated: ValueError outside [1, n_max]; or an int64 device tensor, clamped by the kernels) -> [rows, n_max] of x's
-    dtype.  Row b holds interp_nan_batch(x[b, :counts[b]], method) in the columns [0, counts[b]) and zeros behind them;
-    what x holds behind a row's count never matters.  The methods and the errors are interp_nan_batch's, the errors taken
-    from the smallest number of valid samples below a row's count, in one read-back."""
-    import torch
-    from . import _lib
-    xd = ragged.device_rows(x, (torch.float64,), "interp_nan_ragged_batch takes a CUDA(HIP) tensor", "x must be [rows, n_max]",
-                            widen=torch.float64, nonempty=False)
-    if method != "linear" and method not in _INTERP_KINDS:
-        if method in _INTERP_HOST_KINDS:
-            raise NotImplementedError(f"method={method!r} needs a banded solve over all knots; not on the device")
-        raise ValueError(f"interp_nan_ragged_batch: unknown method {method!r}")
-    if not x.is_floating_point():
-        raise TypeError("x must be a floating-point tensor")
-    rows, n = x.shape
-    if rows == 0 or n == 0:
-        return x.clone()
-    dev = x.device
-    cnt = ragged.check_counts(counts, rows, n, dev, "counts")
-    pitch_ = ragged.row_pitch(xd)
-    with torch.cuda.device(dev):
-        cd = ragged.counts_on_device(cnt, dev)
-        c = cd.clamp(1, n)
-        valid = ((~torch.isnan(xd)) & (torch.arange(n, device=dev)[None, :] < c[:, None])).sum(dim=1)
-        if method == "linear":                              # scipy.interpolate.interp1d needs two points, NaN or not
-            if int(valid.min()) < 2:
-                raise ValueError("x and y arrays must have at least 2 entries")
-        else:                                               # a row without a NaN below its count is returned as it is
-            fewest = int(torch.where(valid < c, valid, torch.full_like(valid, 2)).min())
-            if method == "slinear" and fewest < 2:
-                raise ValueError("x and y arrays must have at least 2 entries")
-            if fewest < 1:
-                if method == "pchip":
-                    raise IndexError("index 0 is out of bounds for axis 0 with size 0")
-                raise ValueError("cannot reshape array of size 0 into shape (0,newaxis)")
-        y = torch.empty((rows, n), dtype=torch.float64, device=dev)
-        lib = _lib.load()
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        if method == "linear":
-            _lib.check(lib.mm_interp_nan_linear_ragged_f64(xd.data_ptr(), rows, n, pitch_, cd.data_ptr(), y.data_ptr(), n,
-                                                           stream), "mm_interp_nan_linear_ragged_f64")
-        else:
-            kind = _INTERP_KINDS[method]
-            ws = torch.empty(int(lib.mm_interp_nan_workspace_bytes(kind, rows, n)), dtype=torch.uint8, device=dev)
-            _lib.check(lib.mm_interp_nan_ragged_f64(kind, xd.data_ptr(), rows, n, pitch_, cd.data_ptr(), y.data_ptr(), n,
-                                                    ws.data_ptr(), ws.numel(), stream), "mm_interp_nan_ragged_f64")
-    return y.to(x.dtype)
-
-
-SPLINE_CHUNK = 1024         # knots per workgroup of the spline solve (kSpChunk of csrc/mm_spline.hip): longer rows are cut
-# interp_NAN methods of mm_interp_spline_f64 (MM_SPLINE_* of include/modmfcc_spline.h): the kind is the spline's degree
-_SPLINE_KINDS = {"quadratic": 2, "cubic": 3}
-_MSG_SPLINE_FEW = "The number of derivatives at boundaries does not match: expected {}, got 0+0"   # make_interp_spline's
-
-
-def _spline_kind(method, who):
-    if method not in _SPLINE_KINDS:
-        raise ValueError(f"{who}: method must be 'quadratic' or 'cubic', got {method!r}")
-    return _SPLINE_KINDS[method]
-
-
-def _spline_refuse(kind, fewest):
-    """scipy's ValueError for the row with the fewest valid samples among the rows that have a NaN."""
-    if fewest < 1:
-        raise ValueError("cannot reshape array of size 0 into shape (0,newaxis)")          # scipy interp1d of empty x
-    if fewest <= kind:
-        raise ValueError(_MSG_SPLINE_FEW.format(kind + 1 - fewest))
-
-
-def interp_nan_spline_batch(x, method: str = "cubic"):
-    """interp_NAN's 'quadratic' and 'cubic' kinds along the last axis of a CUDA(HIP) tensor [n] or [rows, n] of any float
-    dtype, on the device only (mm_interp_spline_f64): computed in float64 and cast back.  scipy's
-    interp1d(valid indices, valid values, method, fill_value='extrapolate') at the NaN samples -- the not-a-knot cubic
-    spline, the quadratic spline with its knots at the midpoints -- within a few of scipy's own roundings, not bit for
-    bit; samples before the first and behind the last valid one are extrapolated with the end pieces.  The valid samples
-    of a row are compacted by rank, the tridiagonal system of a row is solved in LDS, in chunks of SPLINE_CHUNK knots
-    for a longer row.  A row without a NaN is returned as it is; a row with a NaN and fewer than 3 ('quadratic') or 4
-    ('cubic') valid samples raises scipy's ValueError, after one read-back of the smallest count.  Another method name
-    is a ValueError, a host array a TypeError.  interp_NAN and interp_nan_batch do not route here."""
-    import torch
-    from . import _lib
-    kind = _spline_kind(method, "interp_nan_spline_batch")
-    if not ragged.is_device_tensor(x):
-        raise TypeError("interp_nan_spline_batch takes a CUDA(HIP) tensor")
-    squeeze = x.dim() == 1
-    xs = x.unsqueeze(0) if squeeze else x
-    if xs.dim() != 2:
-        raise ValueError("x must be [n] or [rows, n]")
-    if not xs.is_floating_point():
-        raise TypeError("x must be a floating-point tensor")
-    rows, n = xs.shape
-    if rows == 0 or n == 0:
-        return x.clone()
-    xd = xs.to(torch.float64)
-    if xd.stride(1) != 1 or xd.stride(0) < n:
-        xd = xd.contiguous()
-    fewest = int((~torch.isnan(xd)).sum(dim=1).min())   # the one read-back: what scipy would raise for
-    if fewest == n:
-        return x.clone()
-    _spline_refuse(kind, fewest)
-    y = torch.empty((rows, n), dtype=torch.float64, device=xd.device)
-    lib = _lib.load()
-    with torch.cuda.device(xd.device):
-        ws = torch.empty(int(lib.mm_interp_spline_workspace_bytes(kind, rows, n)), dtype=torch.uint8, device=xd.device)
-        _lib.check(lib.mm_interp_spline_f64(kind, xd.data_ptr(), rows, n, ragged.row_pitch(xd), y.data_ptr(), n, ws.data_ptr(),
-                                            ws.numel(), C.c_void_p(torch.cuda.current_stream(xd.device).cuda_stream)),
-                   "mm_interp_spline_f64")
-    y = y.to(x.dtype)
-    return y[0] if squeeze else y
-
-
-def interp_nan_spline_ragged_batch(x, counts, method: str = "cubic"):
-    """interp_nan_spline_batch with a count per row: ``x`` [rows, n_max] on the device, ``counts`` [rows] (host integers,
-    validated: ValueError outside [1, n_max]; or an int64 device tensor, clamped by the kernels) -> [rows, n_max] of x's
-    dtype.  Row b holds interp_nan_spline_batch(x[b, :counts[b]], method) in the columns [0, counts[b]), bit for bit, and
-    zeros behind them; what x holds behind a row's count never matters.  The errors are interp_nan_spline_batch's, taken
-    from the smallest number of valid samples below a row's count, in one read-back."""
-    import torch
-    from . import _lib
-    kind = _spline_kind(method, "interp_nan_spline_ragged_batch")
-    xd = ragged.device_rows(x, (torch.float64,), "interp_nan_spline_ragged_batch takes a CUDA(HIP) tensor",
-                            "x must be [rows, n_max]", widen=torch.float64, nonempty=False)
-    if not x.is_floating_point():
-        raise TypeError("x must be a floating-point tensor")
-    rows, n = x.shape
-    if rows == 0 or n == 0:
-        return x.clone()
-    dev = x.device
-    cnt = ragged.check_counts(counts, rows, n, dev, "counts")
-    with torch.cuda.device(dev):
-        cd = ragged.counts_on_device(cnt, dev)
-        c = cd.clamp(1, n)
-        valid = ((~torch.isnan(xd)) & (torch.arange(n, device=dev)[None, :] < c[:, None])).sum(dim=1)
-        # a row without a NaN below its count is returned as it is, however few samples it has
-        _spline_refuse(kind, int(torch.where(valid < c, valid, torch.full_like(valid, kind + 1)).min()))
-        y = torch.empty((rows, n), dtype=torch.float64, device=dev)
-        lib = _lib.load()
-        ws = torch.empty(int(lib.mm_interp_spline_workspace_bytes(kind, rows, n)), dtype=torch.uint8, device=dev)
-        _lib.check(lib.mm_interp_spline_ragged_f64(kind, xd.data_ptr(), rows, n, ragged.row_pitch(xd), cd.data_ptr(),
-                                                   y.data_ptr(), n, ws.data_ptr(), ws.numel(),
-                                                   C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                   "mm_interp_spline_ragged_f64")
-    return y.to(x.dtype)
-
-
-def interp_NAN(X, method: str = "linear"):
-    """script/calc.py:345-385: NaN samples of a curve filled by interpolation.  'linear' (scipy interp1d, extrapolated at
-    the ends) runs on the device (mm_interp_nan_linear_f64) for numpy curves and CUDA(HIP) tensors ([n] or [rows, n]).
-    A CUDA(HIP) tensor stays on the device for 'pchip' (PchipInterpolator after the reference's end fix), 'nearest',
-    'nearest-up', 'previous', 'next', 'zero' and 'slinear' too (interp_nan_batch, mm_interp_nan_f64); only 'quadratic' and
-    'cubic', which solve a banded system over all knots, take a device tensor through scipy on the host and back.  A
-    numpy curve with any method but 'linear' runs the reference's own scipy calls.  On the device a row without a valid
-    sample raises IndexError under 'pchip' and scipy's ValueError for empty input otherwise; 'linear' and 'slinear' need
-    two valid samples (ValueError)."""
-    if method == "linear":
-        if ragged.is_device_tensor(X):
-            return _interp_linear_device(X)
-        a = np.asarray(X)
-        if np.sum(np.isnan(a)) == 0:
-            return a.copy()
-        import torch
-        y = _interp_linear_device(torch.from_numpy(np.ascontiguousarray(a)).to(_gpu()))
-        return y.cpu().numpy()
-    if ragged.is_device_tensor(X):
-        if method in _INTERP_KINDS:
-            return _interp_kind_device(X, method)
-        import torch
-        rows = X.cpu().numpy()
-        out = _interp_nan_host(rows, method) if rows.ndim == 1 else np.stack([_interp_nan_host(r, method) for r in rows])
-        return torch.from_numpy(np.ascontiguousarray(out)).to(X.device)
-    return _interp_nan_host(X, method)
-
-
 _MSG_GAPS = inspect.cleandoc("""Post processing filters should be applied (outFiltes is not None) \
         but unvoiced regions are not interpolated (interpUnvoiced is None).
         Cannot filter f0 signal with gaps due to unvoiced regions""")

@@ -14,6 +14,14 @@ def is_device_tensor(x):
     return type(x).__module__.startswith("torch") and getattr(x, "is_cuda", False)
 
 
+def gpu():
+    """The current device, where host data goes (numpy curves, files read from disk)."""
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("modulation_mfcc_amd needs an AMD GPU (gfx950); there is no CPU fallback")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
 # ---- counts: one integer per row ------------------------------------------------------------------------------------
 def check_counts(x, batch, hi, device, what):
     """One integer count per clip, in [1, hi]: host values validated -> int64 numpy array; an int64 tensor on `device`

@@ -25,7 +25,7 @@ assert np.finfo(np.longdouble).eps < 1e-18, "np.longdouble is no wider than floa
 METHODS = ("quadratic", "cubic")
 DEGREE = {"quadratic": 2, "cubic": 3}
 FLOOR, MARGIN, CEILING = 1e-12, 16.0, 1e-10
-S = 1024                    # pitch.INTERP_SEGMENT = pitch.SPLINE_CHUNK
+S = 1024                    # interp.INTERP_SEGMENT = interp.SPLINE_CHUNK
 
 
 def recipe(x, method):

@@ -883,11 +883,11 @@ def interp_case(kind, ragged, rows=4, n=2500):
         return d
 
     def setup(env):
-        from modulation_mfcc_amd import pitch
+        from modulation_mfcc_amd import interp
         L, lib = _lib()
         x = env.buf["x"]
         y = env.out((rows, n), torch.float64)
-        code = 0 if lin else pitch._INTERP_KINDS[kind]
+        code = 0 if lin else interp._INTERP_KINDS[kind]
         ws = env.work(lib.mm_interp_nan_workspace_bytes(code, rows, n))
         cnt = env.buf.get("counts")
 
@@ -913,13 +913,13 @@ for _r in (False, True):
 
 
 def interp_wrapper_case(rows=4, n=2500):
-    """pitch.interp_nan_ragged_batch with an int64 device tensor of counts.  Its documentation announces ONE read-back (the
+    """interp.interp_nan_ragged_batch with an int64 device tensor of counts.  Its documentation announces ONE read-back (the
     smallest number of valid samples below a row's count, for the reference's errors): the call waits for its stream."""
     name = "interp_nan_ragged_batch/pchip"
 
     def setup(env):
-        from modulation_mfcc_amd import pitch
-        return lambda: pitch.interp_nan_ragged_batch(env.buf["x"], env.buf["counts"], "pchip")
+        from modulation_mfcc_amd import interp
+        return lambda: interp.interp_nan_ragged_batch(env.buf["x"], env.buf["counts"], "pchip")
     add(name, "mm_interp_nan_ragged_f64", "interp", lambda: {"x": _gap_sets(name, rows, n), "counts": length_sets(rows, n, 3)}, setup,
         ragged=True, host_sync="interp_nan_ragged_batch: 'the errors taken from the smallest number of valid samples below a "
                                "row's count, in one read-back'")

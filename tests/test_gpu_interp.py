@@ -12,12 +12,12 @@ from scipy import interpolate
 
 import pyin_oracle as O
 from test_interp_host import KINDS, write_pos
-from modulation_mfcc_amd import (pitch, get_f0, interp_NAN, interp_nan_batch, read_AG50x_arrays, velocity_batch,
+from modulation_mfcc_amd import (interp, get_f0, interp_NAN, interp_nan_batch, read_AG50x_arrays, velocity_batch,
                                  find_peaks_batch, peaks_to_list)
 
 pytestmark = pytest.mark.gpu
 
-S = pitch.INTERP_SEGMENT
+S = interp.INTERP_SEGMENT
 COPYING = ("nearest", "nearest-up", "previous", "next", "zero")
 NAN = np.nan
 
@@ -87,7 +87,7 @@ def test_device_tensor_never_goes_through_the_host(gpu, monkeypatch):
 
     def boom(*a, **k):
         raise AssertionError("interp_NAN took a device tensor to the host")
-    monkeypatch.setattr(pitch, "_interp_nan_host", boom)
+    monkeypatch.setattr(interp, "_interp_nan_host", boom)
     for method in KINDS:
         got = interp_NAN(_dev(x, gpu), method)
         assert isinstance(got, torch.Tensor) and got.device.type == "cuda" and got.dtype == torch.float64
@@ -417,3 +417,29 @@ def test_position_velocity_peak_chain_on_the_device(gpu, tmp_path):
         want = scipy.signal.find_peaks(-vel.cpu().numpy() if negate else vel.cpu().numpy())[0]
         assert len(want) > 5
         np.testing.assert_array_equal(got, want)
+
+
+def test_all_ten_methods_a_row_alone_in_a_batch_and_under_full_counts_are_the_same_bits(gpu):
+    """Every method of the table on a [3, 1030] float64 batch (a segment border; two chunks of the spline solve) with gaps
+    at both ends: interp_nan_batch / interp_nan_spline_batch of a row alone is the row inside the batch, and both are the
+    ragged call with full counts, host and device, bit for bit.  (The comparisons with scipy are the tests above, in
+    test_gpu_pitch.py and in test_gpu_spline.py.)"""
+    from modulation_mfcc_amd import (interp_nan_ragged_batch, interp_nan_spline_batch, interp_nan_spline_ragged_batch)
+    n = S + 6
+    rows = np.stack([_nan_curve(n, 2 + s, 3 + 2 * s, seed=40 + s) for s in range(3)])
+    assert np.isnan(rows[:, 0]).all() and np.isnan(rows[:, -1]).all()
+
+    def same(a, b):                                           # (NaN for NaN: 'previous' and 'next' leave one end unfilled)
+        return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.view(torch.int64), b.view(torch.int64))
+    x = _dev(rows, gpu)
+    assert sorted(interp._METHODS) == sorted(("linear",) + tuple(KINDS) + ("quadratic", "cubic"))
+    for method, m in interp._METHODS.items():
+        alone, ragged = ((interp_nan_spline_batch, interp_nan_spline_ragged_batch) if m.family is interp._SPLINE else
+                         (interp_nan_batch, interp_nan_ragged_batch))
+        batch = alone(x, method)
+        assert batch.shape == (3, n) and batch.dtype == torch.float64, method
+        assert torch.equal(batch[~torch.isnan(x)], x[~torch.isnan(x)]), method
+        for r in range(3):
+            assert same(alone(x[r], method), batch[r]), (method, r)
+        assert same(ragged(x, [n] * 3, method), batch), method
+        assert same(ragged(x, torch.full((3,), n, dtype=torch.int64, device=gpu), method), batch), method

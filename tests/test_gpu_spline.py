@@ -94,8 +94,8 @@ def test_rows_without_gaps_come_back_as_they_are(gpu, method):
 @pytest.mark.parametrize("method", O.METHODS)
 @pytest.mark.parametrize("K", O.KNOT_COUNTS)
 def test_knot_counts_around_the_chunk_size(gpu, K, method):
-    from modulation_mfcc_amd import pitch
-    assert pitch.SPLINE_CHUNK == SEG
+    from modulation_mfcc_amd import interp
+    assert interp.SPLINE_CHUNK == SEG
     name = f"knots-{K}"
     assert (~np.isnan(O.fixture(name))).sum() == K
     O.check(fill(O.fixture(name), method, gpu), name, method)
@@ -299,9 +299,9 @@ def _ctypes_case(method, ragged):
 
     def setup(env):
         import torch
-        from modulation_mfcc_amd import _lib, pitch
+        from modulation_mfcc_amd import _lib, interp
         lib = _lib.load()
-        kind = pitch._SPLINE_KINDS[method]
+        kind = interp._SPLINE_KINDS[method]
         x = env.buf["x"]
         y = env.out((S_ROWS, S_N), torch.float64)
         need = int(lib.mm_interp_spline_workspace_bytes(kind, S_ROWS, S_N))
@@ -338,8 +338,8 @@ def stream_session(gpu):
 def test_the_stream_cases_are_not_in_the_registry():
     assert not {c.name for c in S.CASES} & {c.name for c in STREAM_CASES}
     assert {c.entry for c in STREAM_CASES} == {"mm_interp_spline_f64", "mm_interp_spline_ragged_f64"}
-    from modulation_mfcc_amd import pitch
-    assert READ_BACK.split("'")[1] in " ".join(pitch.interp_nan_spline_ragged_batch.__doc__.split())
+    from modulation_mfcc_amd import interp
+    assert READ_BACK.split("'")[1] in " ".join(interp.interp_nan_spline_ragged_batch.__doc__.split())
 
 
 @pytest.mark.parametrize("case", STREAM_CASES, ids=lambda c: c.name)

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import pyin_oracle as O
-from modulation_mfcc_amd import _lib, get_f0, get_f0_batch, pitch, pyin_ragged_frames
+from modulation_mfcc_amd import _lib, get_f0, get_f0_batch, interp, pitch, pyin_ragged_frames
 from modulation_mfcc_amd.plan import check_lengths
 
 C5 = dict(frame_length=512, hop_length=40, fmin=100, fmax=500)
@@ -111,7 +111,7 @@ def test_host_lengths_are_validated():
     with pytest.raises(TypeError):
         pitch.pyin_ragged_batch(np.zeros((2, 4000), np.float32), [4000, 1], C5_SR, **C5)
     with pytest.raises(TypeError):
-        pitch.interp_nan_ragged_batch(np.zeros((2, 40)), [40, 1])
+        interp.interp_nan_ragged_batch(np.zeros((2, 40)), [40, 1])
 
 
 def test_get_f0_batch_carries_get_f0s_keywords_and_refusals():
@@ -130,5 +130,6 @@ def test_get_f0_batch_carries_get_f0s_keywords_and_refusals():
         get_f0_batch(y, 16000, method="pyin", interpUnvoiced=None)
     for name in ("pyin_ragged_batch", "pyin_ragged_frames", "interp_nan_ragged_batch", "get_f0_batch"):
         assert name in pitch.__all__
+    assert "interp_nan_ragged_batch" in interp.__all__
     keys = lambda f: [p.name for p in inspect.signature(f).parameters.values() if p.kind == inspect.Parameter.KEYWORD_ONLY]
     assert keys(pitch.pyin_ragged_batch) == keys(pitch.pyin_batch)

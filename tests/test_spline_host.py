@@ -11,7 +11,7 @@ from scipy.interpolate import CubicSpline, PchipInterpolator, make_interp_spline
 
 import spline_oracle as O
 from conftest import ROOT
-from modulation_mfcc_amd import _lib, pitch
+from modulation_mfcc_amd import _lib, interp
 
 HEADER = os.path.join(ROOT, "include", "modmfcc_spline.h")
 
@@ -42,7 +42,7 @@ def test_every_symbol_of_the_fourth_header_is_exported_and_bound():
     assert lib.mm_version() == 123
     txt = open(HEADER).read()
     assert re.search(r"MM_SPLINE_QUADRATIC\s*=\s*2\s*,\s*MM_SPLINE_CUBIC\s*=\s*3", txt)
-    assert (_lib.MM_SPLINE_QUADRATIC, _lib.MM_SPLINE_CUBIC) == (2, 3) and pitch._SPLINE_KINDS == {"quadratic": 2, "cubic": 3}
+    assert (_lib.MM_SPLINE_QUADRATIC, _lib.MM_SPLINE_CUBIC) == (2, 3) and interp._SPLINE_KINDS == {"quadratic": 2, "cubic": 3}
 
 
 def test_the_unit_is_in_both_builds():
@@ -51,7 +51,7 @@ def test_the_unit_is_in_both_builds():
     assert re.search(r"^TUS\s*:=.*\bmm_spline\b", mk, flags=re.M) and re.search(r"^HDRS\s*:=.*modmfcc_spline\.h", mk, flags=re.M)
     assert '#include "mm_spline.hip"' in open(os.path.join(csrc, "mm_unity.hip")).read()
     src = open(os.path.join(csrc, "mm_spline.hip")).read()
-    assert f"kSpChunk = {pitch.SPLINE_CHUNK};" in src and '#include "mm_interp_seg.hip.inc"' in src
+    assert f"kSpChunk = {interp.SPLINE_CHUNK};" in src and '#include "mm_interp_seg.hip.inc"' in src
     assert '#include "mm_interp_seg.hip.inc"' in open(os.path.join(csrc, "mm_interp.hip")).read()
 
 
@@ -110,10 +110,10 @@ def test_the_workspace_size_is_monotone_and_the_largest_n_has_one():
 # ---- Python, without a device ---------------------------------------------------------------------------------------------------
 def test_the_names_are_exported():
     import modulation_mfcc_amd as M
-    assert M.interp_nan_spline_batch is pitch.interp_nan_spline_batch
-    assert M.interp_nan_spline_ragged_batch is pitch.interp_nan_spline_ragged_batch
-    assert pitch.SPLINE_CHUNK == 1024 == O.S == pitch.INTERP_SEGMENT
-    assert pitch._INTERP_HOST_KINDS == ("quadratic", "cubic")         # the old route keeps them
+    assert M.interp_nan_spline_batch is interp.interp_nan_spline_batch
+    assert M.interp_nan_spline_ragged_batch is interp.interp_nan_spline_ragged_batch
+    assert interp.SPLINE_CHUNK == 1024 == O.S == interp.INTERP_SEGMENT
+    assert interp._INTERP_HOST_KINDS == ("quadratic", "cubic")         # the old route keeps them
 
 
 def test_python_refusals():
@@ -121,15 +121,15 @@ def test_python_refusals():
     x = np.ones(10)
     for m in ("linear", "pchip", "slinear", "spline", ""):
         with pytest.raises(ValueError, match="'quadratic' or 'cubic'"):
-            pitch.interp_nan_spline_batch(x, m)
+            interp.interp_nan_spline_batch(x, m)
         with pytest.raises(ValueError, match="'quadratic' or 'cubic'"):
-            pitch.interp_nan_spline_ragged_batch(x, [10], m)
+            interp.interp_nan_spline_ragged_batch(x, [10], m)
     for m in O.METHODS:
         for host in (x, torch.ones(10, dtype=torch.float64)):
             with pytest.raises(TypeError, match="CUDA"):
-                pitch.interp_nan_spline_batch(host, m)
+                interp.interp_nan_spline_batch(host, m)
             with pytest.raises(TypeError, match="CUDA"):
-                pitch.interp_nan_spline_ragged_batch(host.reshape(1, 10), [10], m)
+                interp.interp_nan_spline_ragged_batch(host.reshape(1, 10), [10], m)
 
 
 def test_the_error_texts_are_scipys():
@@ -141,9 +141,9 @@ def test_the_error_texts_are_scipys():
             with pytest.raises(ValueError) as e:
                 O.recipe(x, m)
             with pytest.raises(ValueError) as mine:
-                pitch._spline_refuse(k, v)
+                interp._spline_refuse(k, v)
             assert str(mine.value) == str(e.value), (m, v)
-        pitch._spline_refuse(k, k + 1)
+        interp._spline_refuse(k, k + 1)
         assert not np.isnan(O.recipe(O.chosen(50, k + 1), m)).any()
 
 

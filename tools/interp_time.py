@@ -1,6 +1,6 @@
 """interp_NAN timing (GPU box): interp_NAN(device tensor, 'pchip') on the device (mm_interp_nan_f64) against the host
 round trip it replaces -- the curve copied to the host, scipy's PchipInterpolator row by row in a Python loop
-(pitch._interp_nan_host, unchanged), the result copied back -- on [1024, 1000] float64 (a batch of ten-second f0 curves at
+(interp._interp_nan_host, unchanged), the result copied back -- on [1024, 1000] float64 (a batch of ten-second f0 curves at
 the 10 ms step) and on [1, 300001] (a five-minute recording at the 1 ms step).  Both are timed with device events around
 the whole call, alternating in one process; the results are compared before anything is timed.  'linear' and 'nearest'
 are timed on the device beside them.
@@ -33,9 +33,9 @@ def f0_like(rows, n, seed):
 def host_round_trip(X, method):
     """What interp_NAN did with a device tensor for every method but 'linear' before mm_interp_nan_f64 existed."""
     import torch
-    from modulation_mfcc_amd import pitch
+    from modulation_mfcc_amd import interp
     rows = X.cpu().numpy()
-    out = pitch._interp_nan_host(rows, method) if rows.ndim == 1 else np.stack([pitch._interp_nan_host(r, method) for r in rows])
+    out = interp._interp_nan_host(rows, method) if rows.ndim == 1 else np.stack([interp._interp_nan_host(r, method) for r in rows])
     return torch.from_numpy(np.ascontiguousarray(out)).to(X.device)
 
 

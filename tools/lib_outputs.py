@@ -10,7 +10,10 @@ matrix-pipe kernel.  n_fft 512, 16 kHz, win 400, 40 mel / 13 MFCC unless said ot
 Case set `tail`: every kernel of mm_tail.hip and its includes (tail_cases).
 Case set `ragged`: every public *_ragged_batch function with host and with device lengths, and the four list front ends
 (ragged_cases) -- for a change of the host code, run on two checkouts with the same library.
-Case set `welch`: every instantiation and path of the Welch power and cross spectrum kernels (welch_cases)."""
+Case set `welch`: every instantiation and path of the Welch power and cross spectrum kernels (welch_cases).
+Case set `gapfill`: every interp_NAN kind through the five gap-filling calls -- shapes, types, layouts, rows with too few valid
+samples, counts, host inputs, get_f0 / get_f0_batch -- with every refusal's type and text (gapfill_cases); for a change of
+the host code, run on two checkouts with the same library as well."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -362,7 +365,138 @@ def welch_cases():
     return out
 
 
-CASESETS = {"s16": s16_cases, "tail": tail_cases, "ragged": ragged_cases, "welch": welch_cases}
+GAP_METHODS = ("linear", "pchip", "nearest", "nearest-up", "previous", "next", "zero", "slinear", "quadratic", "cubic", "akima")
+GAP_SOME = ("linear", "pchip", "cubic")
+
+
+def gap_rows(seed, rows, n):
+    """A random walk per row with a third of its samples NaN, a gap before the first and behind the last valid sample."""
+    rng = np.random.default_rng(seed)
+    x = np.cumsum(rng.standard_normal((rows, n)), axis=1)
+    if n > 8:
+        x[rng.random((rows, n)) < 0.3] = np.nan
+        x[:, 2:7] = rng.standard_normal((rows, 5))          # five valid samples whatever was drawn
+        x[:, :2] = np.nan
+        x[:, n - 3:] = np.nan
+    else:
+        x[:, 0] = np.nan
+        x[:, n - 1] = np.nan
+    return x
+
+
+def gapfill_cases():
+    """Case set `gapfill`: every interp_NAN kind through the five gap-filling calls, what they return and what they
+    refuse with.  Only names the package exports, so that the same code runs on an older checkout."""
+    import torch
+    import modulation_mfcc_amd as M
+    dev = torch.device("cuda", 0)
+    out = {}
+
+    def keep(name, call):
+        """the call's result (a tensor, an array, or get_f0's pairs); a refusal is kept as its type and text"""
+        try:
+            r = call()
+            parts = [a for pair in r for a in pair] if isinstance(r, list) else list(r) if isinstance(r, tuple) else [r]
+            for k, a in enumerate(parts):
+                out["%s.%d" % (name, k)] = a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        except Exception as e:
+            out[name + ".error"] = np.frombuffer(("%s: %s" % (type(e).__name__, e)).encode(), dtype=np.uint8)
+
+    def every_call(name, x, counts, methods):
+        """the five calls on one tensor; the ragged ones (two dimensions only) with host and with device counts"""
+        for m in methods:
+            keep("%s.NAN.%s" % (name, m), lambda: M.interp_NAN(x, m))
+            keep("%s.batch.%s" % (name, m), lambda: M.interp_nan_batch(x, m))
+            keep("%s.spline.%s" % (name, m), lambda: M.interp_nan_spline_batch(x, m))
+            if counts is not None:
+                for where, c in (("host", list(counts)), ("dev", torch.tensor(list(counts), dtype=torch.int64, device=dev))):
+                    keep("%s.ragged.%s.%s" % (name, where, m), lambda: M.interp_nan_ragged_batch(x, c, m))
+                    keep("%s.splragged.%s.%s" % (name, where, m), lambda: M.interp_nan_spline_ragged_batch(x, c, m))
+
+    def put(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+    # shapes and types: 1030 crosses a segment border and makes the spline solve take two chunks
+    for n in (5, 1024, 1025, 1030, 2100):
+        x = gap_rows(n, 3, n)
+        counts = (n, max(1, n // 2), max(1, n - 3))
+        for dt in (np.float64, np.float32):
+            name = "n%d.%s" % (n, np.dtype(dt).name)
+            every_call(name + ".rows", put(x.astype(dt)), counts, GAP_METHODS)
+            every_call(name + ".one", put(x[1].astype(dt)), None, GAP_METHODS)
+    # layouts: a wider row pitch, a non-unit inner stride; an integer tensor; no row, no column
+    x = gap_rows(77, 3, 1030)
+    wide = put(np.concatenate([x, np.zeros((3, 7))], axis=1))[:, :1030]
+    every_call("pitch", wide, (1030, 600, 1027), GAP_SOME)
+    every_call("stride", put(np.repeat(x, 2, axis=1))[:, ::2], (1030, 600, 1027), GAP_SOME)
+    every_call("stride.one", put(np.repeat(x[0], 2))[::2], None, GAP_SOME)
+    every_call("int64", torch.arange(60, device=dev).reshape(3, 20), (20, 7, 1), GAP_SOME)
+    every_call("int64.one", torch.arange(20, device=dev), None, GAP_SOME)
+    every_call("norow", torch.zeros((0, 7), dtype=torch.float64, device=dev), (), GAP_SOME)
+    every_call("nocolumn", torch.zeros((3, 0), dtype=torch.float64, device=dev), (1, 1, 1), GAP_SOME)
+    # rows with exactly v valid samples (v = 12: no NaN), alone and between two good rows; then the same below a count of
+    # 12 with valid samples behind it.  A clean row below a count of 2 has fewer samples than any kind with a NaN needs.
+    spots = (2, 5, 7, 9, 10)
+    good = gap_rows(5, 2, 20)
+    for v in (0, 1, 2, 3, 4, 12):
+        row = np.full(20, np.nan)
+        if v == 12:
+            row[:12] = np.arange(12) * 0.5 + 1.0
+        else:
+            row[list(spots[:v])] = 1.0 + np.arange(v) ** 2
+        every_call("few%d.one" % v, put(row[:12]), None, GAP_METHODS)
+        every_call("few%d.row" % v, put(row[None, :12]), (12,), GAP_METHODS)
+        every_call("few%d.batch" % v, put(np.stack([good[0, :12], row[:12], good[1, :12]])), (12, 12, 12), GAP_METHODS)
+        row[12:] = 3.0                                             # valid samples behind the count
+        if v == 12:
+            row[15] = np.nan
+        every_call("few%d.below" % v, put(np.stack([good[0], row, good[1]])), (20, 12, 20), GAP_METHODS)
+        every_call("few%d.below.row" % v, put(row[None, :]), (12,), GAP_METHODS)
+    clean = np.stack([good[0], np.r_[1.0, 2.0, np.full(18, np.nan)], good[1]])
+    every_call("clean2.below", put(clean), (20, 2, 20), GAP_METHODS)
+    every_call("clean1.below", put(clean), (20, 1, 20), GAP_METHODS)
+    # counts: host values out of range are refused, device values are clamped
+    x = put(gap_rows(9, 3, 40))
+    for m in GAP_SOME:
+        for name, c in (("zero", [0, 40, 40]), ("beyond", [40, 41, 40]), ("short", [40, 40]), ("float", [40.0, 40.0, 40.0])):
+            keep("counts.host.%s.%s" % (name, m), lambda: M.interp_nan_ragged_batch(x, c, m))
+            keep("counts.host.%s.spl.%s" % (name, m), lambda: M.interp_nan_spline_ragged_batch(x, c, m))
+        c = torch.tensor([0, 45, 30], dtype=torch.int64, device=dev)
+        keep("counts.dev.%s" % m, lambda: M.interp_nan_ragged_batch(x, c, m))
+        keep("counts.dev.spl.%s" % m, lambda: M.interp_nan_spline_ragged_batch(x, c, m))
+        keep("counts.dev.int32.%s" % m, lambda: M.interp_nan_ragged_batch(x, c.int(), m))
+    # host inputs: numpy curves into interp_NAN; host data into the device-only calls
+    curve = gap_rows(11, 1, 50)[0]
+    whole = np.cumsum(np.random.default_rng(12).standard_normal(50))
+    for m in GAP_SOME:
+        keep("numpy.gaps.%s" % m, lambda: M.interp_NAN(curve, m))
+        keep("numpy.whole.%s" % m, lambda: M.interp_NAN(whole, m))
+        keep("numpy.f32.%s" % m, lambda: M.interp_NAN(curve.astype(np.float32), m))
+        for name, h in (("numpy", curve[None, :]), ("cpu", torch.from_numpy(curve[None, :]))):
+            keep("host.%s.batch.%s" % (name, m), lambda: M.interp_nan_batch(h, m))
+            keep("host.%s.ragged.%s" % (name, m), lambda: M.interp_nan_ragged_batch(h, [50], m))
+            keep("host.%s.spline.%s" % (name, m), lambda: M.interp_nan_spline_batch(h, m))
+            keep("host.%s.splragged.%s" % (name, m), lambda: M.interp_nan_spline_ragged_batch(h, [50], m))
+    # end to end: two short clips with a silent stretch (unvoiced frames), one numpy, one on the device
+    sig = [clips(80 + i, 1, n, 16000)[0].astype(np.float64) for i, n in enumerate((4000, 3100))]
+    for s in sig:
+        s[len(s) // 3:len(s) // 2] *= 1e-4
+        s[:200] *= 1e-4
+    lst = [sig[0], torch.from_numpy(sig[1].astype(np.float32)).to(dev)]
+    kw = dict(method="pyin", hopSize=0.002, minPitch=100, maxPitch=500, pyinframe_length=512)
+    for m in (None,) + GAP_SOME:
+        filt = dict(outFilter=None) if m is None else dict(outFilter="iir", outFiltCutOff=[10])
+        keep("f0.batch.%s" % m, lambda: M.get_f0_batch(lst, 16000, interpUnvoiced=m, **filt, **kw))
+        keep("f0.batch.nofilter.%s" % m, lambda: M.get_f0_batch(lst, 16000, interpUnvoiced=m, outFilter=None, **kw))
+        for i, s in enumerate(lst):
+            keep("f0.one%d.%s" % (i, m), lambda: M.get_f0(s, 16000, interpUnvoiced=m, **filt, **kw))
+            keep("f0.one%d.nofilter.%s" % (i, m), lambda: M.get_f0(s, 16000, interpUnvoiced=m, outFilter=None, **kw))
+    torch.cuda.synchronize()
+    print("%d results, %d of them refusals" % (len(out), sum(k.endswith(".error") for k in out)), flush=True)
+    return out
+
+
+CASESETS = {"s16": s16_cases, "tail": tail_cases, "ragged": ragged_cases, "welch": welch_cases, "gapfill": gapfill_cases}
 
 if __name__ == "__main__":
     if len(sys.argv) == 4 and sys.argv[1] == "--compare":

@@ -1,5 +1,5 @@
 """Spline gap filling timing (GPU box): interp_nan_spline_batch / interp_nan_spline_ragged_batch (mm_interp_spline_f64) against
-the route they replace -- the curves copied to the host, scipy's interp1d row by row (pitch._interp_nan_host, unchanged),
+the route they replace -- the curves copied to the host, scipy's interp1d row by row (interp._interp_nan_host, unchanged),
 the result copied back: what interp_NAN(device tensor, 'quadratic' | 'cubic') does -- and against
 interp_nan_batch(..., 'pchip') as the floor, on [1024, 1001] float64 f0-like rows, on the same rows ragged at 200 .. 1001
 samples, and on [1, 300001].  Every call is timed whole with device events (the wrappers' one read-back included),
@@ -16,14 +16,14 @@ from interp_time import f0_like
 
 def host_round_trip(X, method, counts=None):
     import torch
-    from modulation_mfcc_amd import pitch
+    from modulation_mfcc_amd import interp
     rows = X.cpu().numpy()
     if counts is None:
-        out = np.stack([pitch._interp_nan_host(r, method) for r in rows])
+        out = np.stack([interp._interp_nan_host(r, method) for r in rows])
     else:
         out = np.zeros_like(rows)
         for b, c in enumerate(counts):
-            out[b, :c] = pitch._interp_nan_host(rows[b, :c], method)
+            out[b, :c] = interp._interp_nan_host(rows[b, :c], method)
     return torch.from_numpy(np.ascontiguousarray(out)).to(X.device)
 
 
