@@ -136,6 +136,14 @@ int mm_build_mel_sweep(const mm_config* cfg, int n_waves, float* wlo /*[n_bins]*
  * m_end}.  counts[0] = n_runs, counts[1] = n_groups.  Capacities are in runs / groups. */
 int mm_build_mel_runs(const mm_config* cfg, int n_waves, int32_t* hdr, int32_t hdr_cap, float* grp,
                       int32_t grp_cap, int32_t* part, int32_t* counts);
+/* The "shared runs" form of that table, which the fused launches of the staged-sample kernel walk where the plan has
+ * two log-mel tiles and no empty filter (host-only, for tests): every run d = -1 .. n_mels-1 appears ONCE.  The first part
+ * with a filter starts at run m_begin-1, every other one at run m_begin; the last run of a part that has a successor
+ * keeps both weights, and its second sum is handed to the successor.  part[w][3] = m_end | 1 << 16 (the part's first
+ * filter takes its rising half from the part before) | 1 << 17 (its last run hands over).  weighted = 1 (n_waves 16
+ * only): the cuts of the fused plan, whose four DCT waves get half-size parts; 0: the cuts of mm_build_mel_runs. */
+int mm_build_mel_runs_shared(const mm_config* cfg, int n_waves, int weighted, int32_t* hdr, int32_t hdr_cap, float* grp,
+                             int32_t grp_cap, int32_t* part, int32_t* counts);
 /* Butterworth low-pass as second-order sections, scipy.signal.butter(order, wn, 'low',
  * output='sos') layout [n_sections][6]; returns the number of sections or a negative status. */
 int mm_build_butter_sos(int order, double wn, double* sos /*[(order+1)/2][6]*/);
@@ -175,6 +183,13 @@ int mm_plan_set_fuse_dct(mm_plan* plan, int on);
  * single launch; off: the time-major launches). */
 int mm_plan_fused_tail(const mm_plan* plan, int64_t batch, int64_t n_samples);
 int mm_plan_set_fuse_tail(mm_plan* plan, int on);
+/* Shared mel runs in the fused launches of the staged-sample kernel: mm_plan_shared_runs() = 1 when a
+ * regular fused call of this plan walks every mel run once (two log-mel tiles, no empty filters, an instantiation for the
+ * plan's hop), 0 when it walks the overlapping runs of mm_build_mel_runs.  The results are bit for bit the same.
+ * mm_plan_set_shared_runs(plan, 0) pins the overlapping runs (A/B measurements, cross-checks); returns the previous
+ * setting; default on. */
+int mm_plan_shared_runs(const mm_plan* plan);
+int mm_plan_set_shared_runs(mm_plan* plan, int on);
 /* force the generic kernels (debug / cross-check); returns previous value */
 int mm_plan_force_generic(mm_plan* plan, int on);
 /* pin one of the variants above (1..5) for the calls it can take, 0 = automatic choice; returns the

@@ -126,6 +126,7 @@ PROTOTYPES = {
     "mm_build_dct": (C.c_int, [_cfgp, _vp]),
     "mm_build_mel_sweep": (C.c_int, [_cfgp, C.c_int, _vp, _vp, _vp, _vp]),
     "mm_build_mel_runs": (C.c_int, [_cfgp, C.c_int, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp]),
+    "mm_build_mel_runs_shared": (C.c_int, [_cfgp, C.c_int, C.c_int, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp]),
     "mm_build_butter_sos": (C.c_int, [C.c_int, C.c_double, _vp]),
     "mm_plan_create": (C.c_int, [_cfgp, C.POINTER(_vp)]),
     "mm_plan_destroy": (C.c_int, [_vp]),
@@ -134,6 +135,8 @@ PROTOTYPES = {
     "mm_plan_fused_dct": (C.c_int, [_vp]),
     "mm_plan_set_fuse_dct": (C.c_int, [_vp, C.c_int]),
     "mm_plan_fused_tail": (C.c_int, [_vp, _i64, _i64]),
+    "mm_plan_shared_runs": (C.c_int, [_vp]),
+    "mm_plan_set_shared_runs": (C.c_int, [_vp, C.c_int]),
     "mm_plan_set_fuse_tail": (C.c_int, [_vp, C.c_int]),
     "mm_mfcc_modspec_f32": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, C.c_size_t, _vp]),
     "mm_plan_force_generic": (C.c_int, [_vp, C.c_int]),

@@ -326,6 +326,28 @@ int mm_build_mel_runs(const mm_config* c, int n_waves, int32_t* hdr, int32_t hdr
   std::memcpy(part, r.part.data(), r.part.size() * 4);
   return MM_OK;
 }
+int mm_build_mel_runs_shared(const mm_config* c, int n_waves, int weighted, int32_t* hdr, int32_t hdr_cap, float* grp,
+                             int32_t grp_cap, int32_t* part, int32_t* counts) {
+  int s = mm::validate(c);
+  if (s) return s;
+  if (n_waves < 1 || !hdr || !grp || !part || !counts || (weighted && n_waves != 16)) return MM_ERR_INVALID_ARG;
+  std::vector<float> mel((size_t)c->n_mels * (c->n_fft / 2 + 1));
+  mm::build_mel(*c, mel.data());
+  mm::MelSweep sw;
+  const double wts_d[16] = {1, 1, 1, MM_S16F_W, 1, 1, 1, MM_S16F_W, 1, 1, 1, MM_S16F_W, 1, 1, 1, MM_S16F_W};
+  if (!(weighted ? mm::build_mel_sweep(*c, mel.data(), n_waves, &sw, wts_d, MM_S16F_SH_FC, MM_S16F_SH_FC)
+                 : mm::build_mel_sweep(*c, mel.data(), n_waves, &sw)))
+    return MM_ERR_UNSUPPORTED;
+  mm::MelRuns r;
+  mm::build_mel_runs_shared(*c, sw, n_waves, &r);
+  counts[0] = (int32_t)(r.hdr.size() / 4);
+  counts[1] = (int32_t)(r.grp.size() / 8);
+  if (counts[0] > hdr_cap || counts[1] > grp_cap) return MM_ERR_WORKSPACE;
+  std::memcpy(hdr, r.hdr.data(), r.hdr.size() * 4);
+  std::memcpy(grp, r.grp.data(), r.grp.size() * 4);
+  std::memcpy(part, r.part.data(), r.part.size() * 4);
+  return MM_OK;
+}
 int mm_build_butter_sos(int order, double wn, double* sos) { return mm::build_butter_sos(order, wn, sos); }
 
 // ---- host tables of a plan: pure functions of the configuration ----
@@ -718,6 +740,32 @@ static void setup_s16f(mm_plan* p, const PlanHost& h, size_t tab16_bytes) {
       p->s16.xa = false;
       p->s16.lds_bytes = (size_t)MM_S16_TAB_OFF(p->s16.nr, false) + tab16_bytes;
     }
+    // Shared runs (mm::build_mel_runs_shared): every run once -- a part loses its first run and the wave that owns a
+    // boundary filter gains the finishing step (~20 instructions, in `extra`).  Two log-mel tiles and no
+    // empty filters only: with one tile the DCT waves read the rows before the finishing step has run, and a skipped
+    // filter has no sum to hand over.  The table is smaller than the one above, so this layout fits wherever that one did.
+    if (!single && !ef.skip) {
+      mm::MelSweep sws;              // its own cuts: a part's cost is its runs (one per filter) far more than its bins
+      mm::MelRuns rs;
+      if (!mm::build_mel_sweep(c, h.melp, 16, &sws, wts_d, MM_S16F_SH_FC, MM_S16F_SH_FC)) return;
+      mm::build_mel_runs_shared(c, sws, 16, &rs);
+      for (int w = 0; w < 16; ++w) if (rs.part[w * 4 + 3] & MM_RUNS_CONSUMER) extra[w] += 20.0;
+      const std::vector<float> tabs = packed_run_table(rs);
+      const std::vector<int> parts = balance_parts_over_simds(rs, extra, &wave_of_part);
+      mm_plan::S16F::Shared& sh = f.sh;
+      sh.roles = ~0ull;
+      for (int k = 0; k < 4; ++k) {
+        const int w = wave_of_part[4 * k + 3];
+        sh.roles = (sh.roles & ~(0xFull << (4 * w))) | ((unsigned long long)k << (4 * w));
+      }
+      sh.n_runs = (int)(rs.hdr.size() / 4); sh.n_tab16 = (int)(tabs.size() / 4);
+      sh.lt_off = (unsigned)align_up((size_t)MM_S16_TAB_OFF(p->s16.nr, xa) + tabs.size() * 4, 16);
+      sh.dcta_off = sh.lt_off + 2u * (unsigned)lt_rows * 320u;
+      sh.red_off = (unsigned)align_up((size_t)sh.dcta_off + dcta.size() * 4, 16);
+      sh.lds_bytes = (size_t)sh.red_off + 2 * 16 * 8;
+      sh.ok = sh.lds_bytes <= lds && p->upload(&sh.d_tab, tabs.data(), tabs.size() * 4) == MM_OK &&
+              p->upload(&sh.d_part, parts.data(), parts.size() * 4) == MM_OK;
+    }
     return;
   }
 }
@@ -1021,6 +1069,13 @@ static bool s16_clip_mode_ok(const mm_plan* p, int64_t batch, int n_mod) {
   return per * g * 100 <= batch * 104;          // at most 4 % of idle workgroup time
 }
 
+// Whether a fused launch of the staged-sample kernel walks the shared-runs table: the plan has one (two log-mel tiles, no
+// empty filters), nobody pinned the overlapping runs, and the call's instantiation exists (mm_s16.h).
+static bool s16f_shared_runs(const mm_plan* p, bool unal) {
+  return p->s16f.ok && p->s16f.sh.ok && !p->user.no_shared_runs &&
+         s16_has_shared(p->s16.nr, p->s16.xa, p->cfg.preemph != 0.0f, p->cfg.hop_length & 1, unal);
+}
+
 // What a log-mel call produces beyond its rows: the MFCC (the DCT may be fused into the launch), the MFCC with clip mode
 // where the plan has empty filters (their share added in the launch), or the MFCC and its modulation spectrum.
 enum Want { WANT_ROWS, WANT_MFCC, WANT_MFCC_CLIP, WANT_MODSPEC };
@@ -1071,6 +1126,19 @@ int mm_plan_set_fuse_tail(mm_plan* p, int on) {
   p->user.no_fuse_tail = on ? 0 : 1;
   p->user.fuse_tail_wide = on == 2 ? 1 : 0;
   return prev;
+}
+
+int mm_plan_set_shared_runs(mm_plan* p, int on) {
+  if (!p) return MM_ERR_INVALID_ARG;
+  const int prev = !p->user.no_shared_runs;
+  p->user.no_shared_runs = on ? 0 : 1;
+  return prev;
+}
+
+int mm_plan_shared_runs(const mm_plan* p) {
+  if (!p) return MM_ERR_INVALID_ARG;
+  return dispatch(p, 1, CallShape(), WANT_MFCC).fused_dct && dispatch(p, 1, CallShape(), WANT_MFCC).kernel == MM_K_W16S &&
+                 s16f_shared_runs(p, false) ? 1 : 0;
 }
 
 int mm_plan_set_variant(mm_plan* p, int variant) {
@@ -1263,26 +1331,30 @@ static int launch_tile512(const mm_plan* p, int mode, const Dispatch& d, const C
     return MM_OK;
   }
   size_t lds = p->s16.lds_bytes;
+  bool sh = false;
   if (d.fused_dct) {
     // DCT fused in: its own run table (half-size parts for the four DCT waves)
     const mm_plan::S16F& f = p->s16f;
-    q.mel_tab = (const float4*)f.d_tab; q.n_runs = f.n_runs; q.n_tab16 = f.n_tab16;
-    q.wave_part = f.d_part;
+    sh = s16f_shared_runs(p, unaligned_rows(c));
+    q.mel_tab = (const float4*)(sh ? f.sh.d_tab : f.d_tab); q.n_runs = sh ? f.sh.n_runs : f.n_runs;
+    q.n_tab16 = sh ? f.sh.n_tab16 : f.n_tab16;
+    q.wave_part = sh ? f.sh.d_part : f.d_part;
     q.out_mfcc = o.mfcc; q.key_nmin = o.key_nmin; q.dct_a = f.d_dcta; q.n_mfcc = p->cfg.n_mfcc;
     q.dct_nk = f.nk; q.dct_kb = f.kb; q.lt_rows = f.lt_rows;
-    q.lt_off = f.lt_off; q.dcta_off = f.dcta_off; q.dct_roles = f.roles;
+    q.lt_off = sh ? f.sh.lt_off : f.lt_off; q.dcta_off = sh ? f.sh.dcta_off : f.dcta_off;
+    q.dct_roles = sh ? f.sh.roles : f.roles;
     q.dct_flags = f.flags | (p->s16.halfwin ? MM_S16F_HALFWIN : 0);
     q.lt_b2 = (f.flags & MM_S16F_SINGLE) ? 0 : f.lt_rows;
     if (p->cfg.top_db < 0.0f) q.out_logmel = nullptr;      // the rows only feed the clamp fix-up
-    lds = f.lds_bytes;
-    q.red_off = f.red_off;
+    lds = sh ? f.sh.lds_bytes : f.lds_bytes;
+    q.red_off = sh ? f.sh.red_off : f.red_off;
     if (d.clip) {
       // whole clips per workgroup: extremes, clamp fix-up and trajectory rFFT inside the launch
       q.out_mod = (float2*)o.mod; q.n_mod = o.mod ? c.n_mod : 0; q.dct_t = p->base.d_dct_t; q.dct_kp = p->kp; q.top_db = p->cfg.top_db;
       grid = c.batch < p->num_cus ? c.batch : p->num_cus;
       const size_t per = (size_t)((c.batch + grid - 1) / grid);
-      lds = std::max((size_t)f.red_off + per * 128, (size_t)MM_S16_FIN_TAB_OFF + MM_S16_FIN_TAB_BYTES);
-      lds = std::max(lds, (size_t)MM_S16_DELTA_OFF((size_t)f.red_off, per, q.n_mod) + per * 4);
+      lds = std::max((size_t)q.red_off + per * 128, (size_t)MM_S16_FIN_TAB_OFF + MM_S16_FIN_TAB_BYTES);
+      lds = std::max(lds, (size_t)MM_S16_DELTA_OFF((size_t)q.red_off, per, q.n_mod) + per * 4);
       if (q.n_mod == 2048) {          // the tail runs the 2048-point transform: its lane table rides in q.tw
         q.tw = (const float2*)p->rf2k.d_lane_tab;
         lds = std::max(lds, (size_t)MM_S16_FIN2K_BYTES);
@@ -1290,7 +1362,7 @@ static int launch_tile512(const mm_plan* p, int mode, const Dispatch& d, const C
       mode = 2;
     }
   }
-  launch_s16(mode, p->s16.nr, p->s16.xa, p->cfg.preemph != 0.0f, p->cfg.hop_length & 1, unaligned_rows(c),
+  launch_s16(mode, p->s16.nr, p->s16.xa, p->cfg.preemph != 0.0f, p->cfg.hop_length & 1, unaligned_rows(c), sh,
              dim3((unsigned)grid), lds, st, q);
   return MM_OK;
 }

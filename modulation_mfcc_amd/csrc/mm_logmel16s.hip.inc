@@ -1,5 +1,5 @@
 #pragma once
-// (included by mm_logmel16s.hip, its own translation unit: 120 instantiations)
+// (included by mm_logmel16s.hip, its own translation unit: 124 instantiations)
 // logmel512s_kernel<MODE, NR>: the 16-wave fused n_fft = 512 kernel of mm_logmel16w.hip.inc with the
 // tile's samples STAGED through LDS.  Measured on the direct-load variant (compile-time ablations, s_memtime
 // stamps in tools/stamps.py): its 16 x 8-byte global loads per item -- every sample is fetched
@@ -491,9 +491,18 @@ __device__ __forceinline__ void s16_ex_store(unsigned m0v, const float (&v)[16])
 
 // From mm_tile512.hip.inc this kernel takes the lane-record offsets, the split-twiddle read and the MODE 0 tile store; the
 // rest of phase A and the mel walk stay on its own code (docs/experiments.md, "S16 over the shared tile pieces").
-template <int MODE, int NR, bool PRE, bool ODD, bool UNAL, bool XA>
+#ifndef MM_S16_SH_PRIO
+#define MM_S16_SH_PRIO 3
+#endif
+// SH ("shared runs", mm::build_mel_runs_shared; fused launches with two log-mel tiles only): every mel run is walked by
+// ONE wave.  The wave whose last run ends at a part boundary leaves that run's second sum -- the rising half of the next
+// part's first filter -- in the filter's own row of the current log-mel tile, in front of the end-of-tile barrier; the
+// wave that owns the filter keeps its falling half in a register through phase B and finishes it right behind that
+// barrier (same sum, same operand order as the walk's own `carry + sa`).  The per-clip extremes follow the finishing step.
+template <int MODE, int NR, bool PRE, bool ODD, bool UNAL, bool XA, bool SH>
 __global__ __launch_bounds__(1024) void logmel512s_kernel(Logmel512Params p) {
   static_assert(!XA || NR >= 3, "the addtid exchange exists for NR 3 / 4 only");
+  static_assert(!SH || MODE != 0, "shared runs belong to the fused launches");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* P = reinterpret_cast<float*>(smem);
   float* S = reinterpret_cast<float*>(smem + MM_S16_S_OFF(XA));
@@ -510,6 +519,8 @@ __global__ __launch_bounds__(1024) void logmel512s_kernel(Logmel512Params p) {
     reinterpret_cast<float4*>(smem + MM_S16_TAB_OFF(NR, XA))[i] = p.mel_tab[i];
   const int run0 = p.wave_part[wave * 4 + 0], run1 = p.wave_part[wave * 4 + 1];
   const int m0 = p.wave_part[wave * 4 + 2];
+  // SH: m_end | MM_RUNS_CONSUMER | MM_RUNS_PRODUCER of this wave's part (wave-uniform)
+  const int m1f = SH ? __builtin_amdgcn_readfirstlane(p.wave_part[wave * 4 + 3]) : 0;
   // Fused DCT (MODE 1, p.out_mfcc): phase B also leaves its log-mel values in an LDS tile Lt[m][frame]
   // (double buffered, pitch 80 floats) and four "DCT waves" -- they walk half-size mel parts -- turn the
   // PREVIOUS tile's Lt into MFCC rows at the end of their phase B: D[16 coefficients x 16 frames] +=
@@ -883,6 +894,7 @@ __global__ __launch_bounds__(1024) void logmel512s_kernel(Logmel512Params p) {
     }
     MM_STAMP_AT(5)
     // ---------------- phase B ----------------
+    float held = 0.0f;          // SH: the falling half of filter m0, from the walk to the finishing step
     if (MODE == 0) {
       tile512_store_power_tile(p.out_power, P, MM_S16_PITCH(XA), b, t0, p.n_frames, wave, 16, lane);
     } else {
@@ -923,7 +935,10 @@ __global__ __launch_bounds__(1024) void logmel512s_kernel(Logmel512Params p) {
           // a live filter -- frames behind the clip's end (its last tile) and filters without weights stay out.  The two
           // updates sit on the common path: in one arm of the branch they cost a register copy on every edge.
           float dbm = __builtin_nanf("");
-          if (dd >= m0) {
+          if (SH && (m1f & MM_RUNS_CONSUMER) && r == run0) {      // (wave-uniform) filter m0: finished behind the barrier
+            held = sa;
+            o += p.n_frames;
+          } else if (dd >= m0) {
             if (!empty_d) {                  // (an empty filter is neither computed nor stored: MM_S16F_SKIP)
               const float v = carry + sa;
               const float db = 3.0102999566398120f * __builtin_amdgcn_logf(mm_max_raw_s(v, p.amin)) - p.db_offset;
@@ -938,9 +953,11 @@ __global__ __launch_bounds__(1024) void logmel512s_kernel(Logmel512Params p) {
           carry = sb;
           MM_STAMP_AT(14)
         }
+        // the hand-over: row m_end of this tile's buffer, which nobody reads before its owner has finished the filter
+        if (SH && (m1f & MM_RUNS_PRODUCER)) Lt[((tile & 1) * p.lt_b2 + (m1f & 0xFFFF)) * 80 + lane] = carry;
       }
       const bool clip_done = (tile + 1 == tile_end) || (ntl == 0);
-      if (clip_done) {   // wave-uniform
+      if (clip_done && !SH) {   // wave-uniform
         vmax = wave_max(vmax);
         if (p.key_nmin || clip_mode) vmin = wave_min(vmin);
         if (clip_mode) {
@@ -956,10 +973,43 @@ __global__ __launch_bounds__(1024) void logmel512s_kernel(Logmel512Params p) {
     MM_STAMP_AT(7)
     wg_barrier_lds();
     MM_STAMP_AT(8)
+    if constexpr (SH) {
+      // The finishing step of filter m0 of the tile just walked: the part before this one has left the filter's rising
+      // half in its row of that tile's buffer.  Nothing of phase A is live here, and the DCT waves read the row behind the
+      // next mid-tile barrier (behind the barrier after the loop for the launch's last tile).
+      // (raised priority: a short dependent chain, which would otherwise queue behind the older waves' phase A)
+      const bool valid = (t0 + lane) < p.n_frames;
+      __builtin_amdgcn_s_setprio(MM_S16_SH_PRIO);
+      if (m1f & MM_RUNS_CONSUMER) {      // (wave-uniform)
+        float* lr = Lt + ((tile & 1) * p.lt_b2 + m0) * 80 + lane;
+        const float v = *lr + held;
+        const float db = 3.0102999566398120f * __builtin_amdgcn_logf(mm_max_raw_s(v, p.amin)) - p.db_offset;
+        if (valid && p.out_logmel) p.out_logmel[((int64_t)b * p.n_mels + m0) * p.n_frames + t0 + lane] = db;
+        *lr = db;
+        const float dbm = valid ? db : __builtin_nanf("");
+        mm_max_acc(vmax, dbm);
+        mm_min_acc(vmin, dbm);
+      }
+      // the clip's extremes, now that its last tile's boundary filters are in (the walk's own block, above, otherwise)
+      if ((tile + 1 == tile_end) || (ntl == 0)) {   // wave-uniform
+        vmax = wave_max(vmax);
+        if (p.key_nmin || clip_mode) vmin = wave_min(vmin);
+        if (clip_mode) {
+          if (lane == 0)
+            reinterpret_cast<float2*>(smem + p.red_off)[(b - tile_begin / tpc) * 16 + wave] = make_float2(vmax, vmin);
+        } else if (lane == 0 && vmax > -INFINITY) {
+          atomicMax(p.clip_key + b, float_key(vmax));
+          if (p.key_nmin) atomicMax(p.key_nmin + b, float_key(-vmin));
+        }
+        vmax = -INFINITY; vmin = INFINITY;
+      }
+      __builtin_amdgcn_s_setprio(0);
+    }
     pb = b; pt0 = t0; has_prev = true;
     b = nb; tl = ntl;
   }
-  // the last tile's log-mel values are complete behind the loop's final barrier
+  // the last tile's log-mel values are complete behind the loop's final barrier (SH: behind its finishing step)
+  if (SH) wg_barrier_lds();
   if (role < 4 && has_prev) dct_tile(Lt + (((tile_end - 1) & 1) * p.lt_b2) * 80, pb, pt0);
   if (clip_mode && has_prev) {           // the tail of this workgroup's clips (s16_finalize_all)
     S16Fin f;
@@ -976,16 +1026,19 @@ __global__ __launch_bounds__(1024) void logmel512s_kernel(Logmel512Params p) {
 
 // ---- host side: the instantiations, listed once.  MODE 0/1/2 x NR 3/4 x PRE x ODD x UNAL x XA = 96; NR 1/2 -- short
 // hops, e.g. the reference's own 10 kHz default with hop 50: 14.6 KB of samples per tile instead of 48 KB of LDS --
-// without PRE or XA (plans with pre-emphasis never ask for NR 1 / 2: setup_tile512): 24.
-// key = mode << 6 | (nr - 1) << 4 | xa << 3 | pre << 2 | odd << 1 | unal; a key without an instantiation holds nullptr ----
+// without PRE or XA (plans with pre-emphasis never ask for NR 1 / 2: setup_tile512): 24.  SH (shared mel runs): MODE 1 / 2
+// x NR 3 / 4 with XA, without PRE / ODD / UNAL: 4 -- the regular calls of the long-hop plans (BASELINE configs[1] / [2]);
+// every other call walks the overlapping runs (s16_has_shared tells the launcher which table to pass).
+// key = sh << 8 | mode << 6 | (nr - 1) << 4 | xa << 3 | pre << 2 | odd << 1 | unal; a key without an instantiation holds nullptr ----
 using S16Kernel = void (*)(Logmel512Params);
-#define MM_S16_KEYS 192
+#define MM_S16_KEYS 448
 template <int KEY>
 static constexpr S16Kernel s16_entry() {
-  constexpr int MODE = KEY >> 6, NR = ((KEY >> 4) & 3) + 1;
-  constexpr bool XA = (KEY & 8) != 0, PRE = (KEY & 4) != 0, ODD = (KEY & 2) != 0, UNAL = (KEY & 1) != 0;
-  if constexpr (NR < 3 && (XA || PRE)) return nullptr;
-  else return logmel512s_kernel<MODE, NR, PRE, ODD, UNAL, XA>;
+  constexpr int MODE = (KEY >> 6) & 3, NR = ((KEY >> 4) & 3) + 1;
+  constexpr bool XA = (KEY & 8) != 0, PRE = (KEY & 4) != 0, ODD = (KEY & 2) != 0, UNAL = (KEY & 1) != 0, SH = (KEY & 256) != 0;
+  if constexpr (MODE == 3 || (NR < 3 && (XA || PRE))) return nullptr;
+  else if constexpr (SH && (MODE == 0 || NR < 3 || !XA || PRE || ODD || UNAL)) return nullptr;
+  else return logmel512s_kernel<MODE, NR, PRE, ODD, UNAL, XA, SH>;
 }
 template <int... KEY>
 static S16Kernel s16_lookup(int key, std::integer_sequence<int, KEY...>) {
@@ -994,14 +1047,21 @@ static S16Kernel s16_lookup(int key, std::integer_sequence<int, KEY...>) {
 }
 static S16Kernel s16_kernel(int key) { return s16_lookup(key, std::make_integer_sequence<int, MM_S16_KEYS>()); }
 
-void launch_s16(int mode, int nr, bool xa, bool pre, bool odd, bool unal, dim3 grid, size_t lds, hipStream_t st,
+static int s16_key(int mode, int nr, bool xa, bool pre, bool odd, bool unal, bool sh) {
+  nr = nr >= 1 && nr <= 3 ? nr : 4;
+  if (nr < 3) { xa = false; pre = false; }
+  return (sh ? 256 : 0) | mode << 6 | (nr - 1) << 4 | (xa ? 8 : 0) | (pre ? 4 : 0) | (odd ? 2 : 0) | (unal ? 1 : 0);
+}
+
+bool s16_has_shared(int nr, bool xa, bool pre, bool odd, bool unal) {
+  return s16_kernel(s16_key(1, nr, xa, pre, odd, unal, true)) != nullptr;
+}
+
+void launch_s16(int mode, int nr, bool xa, bool pre, bool odd, bool unal, bool sh, dim3 grid, size_t lds, hipStream_t st,
                 const Logmel512Params& q) {
   if (mode == 1 && q.out_mod != nullptr) mode = 2;        // clip mode (fused tail); 2 may also be asked for directly (n_mod 0)
   mode = mode == 0 || mode == 1 ? mode : 2;
-  nr = nr >= 1 && nr <= 3 ? nr : 4;
-  if (nr < 3) { xa = false; pre = false; }
-  const int key = mode << 6 | (nr - 1) << 4 | (xa ? 8 : 0) | (pre ? 4 : 0) | (odd ? 2 : 0) | (unal ? 1 : 0);
-  hipLaunchKernelGGL(s16_kernel(key), grid, dim3(1024), lds, st, q);
+  hipLaunchKernelGGL(s16_kernel(s16_key(mode, nr, xa, pre, odd, unal, sh)), grid, dim3(1024), lds, st, q);
 }
 
 bool set_s16_attr(int bytes) {

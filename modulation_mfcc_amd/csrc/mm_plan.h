@@ -67,6 +67,13 @@ struct mm_plan {
     int flags = 0;                 // Logmel512Params::dct_flags (MM_S16F_SINGLE | MM_S16F_SKIP)
     unsigned lt_off = 0, dcta_off = 0, red_off = 0;   // red_off: clip mode's per-wave clip max / min slots
     unsigned long long roles = 0; size_t lds_bytes = 0;
+    struct Shared {                // the same plan on the shared-runs table (mm::build_mel_runs_shared): two log-mel tiles and
+      bool ok = false;             // no empty filters only; DCT operands, flags and row counts are those above
+      float* d_tab = nullptr; int* d_part = nullptr;
+      int n_runs = 0, n_tab16 = 0;
+      unsigned lt_off = 0, dcta_off = 0, red_off = 0;
+      unsigned long long roles = 0; size_t lds_bytes = 0;
+    } sh;
   } s16f;
   struct M12 {                     // 12-wave MFMA-mel variant (mm_logmel12m.hip.inc)
     bool ok = false, fused_dct = false;
@@ -97,6 +104,7 @@ struct mm_plan {
     int force_generic = 0;         // mm_plan_force_generic
     int no_fuse = 0;               // mm_plan_set_fuse_dct(0): always run the separate clamp + DCT kernel
     int no_fuse_tail = 0;          // mm_plan_set_fuse_tail(0): mm_mfcc_modspec_f32 always runs its separate launches
+    int no_shared_runs = 0;        // mm_plan_set_shared_runs(0): fused launches walk the overlapping runs (A/B, cross-checks)
     int fuse_tail_wide = 0;        // mm_plan_set_fuse_tail(2): clip mode also for 2048-point trajectories and for mm_mfcc_f32 (empty filters)
   } user;
   struct Timing {

@@ -1,4 +1,4 @@
-// The staged-sample n_fft = 512 kernel (mm_logmel16s.hip.inc) is its own translation unit (120 instantiations): this
+// The staged-sample n_fft = 512 kernel (mm_logmel16s.hip.inc) is its own translation unit (124 instantiations): this
 // header carries what the plan / dispatch code in mm_api.hip needs from it -- the LDS layout and the launch wrappers.
 #pragma once
 #include "mm_common.h"
@@ -34,6 +34,11 @@ static_assert(1068 <= 4 * MM_S16_XA_PITCH && 15 * 4 * MM_S16_XA_PITCH * 4 < 6553
 #ifndef MM_S16F_W
 #define MM_S16F_W 0.5     // mel share of a DCT wave relative to the other waves
 #endif
+// cuts of the shared-runs table (mm::build_mel_sweep's filter_cost = lead_cost): a run costs the walk ~58 instructions, a
+// 4-bin group ~8.5 (balance_parts_over_simds), i.e. a filter weighs as much as ~27 bins
+#ifndef MM_S16F_SH_FC
+#define MM_S16F_SH_FC 27.0
+#endif
 #define MM_S16_LT_OFF(NR, XA) (MM_S16_S_OFF(XA) + (NR) * 16384)
 #define MM_S16_TAB_OFF(NR, XA) (MM_S16_LT_OFF(NR, XA) + 16 * MM_W16_LT_PITCH * 4)
 
@@ -49,7 +54,9 @@ static_assert(1068 <= 4 * MM_S16_XA_PITCH && 15 * 4 * MM_S16_XA_PITCH * 4 < 6553
 
 struct Logmel512Params;
 // mode 0 power rows | 1 log-mel (+ fused DCT) | (1 with q.out_mod set ->) 2 clip mode; nr = 16-byte staging groups per thread;
-// xa (nr 3 / 4 only): the ds_write_addtid_b32 exchange at pitch MM_S16_PITCH(true)
-void launch_s16(int mode, int nr, bool xa, bool pre, bool odd, bool unal, dim3 grid, size_t lds, hipStream_t st,
+// xa (nr 3 / 4 only): the ds_write_addtid_b32 exchange at pitch MM_S16_PITCH(true); sh: q carries a shared-runs table
+// (mm::build_mel_runs_shared) -- only where s16_has_shared() says the instantiation exists
+void launch_s16(int mode, int nr, bool xa, bool pre, bool odd, bool unal, bool sh, dim3 grid, size_t lds, hipStream_t st,
                 const Logmel512Params& q);
+bool s16_has_shared(int nr, bool xa, bool pre, bool odd, bool unal);
 bool set_s16_attr(int bytes);       // hipFuncAttributeMaxDynamicSharedMemorySize on every instantiation (current device)

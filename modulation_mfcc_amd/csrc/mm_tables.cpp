@@ -209,7 +209,8 @@ void build_mel_csr(const mm_config& c, const float* dense, MelCsr* csr) {
 
 // Returns false when the matrix does not have the <= 2 adjacent filters per bin structure
 // (cannot happen for triangular filters with shared edges; checked anyway).
-bool build_mel_sweep(const mm_config& c, const float* dense, int n_waves, MelSweep* out, const double* weights) {
+bool build_mel_sweep(const mm_config& c, const float* dense, int n_waves, MelSweep* out, const double* weights,
+                     double filter_cost, double lead_cost) {
   const int n_mels = c.n_mels, n_bins = c.n_fft / 2 + 1;
   out->wlo.assign(n_bins, 0.0f);
   out->whi.assign(n_bins, 0.0f);
@@ -236,7 +237,7 @@ bool build_mel_sweep(const mm_config& c, const float* dense, int n_waves, MelSwe
     out->d[k] = d;
     prev = d;
   }
-  // partition the filters over the waves: cost = bins swept + 6 per emitted filter
+  // partition the filters over the waves: cost = bins swept + filter_cost (6) per emitted filter (+ lead_cost once)
   auto range_of = [&](int m0, int m1, int* kb, int* ke) {
     int b = n_bins, e = 0;
     for (int k = 0; k < n_bins; ++k)
@@ -249,7 +250,7 @@ bool build_mel_sweep(const mm_config& c, const float* dense, int n_waves, MelSwe
   };
   int kb_all, ke_all;
   range_of(0, n_mels, &kb_all, &ke_all);
-  const double total = (double)(ke_all - kb_all) + 6.0 * n_mels;
+  const double total = (double)(ke_all - kb_all) + filter_cost * n_mels + lead_cost;
   out->part.assign((size_t)n_waves * 4, 0);
   double wsum = 0.0, wcum = 0.0;
   for (int w = 0; w < n_waves; ++w) wsum += weights ? weights[w] : 1.0;
@@ -266,7 +267,7 @@ bool build_mel_sweep(const mm_config& c, const float* dense, int n_waves, MelSwe
       while (m1 < n_mels) {
         int kb, ke;
         range_of(0, m1 + 1, &kb, &ke);
-        const double cum = (double)(ke - kb_all > 0 ? ke - kb_all : 0) + 6.0 * (m1 + 1);
+        const double cum = (double)(ke - kb_all > 0 ? ke - kb_all : 0) + filter_cost * (m1 + 1) + lead_cost;
         if (cum > target && m1 > m0) break;
         ++m1;
         if (cum > target) break;
@@ -286,6 +287,31 @@ bool build_mel_sweep(const mm_config& c, const float* dense, int n_waves, MelSwe
   return true;
 }
 
+// One run of the sweep: header {first bin, n_groups, first group, d} and its 4-bin groups {wlo x4, whi x4}.  The groups
+// span every bin of the run that carries a weight, whichever half is zeroed afterwards.
+static void emit_mel_run(const MelSweep& sw, int n_bins, int d, bool zero_lo, bool zero_hi, MelRuns* out) {
+  int ks = n_bins, ke = 0;
+  for (int k = 0; k < n_bins; ++k)
+    if (sw.d[k] == d && (sw.wlo[k] != 0.0f || sw.whi[k] != 0.0f)) { ks = std::min(ks, k); ke = std::max(ke, k + 1); }
+  int g0 = 0, g1 = 0;
+  if (ke > ks) { g0 = ks / 4; g1 = (ke + 3) / 4; }
+  out->hdr.push_back(4 * g0);
+  out->hdr.push_back(g1 - g0);
+  out->hdr.push_back((int)(out->grp.size() / 8));
+  out->hdr.push_back(d);
+  for (int g = g0; g < g1; ++g) {
+    float wl[4], wh[4];
+    for (int u = 0; u < 4; ++u) {
+      const int k = 4 * g + u;
+      const bool in = (k >= ks && k < ke && k < n_bins && sw.d[k] == d);
+      wl[u] = in && !zero_lo ? sw.wlo[k] : 0.0f;
+      wh[u] = in && !zero_hi ? sw.whi[k] : 0.0f;
+    }
+    for (int u = 0; u < 4; ++u) out->grp.push_back(wl[u]);
+    for (int u = 0; u < 4; ++u) out->grp.push_back(wh[u]);
+  }
+}
+
 void build_mel_runs(const mm_config& c, const MelSweep& sw, int n_waves, MelRuns* out) {
   const int n_bins = c.n_fft / 2 + 1;
   out->hdr.clear(); out->grp.clear();
@@ -295,34 +321,32 @@ void build_mel_runs(const mm_config& c, const MelSweep& sw, int n_waves, MelRuns
     out->part[w * 4 + 0] = (int)(out->hdr.size() / 4);
     out->part[w * 4 + 2] = m0;
     out->part[w * 4 + 3] = m1;
+    // filter m0-1 (first run) and filter m1 (last run) belong to other waves
+    for (int d = m0 - 1; m1 > m0 && d <= m1 - 1; ++d) emit_mel_run(sw, n_bins, d, d == m0 - 1, d == m1 - 1, out);
+    out->part[w * 4 + 1] = (int)(out->hdr.size() / 4);
+  }
+}
+
+void build_mel_runs_shared(const mm_config& c, const MelSweep& sw, int n_waves, MelRuns* out) {
+  const int n_bins = c.n_fft / 2 + 1;
+  out->hdr.clear(); out->grp.clear();
+  out->part.assign((size_t)n_waves * 4, 0);
+  bool first = true;
+  for (int w = 0; w < n_waves; ++w) {
+    const int m0 = sw.part[w * 4 + 2], m1 = sw.part[w * 4 + 3];
+    out->part[w * 4 + 0] = (int)(out->hdr.size() / 4);
+    out->part[w * 4 + 2] = m0;
+    int flags = 0;
     if (m1 > m0) {
-      for (int d = m0 - 1; d <= m1 - 1; ++d) {
-        int ks = n_bins, ke = 0;
-        for (int k = 0; k < n_bins; ++k)
-          if (sw.d[k] == d && (sw.wlo[k] != 0.0f || sw.whi[k] != 0.0f)) { ks = std::min(ks, k); ke = std::max(ke, k + 1); }
-        int g0 = 0, g1 = 0;
-        if (ke > ks) { g0 = ks / 4; g1 = (ke + 3) / 4; }
-        out->hdr.push_back(4 * g0);
-        out->hdr.push_back(g1 - g0);
-        out->hdr.push_back((int)(out->grp.size() / 8));
-        out->hdr.push_back(d);
-        for (int g = g0; g < g1; ++g) {
-          float wl[4], wh[4];
-          for (int u = 0; u < 4; ++u) {
-            const int k = 4 * g + u;
-            const bool in = (k >= ks && k < ke && k < n_bins && sw.d[k] == d);
-            wl[u] = in ? sw.wlo[k] : 0.0f;
-            wh[u] = in ? sw.whi[k] : 0.0f;
-            // filter m0-1 (first run) and filter m1 (last run) belong to other waves
-            if (d == m0 - 1) wl[u] = 0.0f;
-            if (d == m1 - 1) wh[u] = 0.0f;
-          }
-          for (int u = 0; u < 4; ++u) out->grp.push_back(wl[u]);
-          for (int u = 0; u < 4; ++u) out->grp.push_back(wh[u]);
-        }
-      }
+      bool succ = false;                 // a later part with a filter: empty parts (fewer filters than waves) are passed over
+      for (int v = w + 1; v < n_waves && !succ; ++v) succ = sw.part[v * 4 + 3] > sw.part[v * 4 + 2];
+      flags = (first ? 0 : MM_RUNS_CONSUMER) | (succ ? MM_RUNS_PRODUCER : 0);
+      // the rising half of the part's first filter: run m0-1, which only the first part walks itself
+      for (int d = first ? m0 - 1 : m0; d <= m1 - 1; ++d) emit_mel_run(sw, n_bins, d, false, d == m1 - 1 && !succ, out);
+      first = false;
     }
     out->part[w * 4 + 1] = (int)(out->hdr.size() / 4);
+    out->part[w * 4 + 3] = m1 | flags;
   }
 }
 

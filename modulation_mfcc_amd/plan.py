@@ -113,6 +113,20 @@ class MfccConfig:
                                                  cnt.ctypes.data), "mm_build_mel_runs")
         return hdr[:cnt[0]], grp[:cnt[1]], part
 
+    def mel_runs_shared(self, n_waves: int = 16, weighted: bool = False):
+        """mel_runs() in the shared-runs form (every run once; part[:, 3] = m_end | consumer << 16 | producer << 17);
+        weighted: the cuts of the fused plan (16 waves, half-size parts for the DCT waves)."""
+        c = self.to_c()
+        cap_r, cap_g = self.n_mels + 2 * n_waves + 8, self.n_bins // 4 + 2 * self.n_mels + 4 * n_waves + 8
+        hdr = np.zeros((cap_r, 4), dtype=np.int32)
+        grp = np.zeros((cap_g, 8), dtype=np.float32)
+        part = np.zeros((n_waves, 4), dtype=np.int32)
+        cnt = np.zeros(2, dtype=np.int32)
+        _lib.check(_lib.load().mm_build_mel_runs_shared(C.byref(c), n_waves, 1 if weighted else 0, hdr.ctypes.data, cap_r,
+                                                        grp.ctypes.data, cap_g, part.ctypes.data,
+                                                        cnt.ctypes.data), "mm_build_mel_runs_shared")
+        return hdr[:cnt[0]], grp[:cnt[1]], part
+
     def asdict(self):
         return asdict(self)
 
@@ -247,6 +261,15 @@ class MfccPlan:
         2048-point trajectories and to mfcc() on plans with empty mel filters (opt-in: include/modmfcc.h); returns the
         previous setting (0 / 1 / 2)."""
         return self._lib.mm_plan_set_fuse_tail(self._h, 2 if on == 2 else (1 if on else 0))
+
+    @property
+    def shared_runs(self):
+        """True when a regular fused call of this plan walks every mel run once (mm_plan_shared_runs)."""
+        return bool(self._lib.mm_plan_shared_runs(self._h))
+
+    def set_shared_runs(self, on=True):
+        """on=False pins the overlapping mel runs in the fused launches (A/B, cross-checks); returns the previous setting."""
+        return bool(self._lib.mm_plan_set_shared_runs(self._h, 1 if on else 0))
 
     def force_generic(self, on=True):
         return self._lib.mm_plan_force_generic(self._h, 1 if on else 0)
