@@ -30,6 +30,8 @@ from .pitch import pyin_ragged_batch, pyin_ragged_frames, get_f0_batch  # noqa: 
 from .interp import interp_NAN, interp_nan_batch, interp_nan_ragged_batch  # noqa: F401
 from .interp import interp_nan_spline_batch, interp_nan_spline_ragged_batch  # noqa: F401
 from .lomb import modulation_lombscargle_batch, modulation_lombscargle_ragged_batch, modulation_lombscargle_list  # noqa: F401
+from .zoom import (zoom_batch, zoom_ragged_batch, spline_filter_batch, spectrogram_image,  # noqa: F401
+                   spectrogram_image_batch)
 from .ema import read_AG50x, read_AG50x_arrays, read_pos_header  # noqa: F401
 
 __version__ = "0.2.0"

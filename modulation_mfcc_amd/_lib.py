@@ -1,6 +1,7 @@
 """ctypes binding of libmodmfcc.so (include/modmfcc.h and, for the Welch modulation power spectrum, include/modmfcc_modpsd.h;
 for the Welch cross spectrum and coherence, include/modmfcc_modcsd.h; for the quadratic and cubic spline gap filling,
-include/modmfcc_spline.h; for the Lomb-Scargle periodogram of rows with holes, include/modmfcc_lomb.h).
+include/modmfcc_spline.h; for the Lomb-Scargle periodogram of rows with holes, include/modmfcc_lomb.h; for the B-spline zoom
+of 2-D feature images, include/modmfcc_zoom.h).
 
 There is NO CPU fallback: when the shared library cannot be loaded, or a plan cannot be created
 because no MI355X is visible, the calls raise.  Build the library with
@@ -275,6 +276,21 @@ PROTOTYPES_LOMB = {
                                      _vp]),
 }
 
+# every symbol include/modmfcc_zoom.h declares (the sixth header: the B-spline zoom of 2-D feature images)
+MM_ZOOM_CONSTANT, MM_ZOOM_MIRROR = 0, 1
+MM_ZOOM_PREFILTER, MM_ZOOM_DB, MM_ZOOM_FILTER_ONLY = 1, 2, 4
+MM_ZOOM_SEGMENT, MM_ZOOM_MAX_TAPS = 128, 80
+_zoom_args = [C.c_int32, C.c_int32, C.c_double, C.c_int32, _vp, _i64, _i64, _i64, _i64, _i64]
+_zoom_out = [_i64, _i64, _vp, _i64, _i64, _vp, C.c_size_t, _vp]
+PROTOTYPES_ZOOM = {
+    "mm_zoom_version": (C.c_int, []),
+    "mm_zoom2d_workspace_bytes": (C.c_size_t, [C.c_int32, _i64, _i64, _i64, _i64, _i64]),
+    "mm_zoom2d_f32": (C.c_int, _zoom_args + _zoom_out),
+    "mm_zoom2d_f64": (C.c_int, _zoom_args + _zoom_out),
+    "mm_zoom2d_ragged_f32": (C.c_int, _zoom_args + [_vp, C.c_double] + _zoom_out),
+    "mm_zoom2d_ragged_f64": (C.c_int, _zoom_args + [_vp, C.c_double] + _zoom_out),
+}
+
 _lib = None
 
 
@@ -296,7 +312,7 @@ def load():
             "`make -C modulation_mfcc_amd/csrc` (needs hipcc, --offload-arch=gfx950). "
             "modulation_mfcc_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for table in (PROTOTYPES, PROTOTYPES_MODPSD, PROTOTYPES_MODCSD, PROTOTYPES_SPLINE, PROTOTYPES_LOMB):
+    for table in (PROTOTYPES, PROTOTYPES_MODPSD, PROTOTYPES_MODCSD, PROTOTYPES_SPLINE, PROTOTYPES_LOMB, PROTOTYPES_ZOOM):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError when the .so is stale
             fn.restype = res
