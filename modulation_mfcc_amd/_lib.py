@@ -292,18 +292,20 @@ PROTOTYPES_ZOOM = {
 }
 
 _lib = None
+_torch = None       # the torch module, bound by load(): call() and workspace() look nothing up per call
 
 
 def load():
     """Load libmodmfcc.so (once).  Raises ImportError -- never falls back to a CPU path."""
-    global _lib
+    global _lib, _torch
     if _lib is not None:
         return _lib
     # torch FIRST: its wheel bundles the HIP runtime (torch/lib/libamdhip64.so), libmodmfcc.so was linked against
     # /opt/rocm's.  Whichever is loaded first serves both (same SONAME); loaded the other way round the process
     # ends up with two runtimes and the second one finds no device ("hipGetDevice failed").
     try:
-        import torch  # noqa: F401
+        import torch
+        _torch = torch
     except ImportError:
         pass
     if not os.path.exists(LIB_PATH):
@@ -334,3 +336,42 @@ def check(status, what):
     if status == MM_ERR_UNSUPPORTED:
         raise NotImplementedError(f"{what}: {msg}")
     raise MMError(status, f"{what}: {msg}", detail)
+
+
+# ---- compute calls: every entry whose last parameter is ``void* stream`` goes through call() ----------------------------
+def torch_stream(dev=None):
+    """torch's current stream of ``dev`` (None: of the current device), read now -- the package's one such read."""
+    if _torch is None:
+        load()
+    return _torch.cuda.current_stream(dev)
+
+
+def call(name, dev, *args, ok=()):
+    """The compute entry ``name`` with ``args`` and, as its last argument, the current stream of ``dev``, read at call time
+    inside the device guard of ``dev`` (a tensor's device need not be the current one); the status goes through check().
+    A failure status listed in ``ok`` is returned unchecked: MM_ERR_UNSUPPORTED where the caller has another route.  The
+    entry is looked up on the loaded library at every call (an attribute ctypes caches)."""
+    lib = _lib or load()
+    with _torch.cuda.device(dev):
+        rc = getattr(lib, name)(*args, C.c_void_p(torch_stream(dev).cuda_stream))
+    if rc != MM_OK and rc not in ok:
+        check(rc, name)
+    return rc
+
+
+def workspace(nbytes, dev):
+    """``nbytes`` of scratch on ``dev`` for the calls of one function (a uint8 tensor; pointer and numel() go to the entry)."""
+    load()
+    return _torch.empty(int(nbytes), dtype=_torch.uint8, device=dev)
+
+
+def call_chunked(name, dev, rows, chunk, args, ws_bytes=None):
+    """The entry ``name`` over ``rows`` rows in calls of at most ``chunk``: ``args(r0, r)`` gives the arguments of the call
+    for the rows r0 .. r0 + r - 1.  With ``ws_bytes``, a function of the rows of one call, one workspace sized for ``chunk``
+    rows serves every call, appended to its arguments as (pointer, bytes)."""
+    tail = ()
+    if ws_bytes is not None:
+        ws = workspace(ws_bytes(chunk), dev)
+        tail = (ws.data_ptr(), ws.numel())
+    for r0 in range(0, rows, chunk):
+        call(name, dev, *args(r0, min(chunk, rows - r0)), *tail)

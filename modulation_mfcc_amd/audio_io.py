@@ -75,11 +75,6 @@ def read_wav_header(path):
                 data_bytes=size, n_frames=size // frame)
 
 
-def _stream(torch, dev):
-    import ctypes as C
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def load_wav(path, device=None):
     """WAVE file -> (float32 CUDA(HIP) tensor [channels, n] in [-1, 1), sample rate).  The data chunk is read
     as bytes, copied to the device and converted there."""
@@ -96,10 +91,7 @@ def load_wav(path, device=None):
     raw = np.fromfile(path, dtype=np.uint8, count=nbytes, offset=h["data_offset"])
     d_raw = torch.from_numpy(raw).to(dev)
     out = torch.empty((h["channels"], n), dtype=torch.float32, device=dev)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        _lib.check(lib.mm_pcm_decode_f32(d_raw.data_ptr(), h["fmt"], h["channels"], n, out.data_ptr(), n, _stream(torch, dev)),
-                   "mm_pcm_decode_f32")
+    _lib.call("mm_pcm_decode_f32", dev, d_raw.data_ptr(), h["fmt"], h["channels"], n, out.data_ptr(), n)
     return out, h["sr"]
 
 
@@ -258,7 +250,6 @@ def resample_batch(x, sr_in: float, sr_out: float, method: str = "auto"):
     order, ~1e-6 of full scale from the float64 sum); 'f64': the vector-pipe kernel with float64 accumulation
     (mm_resample_f32; also the fall-back for ratios whose period does not fit the LDS tile)."""
     import torch
-    from . import _lib
     if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32):
         raise TypeError("x must be a float32 CUDA(HIP) tensor")
     if method not in ("auto", "mfma", "f64"):
@@ -266,36 +257,34 @@ def resample_batch(x, sr_in: float, sr_out: float, method: str = "auto"):
     L, M = resample_ratio(sr_in, sr_out)
     if L == M:
         return x.clone()
-    squeeze = x.dim() == 1
-    x2 = x.unsqueeze(0) if squeeze else x
-    if x2.dim() != 2:
-        raise ValueError("x must be [n] or [rows, n]")
-    if x2.stride(1) != 1:
-        x2 = x2.contiguous()
-    rows, n = x2.shape
+    x2, squeeze = ragged.batch_rows(x, "x must be [n] or [rows, n]")
+    out = _resample(x2, x2.stride(0), L, M, method)
+    return out[0] if squeeze else out
+
+
+def _resample(x, pitch, L, M, method, d_lens=None):
+    """The resampler on checked rows [rows, n] of pitch ``pitch`` -> float32 [rows, ceil(n L / M)]: the banded entry, then
+    (method 'f64', or 'auto' where the banded entry answers MM_ERR_UNSUPPORTED) the float64 one per 65535 rows -- the
+    single-length entries (``d_lens`` None) or their _ragged twins, which also take the pitch of the output's valid part."""
+    import torch
+    from . import _lib
+    rows, n = x.shape
     n_out = -(-n * L // M)
     out = torch.empty((rows, n_out), dtype=torch.float32, device=x.device)
-    lib = _lib.load()
-    done = False
+    lens = ragged.lens_arg(d_lens)
+    form, valid = ("", ()) if d_lens is None else ("_ragged", (n_out,))
     if method != "f64":
         tb = _device_banded(L, M, x.device)
-        with torch.cuda.device(x.device):
-            rc = lib.mm_resample_banded_f32(x2.data_ptr(), rows, n, x2.stride(0), tb["d_atab"].data_ptr(), tb["d_lo_off"].data_ptr(),
-                                            tb["F"], tb["S"], tb["NB"], tb["ksteps"], tb["lo_min"], tb["win"], out.data_ptr(),
-                                            n_out, _stream(torch, x.device))
-        if rc == _lib.MM_ERR_UNSUPPORTED and method == "auto":
-            done = False
-        else:
-            _lib.check(rc, "mm_resample_banded_f32")
-            done = True
-    if not done:
-        taps, tpp, half = _device_taps(L, M, x.device)
-        with torch.cuda.device(x.device):
-            for r0 in range(0, rows, 65535):         # the kernel's grid takes the rows on its y axis
-                r = min(65535, rows - r0)
-                _lib.check(lib.mm_resample_f32(x2[r0:].data_ptr(), r, n, x2.stride(0), taps.data_ptr(), L, M, tpp, half,
-                                               out[r0:].data_ptr(), n_out, _stream(torch, x.device)), "mm_resample_f32")
-    return out[0] if squeeze else out
+        rc = _lib.call(f"mm_resample_banded{form}_f32", x.device, x.data_ptr(), rows, n, pitch, *lens, tb["d_atab"].data_ptr(),
+                       tb["d_lo_off"].data_ptr(), tb["F"], tb["S"], tb["NB"], tb["ksteps"], tb["lo_min"], tb["win"],
+                       out.data_ptr(), n_out, *valid, ok=(_lib.MM_ERR_UNSUPPORTED,) if method == "auto" else ())
+        if rc == _lib.MM_OK:
+            return out
+    taps, tpp, half = _device_taps(L, M, x.device)
+    _lib.call_chunked(f"mm_resample{form}_f32", x.device, rows, 65535,         # the kernel's grid takes the rows on its y axis
+                      lambda r0, r: (x[r0:].data_ptr(), r, n, pitch, *(() if d_lens is None else (d_lens[r0:].data_ptr(),)),
+                                     taps.data_ptr(), L, M, tpp, half, out[r0:].data_ptr(), n_out, *valid))
+    return out
 
 
 def load_audio(path, sr=None, device=None):
@@ -391,10 +380,8 @@ def decode_wav_batch(d_raw, d_tab, pl):
     R, n_max = int(pl["first_row"][-1]), pl["n_max"]
     pitch = -(-n_max // 4) * 4                                   # 16-byte aligned rows: vector stores here, vector staging later
     out = torch.empty((R, pitch), dtype=torch.float32, device=dev)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        _lib.check(lib.mm_pcm_decode_ragged_f32(d_raw.data_ptr(), pl["total_bytes"], d_tab.data_ptr(), len(pl["frames"]), n_max,
-                                                out.data_ptr(), R, pitch, _stream(torch, dev)), "mm_pcm_decode_ragged_f32")
+    _lib.call("mm_pcm_decode_ragged_f32", dev, d_raw.data_ptr(), pl["total_bytes"], d_tab.data_ptr(), len(pl["frames"]), n_max,
+              out.data_ptr(), R, pitch)
     return out[:, :n_max]
 
 
@@ -419,7 +406,6 @@ def resample_ragged_batch(x, lengths, sr_in: float, sr_out: float, method: str =
     'auto' falls back to the float64 kernel where the banded one does not apply, 'mfma' raises NotImplementedError
     there.  Equal rates return the valid parts copied, zeros behind them."""
     import torch
-    from . import _lib
     x = ragged.device_rows(x, (torch.float32,), "x must be a float32 CUDA(HIP) tensor", "x must be [rows, n_max] with rows, n_max >= 1")
     if method not in ("auto", "mfma", "f64"):
         raise ValueError("method must be 'auto', 'mfma' or 'f64'")
@@ -436,29 +422,7 @@ def resample_ragged_batch(x, lengths, sr_in: float, sr_out: float, method: str =
     if L == M:
         keep = torch.arange(n_max, device=x.device)[None, :] < d_lens.clamp(1, n_max)[:, None]
         return torch.where(keep, x, x.new_zeros(())), n_in
-    n_out = -(-n_max * L // M)
-    out = torch.empty((rows, n_out), dtype=torch.float32, device=x.device)
-    pitch = ragged.row_pitch(x)
-    lib = _lib.load()
-    done = False
-    if method != "f64":
-        tb = _device_banded(L, M, x.device)
-        with torch.cuda.device(x.device):
-            rc = lib.mm_resample_banded_ragged_f32(x.data_ptr(), rows, n_max, pitch, d_lens.data_ptr(), tb["d_atab"].data_ptr(),
-                                                   tb["d_lo_off"].data_ptr(), tb["F"], tb["S"], tb["NB"], tb["ksteps"],
-                                                   tb["lo_min"], tb["win"], out.data_ptr(), n_out, n_out, _stream(torch, x.device))
-        if not (rc == _lib.MM_ERR_UNSUPPORTED and method == "auto"):
-            _lib.check(rc, "mm_resample_banded_ragged_f32")
-            done = True
-    if not done:
-        taps, tpp, half = _device_taps(L, M, x.device)
-        with torch.cuda.device(x.device):
-            for r0 in range(0, rows, 65535):         # the kernel's grid takes the rows on its y axis
-                r = min(65535, rows - r0)
-                _lib.check(lib.mm_resample_ragged_f32(x[r0:].data_ptr(), r, n_max, pitch, d_lens[r0:].data_ptr(), taps.data_ptr(),
-                                                      L, M, tpp, half, out[r0:].data_ptr(), n_out, n_out,
-                                                      _stream(torch, x.device)), "mm_resample_ragged_f32")
-    return out, resample_out_lengths(n_in, L, M)
+    return _resample(x, ragged.row_pitch(x), L, M, method, d_lens), resample_out_lengths(n_in, L, M)
 
 
 def load_audio_batch(paths, sr=None, channel=0, device=None):

@@ -108,29 +108,36 @@ def rfft_batch(rows, n: int, cfg: MfccConfig = None, out=None):
     return get_plan(cfg or MfccConfig()).rfft(rows, n, out=out)
 
 
+def _rms(audio, pitch, frame_length, hop_length, center, n_out, d_lens=None):
+    """mm_rms_f32 (``d_lens`` None) or mm_rms_ragged_f32 on checked rows [B, n] -> [B, n_out] float32."""
+    import torch
+    from . import _lib
+    B, n = audio.shape
+    out = torch.empty((B, n_out), dtype=torch.float32, device=audio.device)
+    _lib.call("mm_rms_f32" if d_lens is None else "mm_rms_ragged_f32", audio.device, audio.data_ptr(), B, n, pitch,
+              *ragged.lens_arg(d_lens), frame_length, hop_length, center, out.data_ptr())
+    return out
+
+
+def _rms_frames(n, frame_length, hop_length, center):
+    from . import _lib
+    n_out = _lib.load().mm_rms_num_frames(n, frame_length, hop_length, center)
+    if n_out < 0:
+        _lib.check(int(n_out), "mm_rms_num_frames")
+    return n_out
+
+
 def rms_batch(audio, frame_length: int, hop_length: int, center: bool = True):
     """Framewise RMS on the device (row N3): [B, n] float32 CUDA(HIP) tensor -> [B, n_out], equal to
     librosa.feature.rms(y, frame_length=..., hop_length=..., center=..., pad_mode='constant') per
     clip (script/calc.py:331)."""
-    import ctypes as C
     import torch
-    from . import _lib
-    lib = _lib.load()
     if not (ragged.is_device_tensor(audio) and audio.dtype == torch.float32):
         raise TypeError("audio must be a float32 CUDA(HIP) tensor")
-    if audio.dim() == 1:
-        audio = audio.unsqueeze(0)
-    if audio.stride(1) != 1:
-        audio = audio.contiguous()
-    B, n = audio.shape
-    n_out = lib.mm_rms_num_frames(n, int(frame_length), int(hop_length), 1 if center else 0)
-    if n_out < 0:
-        _lib.check(int(n_out), "mm_rms_num_frames")
-    out = torch.empty((B, n_out), dtype=torch.float32, device=audio.device)
-    stream = C.c_void_p(torch.cuda.current_stream(audio.device).cuda_stream)
-    _lib.check(lib.mm_rms_f32(audio.data_ptr(), B, n, audio.stride(0), int(frame_length), int(hop_length),
-                              1 if center else 0, out.data_ptr(), stream), "mm_rms_f32")
-    return out
+    audio, _ = ragged.batch_rows(audio, "audio must be [n] or [B, n]")
+    frame_length, hop_length, center = int(frame_length), int(hop_length), 1 if center else 0
+    n_out = _rms_frames(audio.shape[1], frame_length, hop_length, center)
+    return _rms(audio, audio.stride(0), frame_length, hop_length, center, n_out)
 
 
 rms_ragged_frames = ragged.centered_frames      # RMS frames of clips of ``lengths`` samples: mm_rms_num_frames per clip
@@ -145,25 +152,14 @@ def rms_ragged_batch(audio, lengths, frame_length: int, hop_length: int, center:
     ``lengths``: host integers (validated: ValueError outside [1, n_max], and for a clip shorter than the frame without
     centring, the clip named) or an int64 device tensor (no read-back; the kernels clamp it, and a clip without a frame gets
     a NaN row).  One launch, that of n_max."""
-    import ctypes as C
     import torch
-    from . import _lib
-    lib = _lib.load()
     audio = ragged.device_rows(audio, (torch.float32,), "audio must be a float32 CUDA(HIP) tensor", "audio must be [B, n_max]",
                                nonempty=False)
     B, n = audio.shape
     lens = ragged.check_lengths(lengths, B, n, audio.device)
     frame_length, hop_length, center = int(frame_length), int(hop_length), 1 if center else 0
-    t_max = lib.mm_rms_num_frames(n, frame_length, hop_length, center)
-    if t_max < 0:
-        _lib.check(int(t_max), "mm_rms_num_frames")
+    t_max = _rms_frames(n, frame_length, hop_length, center)
     ragged.refuse_short(lens, n, 1 if center else frame_length,
                         lambda short: f"rms: a clip of {short} samples is shorter than frame_length={frame_length}", "clip", None)
-    out = torch.empty((B, t_max), dtype=torch.float32, device=audio.device)
-    with torch.cuda.device(audio.device):
-        lens_dev = ragged.counts_on_device(lens, audio.device)
-        stream = C.c_void_p(torch.cuda.current_stream(audio.device).cuda_stream)
-        _lib.check(lib.mm_rms_ragged_f32(audio.data_ptr(), B, n, ragged.row_pitch(audio),
-                                         lens_dev.data_ptr(), frame_length, hop_length, center, out.data_ptr(), stream),
-                   "mm_rms_ragged_f32")
-    return out
+    return _rms(audio, ragged.row_pitch(audio), frame_length, hop_length, center, t_max,
+                ragged.counts_on_device(lens, audio.device))

@@ -109,13 +109,9 @@ def rfft_rows_long(x, n_fft, out=None):
     lib = _lib.load()
     per_row = int(lib.mm_hilbert_rfft_workspace_bytes(plan.h, 1))
     chunk = int(max(1, min(rows, 65535, HILBERT_WS_BYTES // max(per_row, 1))))
-    ws = torch.empty(int(lib.mm_hilbert_rfft_workspace_bytes(plan.h, chunk)), dtype=torch.uint8, device=x.device)
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    with torch.cuda.device(x.device):
-        for r0 in range(0, rows, chunk):
-            r = min(chunk, rows - r0)
-            _lib.check(lib.mm_hilbert_rfft_f32(plan.h, x[r0:].data_ptr(), r, x.stride(0), T, out[r0:].data_ptr(),
-                                               ws.data_ptr(), ws.numel(), stream), "mm_hilbert_rfft_f32")
+    _lib.call_chunked("mm_hilbert_rfft_f32", x.device, rows, chunk,
+                      lambda r0, r: (plan.h, x[r0:].data_ptr(), r, x.stride(0), T, out[r0:].data_ptr()),
+                      lambda r: lib.mm_hilbert_rfft_workspace_bytes(plan.h, r))
     return out
 
 
@@ -128,17 +124,11 @@ def hilbert_envelope_batch(x):
     clip, 441 000, 480 000 ...) are transformed directly by the library's mixed-radix Stockham FFT, any other length
     through Bluestein's chirp-z identity over a power-of-two FFT (mm_hilbert_envelope, csrc/mm_hilbert.hip.inc);
     the constant tables of a length are built once and kept (LRU of HILBERT_MAX_PLANS lengths)."""
-    import ctypes as C
     import torch
     from . import _lib
     if not (ragged.is_device_tensor(x) and x.dtype in (torch.float32, torch.float64)):
         raise TypeError("x must be a float32 / float64 CUDA(HIP) tensor")
-    squeeze = x.dim() == 1
-    x2 = x.unsqueeze(0) if squeeze else x
-    if x2.dim() != 2:
-        raise ValueError("x must be [n] or [B, n]")
-    if x2.stride(1) != 1:
-        x2 = x2.contiguous()
+    x2, squeeze = ragged.batch_rows(x, "x must be [n] or [B, n]")
     rows, n = x2.shape
     out = torch.empty((rows, n), dtype=x.dtype, device=x.device)
     if n == 0 or rows == 0:
@@ -149,13 +139,9 @@ def hilbert_envelope_batch(x):
     # two clips share one complex transform: calls of an even number of clips, sized by what a PAIR needs
     per_pair = int(lib.mm_hilbert_workspace_bytes(plan.h, 2))
     chunk = max(1, min(rows, 65534, 2 * (HILBERT_WS_BYTES // per_pair)))
-    ws = torch.empty(int(lib.mm_hilbert_workspace_bytes(plan.h, chunk)), dtype=torch.uint8, device=x.device)
-    stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    with torch.cuda.device(x.device):
-        for r0 in range(0, rows, chunk):
-            r = min(chunk, rows - r0)
-            _lib.check(lib.mm_hilbert_envelope(plan.h, x2[r0:].data_ptr(), r, x2.stride(0), out[r0:].data_ptr(), n,
-                                               ws.data_ptr(), ws.numel(), stream), "mm_hilbert_envelope")
+    _lib.call_chunked("mm_hilbert_envelope", x.device, rows, chunk,
+                      lambda r0, r: (plan.h, x2[r0:].data_ptr(), r, x2.stride(0), out[r0:].data_ptr(), n),
+                      lambda r: lib.mm_hilbert_workspace_bytes(plan.h, r))
     return out[0] if squeeze else out
 
 
@@ -172,7 +158,6 @@ def _hilbert_ragged_classes(lens):
 def _hilbert_ragged_rows(x2, lens_dev, M):
     """mm_hilbert_envelope_ragged on x2 [rows, n_max] (unit inner stride) with device lengths, through the transform length
     ``M`` >= 2 n_max - 1 -> [rows, n_max]; the rows are cut into calls of at most HILBERT_WS_BYTES of workspace."""
-    import ctypes as C
     import torch
     from . import _lib
     rows, n = x2.shape
@@ -182,14 +167,10 @@ def _hilbert_ragged_rows(x2, lens_dev, M):
     out = torch.empty((rows, n), dtype=x2.dtype, device=x2.device)
     per_row = int(lib.mm_hilbert_ragged_workspace_bytes(plan.h, 1, n))
     chunk = int(max(1, min(rows, 65535, HILBERT_WS_BYTES // max(per_row, 1))))
-    ws = torch.empty(int(lib.mm_hilbert_ragged_workspace_bytes(plan.h, chunk, n)), dtype=torch.uint8, device=x2.device)
-    stream = C.c_void_p(torch.cuda.current_stream(x2.device).cuda_stream)
-    with torch.cuda.device(x2.device):
-        for r0 in range(0, rows, chunk):
-            r = min(chunk, rows - r0)
-            _lib.check(lib.mm_hilbert_envelope_ragged(plan.h, x2[r0:].data_ptr(), r, n, ragged.row_pitch(x2), lens_dev[r0:].data_ptr(),
-                                                      out[r0:].data_ptr(), n, ws.data_ptr(), ws.numel(), stream),
-                       "mm_hilbert_envelope_ragged")
+    _lib.call_chunked("mm_hilbert_envelope_ragged", x2.device, rows, chunk,
+                      lambda r0, r: (plan.h, x2[r0:].data_ptr(), r, n, ragged.row_pitch(x2), lens_dev[r0:].data_ptr(),
+                                     out[r0:].data_ptr(), n),
+                      lambda r: lib.mm_hilbert_ragged_workspace_bytes(plan.h, r, n))
     return out
 
 
@@ -496,17 +477,18 @@ def apply_stencil_ragged(x2, lens_dev, st, n_min: int = 0):
     stride, a length per row (``lens_dev``: int64 device tensor [rows]; mm_stencil_ragged_f64): row b equals
     apply_stencil on x2[b:b+1, :n_b] bit for bit in its first n_b columns and is +0.0 behind them; nothing at or behind n_b
     is read.  A row shorter than the operator takes (or than ``n_min``) comes out NaN."""
+    return _stencil(x2, _c_stencil(st, n_min), lens_dev)
+
+
+def _stencil(x2, cs, d_lens=None):
+    """One pass of the C stencil ``cs``: mm_stencil_f64 (``d_lens`` None) or mm_stencil_ragged_f64 -> float64 [rows, n]."""
     import ctypes as C
     import torch
     from . import _lib
     rows, n = x2.shape
-    cs = _c_stencil(st, n_min)
     out = torch.empty((rows, n), dtype=torch.float64, device=x2.device)
-    with torch.cuda.device(x2.device):
-        _lib.check(_lib.load().mm_stencil_ragged_f64(C.byref(cs), x2.data_ptr(), rows, n, ragged.row_pitch(x2),
-                                                     lens_dev.data_ptr(), out.data_ptr(),
-                                                     C.c_void_p(torch.cuda.current_stream(x2.device).cuda_stream)),
-                   "mm_stencil_ragged_f64")
+    _lib.call("mm_stencil_f64" if d_lens is None else "mm_stencil_ragged_f64", x2.device, C.byref(cs), x2.data_ptr(), rows, n,
+              ragged.row_pitch(x2), *ragged.lens_arg(d_lens), out.data_ptr())
     return out
 
 
@@ -514,20 +496,10 @@ def apply_stencil(x2, st, passes: int = 1):
     """Run the banded operator ``st`` (dict: off, c, den_c, n_edge, edge_w, el, er, den_e -- the fields of the C
     struct mm_stencil) ``passes`` times along the last axis of a float64 CUDA(HIP) tensor [rows, n] with unit
     inner stride (mm_stencil_f64)."""
-    import ctypes as C
-    import torch
-    from . import _lib
-    rows, n = x2.shape
     cs = _c_stencil(st)
-    lib = _lib.load()
-    stream = C.c_void_p(torch.cuda.current_stream(x2.device).cuda_stream)
-    with torch.cuda.device(x2.device):
-        src = x2
-        for _ in range(passes):
-            out = torch.empty((rows, n), dtype=torch.float64, device=x2.device)
-            _lib.check(lib.mm_stencil_f64(C.byref(cs), src.data_ptr(), rows, n, ragged.row_pitch(src),
-                                          out.data_ptr(), stream), "mm_stencil_f64")
-            src = out
+    src = x2
+    for _ in range(passes):
+        src = _stencil(src, cs)
     return src
 
 
@@ -553,12 +525,7 @@ def velocity_batch(x, sr: float, difference: int = 1, method: str = "gradient", 
             raise
         from .filters import savgol_batch       # windows beyond the stencil: mm_savgol_f64 (delta 1, as the reference calls it)
         return savgol_batch(x, width, polyOrder, deriv=difference, delta=1.0)
-    squeeze = x.dim() == 1
-    x2 = x.unsqueeze(0) if squeeze else x
-    if x2.dim() != 2:
-        raise ValueError("x must be [n] or [rows, n]")
-    if x2.stride(1) != 1:
-        x2 = x2.contiguous()
+    x2, squeeze = ragged.batch_rows(x, "x must be [n] or [rows, n]")
     rows, n = x2.shape
     if method == "sg" and n < len(st["c"]):       # scipy.signal.savgol_filter's own check and message
         raise ValueError(ragged.SG_WINDOW_TEXT)
@@ -722,10 +689,7 @@ def _find_peaks(x, negate, height, threshold, prominence, lo, hi, ext):
     from . import _lib
     if not (ragged.is_device_tensor(x) and x.dtype in (torch.float64, torch.float32)):
         raise TypeError("x must be a float64 (or float32) CUDA(HIP) tensor")
-    squeeze = x.dim() == 1
-    x2 = x.unsqueeze(0) if squeeze else x
-    if x2.dim() != 2:
-        raise ValueError("x must be [n] or [rows, n]")
+    x2, squeeze = ragged.batch_rows(x, "x must be [n] or [rows, n]", pitched=True)
     o = _lib.mm_peaks_opts()
     o.negate = 1 if negate else 0
     for name, v, field in (("height", height, o.height), ("threshold", threshold, o.threshold),
@@ -733,8 +697,6 @@ def _find_peaks(x, negate, height, threshold, prominence, lo, hi, ext):
         field[0], field[1] = _peak_interval(name, v) if v is not None else (-math.inf, math.inf)
         setattr(o, "use_" + name, 0 if v is None else 1)
     rows, n = x2.shape
-    if (x2.stride(1) != 1 and n > 1) or (rows > 1 and x2.stride(0) < n):
-        x2 = x2.contiguous()
     dev = x2.device
     d_lo, d_hi = _peak_range("lo", lo, rows, n, dev), _peak_range("hi", hi, rows, n, dev)
     cap = max(0, (n - 1) // 2)
@@ -754,14 +716,11 @@ def _find_peaks(x, negate, height, threshold, prominence, lo, hi, ext):
         lib = _lib.load()
         stride = ragged.row_pitch(x2)
         ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None   # noqa: E731
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         dtype = 0 if x2.dtype == torch.float32 else 1
         if ext is None:
-            ws = torch.empty(int(lib.mm_find_peaks_workspace_bytes(rows, n)), dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(lib.mm_find_peaks(C.byref(o), x2.data_ptr(), dtype, rows, n, stride, ptr(d_lo), ptr(d_hi), cap,
-                                             count.data_ptr(), ptr(idx), ptr(prom), ptr(lb), ptr(rb), ws.data_ptr(),
-                                             ws.numel(), stream), "mm_find_peaks")
+            ws = _lib.workspace(lib.mm_find_peaks_workspace_bytes(rows, n), dev)
+            _lib.call("mm_find_peaks", dev, C.byref(o), x2.data_ptr(), dtype, rows, n, stride, ptr(d_lo), ptr(d_hi), cap,
+                      count.data_ptr(), ptr(idx), ptr(prom), ptr(lb), ptr(rb), ws.data_ptr(), ws.numel())
         else:
             e = _lib.mm_peaks_ext()
             for name, use in (("plateau_size", plateau), ("width", widths)):
@@ -771,12 +730,9 @@ def _find_peaks(x, negate, height, threshold, prominence, lo, hi, ext):
             e.rel_height, e.wlen = ext["rel_height"], ext["wlen"]
             e.distance, e.use_distance = ext["distance"], 1 if ext["distance"] else 0
             out = _lib.mm_peaks_out(count.data_ptr(), ptr(idx), ptr(prom), ptr(lb), ptr(rb), *(ptr(t) for t in wout + pout))
-            ws = torch.empty(int(lib.mm_find_peaks_ex_workspace_bytes(C.byref(o), C.byref(e), rows, n)), dtype=torch.uint8,
-                             device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(lib.mm_find_peaks_ex(C.byref(o), C.byref(e), x2.data_ptr(), dtype, rows, n, stride, ptr(d_lo),
-                                                ptr(d_hi), cap, C.byref(out), ws.data_ptr(), ws.numel(), stream),
-                           "mm_find_peaks_ex")
+            ws = _lib.workspace(lib.mm_find_peaks_ex_workspace_bytes(C.byref(o), C.byref(e), rows, n), dev)
+            _lib.call("mm_find_peaks_ex", dev, C.byref(o), C.byref(e), x2.data_ptr(), dtype, rows, n, stride, ptr(d_lo),
+                      ptr(d_hi), cap, C.byref(out), ws.data_ptr(), ws.numel())
     if plateau:
         props["plateau_sizes"], props["left_edges"], props["right_edges"] = pout
     if height is not None or threshold is not None:

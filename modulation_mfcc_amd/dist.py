@@ -17,6 +17,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 
+from . import _lib
 from .plan import MfccConfig
 
 
@@ -129,10 +130,9 @@ class PipelinedGather:
         return (sum(ms) / len(ms) if ms else 0.0), len(ms)
 
     def acquire(self):
-        import torch
         i = self.k % self.depth
         if self._used[i]:
-            torch.cuda.current_stream().wait_event(self.ev_done[i])
+            _lib.torch_stream().wait_event(self.ev_done[i])
         return self.slabs[i]
 
     def submit(self, post=None):
@@ -141,7 +141,7 @@ class PipelinedGather:
         ``recv_block[i]``."""
         import torch
         i = self.k % self.depth
-        self.ev_ready[i].record(torch.cuda.current_stream())
+        self.ev_ready[i].record(_lib.torch_stream())
         with torch.cuda.stream(self.stream):
             self.stream.wait_event(self.ev_ready[i])
             timed = self._time_every and self.k % self._time_every == 0
@@ -159,8 +159,7 @@ class PipelinedGather:
         self.k += 1
 
     def finish(self):
-        import torch
-        torch.cuda.current_stream().wait_stream(self.stream)
+        _lib.torch_stream().wait_stream(self.stream)
 
 
 def mfcc_modspec_sharded(audio_all_or_local, cfg: MfccConfig, *, with_modspec=True, dst=0, group=None,

@@ -9,7 +9,6 @@ reference's, quirks included, computed with numpy on the host exactly as it writ
 """
 from __future__ import annotations
 
-import ctypes as C
 
 import numpy as np
 
@@ -68,11 +67,8 @@ def read_AG50x_arrays(path, target_sample_rate=200, device=None):
         y = torch.from_numpy(np.array(data)).to(dev)              # a writable copy: np.frombuffer's view is read-only
         t_in = torch.from_numpy(original_time).to(dev)
         t_out = torch.from_numpy(new_time).to(dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().mm_regrid_linear_f32_f64(y.data_ptr(), n, cols, cols, t_in.data_ptr(), t_out.data_ptr(), m,
-                                                            out.data_ptr(), cols,
-                                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                       "mm_regrid_linear_f32_f64")
+        _lib.call("mm_regrid_linear_f32_f64", dev, y.data_ptr(), n, cols, cols, t_in.data_ptr(), t_out.data_ptr(), m,
+                  out.data_ptr(), cols)
     return dict(ema=out, time=new_time, channels=np.arange(channels), dimensions=list(DIMENSIONS),
                 attrs=dict(device="AG50x", duration=new_time[-1], original_samplerate=h["samplerate"],
                            resampled_samplerate=target_sample_rate))

@@ -108,32 +108,36 @@ def sosfiltfilt_batch(x, sos):
     """scipy.signal.sosfiltfilt(sos, x) along the last axis of a float64 or float32 CUDA(HIP) tensor [rows, n] (or [n])
     on the device (mm_sosfiltfilt_f64 / _f32_f64): the recursion of applyFilter(filt='iir') for a whole batch of
     curves; float64 result, as scipy returns for either input type."""
-    import ctypes as C
     import torch
-    from . import _lib
     if not (ragged.is_device_tensor(x) and x.dtype in (torch.float64, torch.float32)):
         raise TypeError("x must be a float64 or float32 CUDA(HIP) tensor")
-    squeeze = x.dim() == 1
-    x2 = x.unsqueeze(0) if squeeze else x
-    if x2.dim() != 2:
-        raise ValueError("x must be [n] or [rows, n]")
-    if x2.stride(1) != 1:
-        x2 = x2.contiguous()
-    rows, n = x2.shape
+    x2, squeeze = ragged.batch_rows(x, "x must be [n] or [rows, n]")
     s = sos_sections(sos)
-    if n <= ragged.sos_padlen(s):   # scipy.signal.sosfiltfilt's own check and message
+    if x2.shape[1] <= ragged.sos_padlen(s):   # scipy.signal.sosfiltfilt's own check and message
         raise ValueError(ragged.PADLEN_TEXT.format(ragged.sos_padlen(s)))
-    lib = _lib.load()
-    out = torch.empty((rows, n), dtype=torch.float64, device=x.device)
-    ws = torch.empty(int(lib.mm_sosfiltfilt_workspace_bytes(rows, n)), dtype=torch.uint8, device=x.device)
-    # float32 rows (librosa's RMS envelope ...): scipy forms their odd extension in float32 before it upcasts -- so does
-    # mm_sosfiltfilt_f32_f64; the result is float64 either way
-    fn, name = (lib.mm_sosfiltfilt_f64, "mm_sosfiltfilt_f64") if x2.dtype == torch.float64 else \
-        (lib.mm_sosfiltfilt_f32_f64, "mm_sosfiltfilt_f32_f64")
-    with torch.cuda.device(x.device):
-        _lib.check(fn(x2.data_ptr(), rows, n, x2.stride(0), s.ctypes.data, s.shape[0], out.data_ptr(), ws.data_ptr(), ws.numel(),
-                      C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), name)
+    out = _sosfiltfilt(x2, x2.stride(0), s)
     return out[0] if squeeze else out
+
+
+def _f64_entry(x2, stem, d_lens):
+    """The name of a filter entry for rows of x2's type, single-length or ragged: float32 rows (librosa's RMS envelope ...)
+    go to the _f32_f64 entries, which form the odd extension in float32 before they upcast, as scipy does; the result is
+    float64 either way."""
+    import torch
+    return stem + ("" if d_lens is None else "_ragged") + ("_f64" if x2.dtype == torch.float64 else "_f32_f64")
+
+
+def _sosfiltfilt(x2, pitch, s, d_lens=None):
+    """mm_sosfiltfilt_f64 / _f32_f64 (``d_lens`` None) or their _ragged twins on checked rows -> float64 [rows, n]."""
+    import torch
+    from . import _lib
+    rows, n = x2.shape
+    sizer = "mm_sosfiltfilt_workspace_bytes" if d_lens is None else "mm_sosfiltfilt_ragged_workspace_bytes"
+    out = torch.empty((rows, n), dtype=torch.float64, device=x2.device)
+    ws = _lib.workspace(getattr(_lib.load(), sizer)(rows, n), x2.device)
+    _lib.call(_f64_entry(x2, "mm_sosfiltfilt", d_lens), x2.device, x2.data_ptr(), rows, n, pitch, *ragged.lens_arg(d_lens),
+              s.ctypes.data, s.shape[0], out.data_ptr(), ws.data_ptr(), ws.numel())
+    return out
 
 
 def fir_filtfilt_stencil(taps):
@@ -250,16 +254,32 @@ def savgol_tables(window_length, polyorder, deriv=0, delta=1.0):
     return c.astype(np.float64), phi.astype(np.float64), P.astype(np.float64)
 
 
-def _long_rows(x):
-    """[n] or [rows, n] -> ([rows, n] with unit inner stride and a row stride >= n: other layouts are copied, was 1-D)."""
-    squeeze = x.dim() == 1
-    x2 = x.unsqueeze(0) if squeeze else x
-    if x2.dim() != 2:
-        raise ValueError("x must be [n] or [rows, n]")
+def _fir_filtfilt(x2, b, d_lens=None):
+    """mm_fir_filtfilt_f64 / _f32_f64 (``d_lens`` None) or their _ragged twins on checked rows -> float64 [rows, n]."""
+    import torch
+    from . import _lib
     rows, n = x2.shape
-    if (n > 1 and x2.stride(1) != 1) or (rows > 1 and x2.stride(0) < n):
-        x2 = x2.contiguous()
-    return x2, squeeze
+    out = torch.empty((rows, n), dtype=torch.float64, device=x2.device)
+    if rows:
+        (h,) = _device_tables(("fir", b.tobytes()), x2.device, lambda: (fir_filtfilt_taps(b),))
+        _lib.call(_f64_entry(x2, "mm_fir_filtfilt", d_lens), x2.device, x2.data_ptr(), rows, n, ragged.row_pitch(x2),
+                  *ragged.lens_arg(d_lens), h.data_ptr(), len(b), out.data_ptr(), n)
+    return out
+
+
+def _savgol(x2, tables, W, p, was_f32, d_lens=None):
+    """mm_savgol_f64 (``d_lens`` None) or mm_savgol_ragged_f64 on checked float64 rows -> [rows, n], float32 again for rows
+    that were float32 (filtered in float64, rounded once)."""
+    import torch
+    from . import _lib
+    rows, n = x2.shape
+    c, q, pe = tables
+    out = torch.empty((rows, n), dtype=torch.float64, device=x2.device)
+    if rows:
+        _lib.call("mm_savgol_f64" if d_lens is None else "mm_savgol_ragged_f64", x2.device, x2.data_ptr(), rows, n,
+                  ragged.row_pitch(x2), *ragged.lens_arg(d_lens), c.data_ptr(), q.data_ptr(), pe.data_ptr(), W, p + 1,
+                  out.data_ptr(), n)
+    return out.float() if was_f32 else out
 
 
 def fir_filtfilt_batch(x, taps):
@@ -268,28 +288,17 @@ def fir_filtfilt_batch(x, taps):
     with the 2 L - 1 taps of fir_filtfilt_taps.  Rows may be strided (row stride >= n).  float64 result, as scipy returns
     for either input type; a float32 row's extension is formed in float32, as scipy forms it.  n <= 3 L raises scipy's
     ValueError."""
-    import ctypes as C
     import torch
-    from . import _lib
     if not (ragged.is_device_tensor(x) and x.dtype in (torch.float64, torch.float32)):
         raise TypeError("x must be a float64 or float32 CUDA(HIP) tensor")
     b = np.asarray(taps, dtype=np.float64).ravel()
     L = len(b)
     if L < 2:
         raise ValueError("fir_filtfilt_batch needs at least two taps")
-    x2, squeeze = _long_rows(x)
-    rows, n = x2.shape
-    if n <= 3 * L:      # scipy.signal.filtfilt's own check and message
+    x2, squeeze = ragged.batch_rows(x, "x must be [n] or [rows, n]", pitched=True)
+    if x2.shape[1] <= 3 * L:      # scipy.signal.filtfilt's own check and message
         raise ValueError(ragged.PADLEN_TEXT.format(3 * L))
-    out = torch.empty((rows, n), dtype=torch.float64, device=x.device)
-    if rows:
-        (h,) = _device_tables(("fir", b.tobytes()), x.device, lambda: (fir_filtfilt_taps(b),))
-        lib = _lib.load()
-        fn, name = (lib.mm_fir_filtfilt_f64, "mm_fir_filtfilt_f64") if x2.dtype == torch.float64 else \
-            (lib.mm_fir_filtfilt_f32_f64, "mm_fir_filtfilt_f32_f64")
-        with torch.cuda.device(x.device):
-            _lib.check(fn(x2.data_ptr(), rows, n, ragged.row_pitch(x2), h.data_ptr(), L, out.data_ptr(), n,
-                          C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), name)
+    out = _fir_filtfilt(x2, b)
     return out[0] if squeeze else out
 
 
@@ -298,39 +307,22 @@ def savgol_batch(x, window_length, polyorder, deriv=0, delta=1.0):
     of a float64 or float32 CUDA(HIP) tensor [rows, n] (or [n]) on the device, for ANY window_length <= n (mm_savgol_f64,
     tables: savgol_tables).  Rows may be strided.  A float32 tensor comes back float32, filtered in float64 and rounded
     once, as scipy does.  Bad arguments raise scipy's ValueErrors."""
-    import ctypes as C
     import torch
-    from . import _lib
     if not (ragged.is_device_tensor(x) and x.dtype in (torch.float64, torch.float32)):
         raise TypeError("x must be a float64 or float32 CUDA(HIP) tensor")
     W, p, deriv, delta = int(window_length), int(polyorder), int(deriv), float(delta)
-    c, q, pe = _device_tables(("sg", W, p, deriv, delta), x.device, lambda: savgol_tables(W, p, deriv, delta))
+    tables = _device_tables(("sg", W, p, deriv, delta), x.device, lambda: savgol_tables(W, p, deriv, delta))
     was_f32 = x.dtype == torch.float32
-    x2, squeeze = _long_rows(x.double() if was_f32 else x)
-    rows, n = x2.shape
-    if W > n:           # scipy.signal.savgol_filter's own check and message
+    x2, squeeze = ragged.batch_rows(x.double() if was_f32 else x, "x must be [n] or [rows, n]", pitched=True)
+    if W > x2.shape[1]:           # scipy.signal.savgol_filter's own check and message
         raise ValueError(ragged.SG_WINDOW_TEXT)
-    out = torch.empty((rows, n), dtype=torch.float64, device=x.device)
-    if rows:
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.load().mm_savgol_f64(x2.data_ptr(), rows, n, ragged.row_pitch(x2), c.data_ptr(),
-                                                 q.data_ptr(), pe.data_ptr(), W, p + 1, out.data_ptr(), n,
-                                                 C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)),
-                       "mm_savgol_f64")
-    if was_f32:
-        out = out.float()
+    out = _savgol(x2, tables, W, p, was_f32)
     return out[0] if squeeze else out
 
 
 def _stencil_rows(x, st):
-    import torch
     from .calc import apply_stencil
-    squeeze = x.dim() == 1
-    x2 = x.unsqueeze(0) if squeeze else x
-    if x2.dim() != 2:
-        raise ValueError("x must be [n] or [rows, n]")
-    if x2.stride(1) != 1:
-        x2 = x2.contiguous()
+    x2, squeeze = ragged.batch_rows(x, "x must be [n] or [rows, n]")
     y = apply_stencil(x2, st, 1)
     return y[0] if squeeze else y
 
@@ -413,25 +405,11 @@ def sosfiltfilt_ragged_batch(x, lengths, sos):
     end.  Host lengths at or below scipy's padlen raise scipy's ValueError with the row named; device lengths go through
     without a read-back (clamped into [1, n_max]; such a row comes out NaN before its length).  Up to 4 sections (more:
     NotImplementedError, the library's MM_ERR_UNSUPPORTED -- apply_filter_ragged_batch filters those per distinct length)."""
-    import ctypes as C
-    import torch
-    from . import _lib
     x2, lens = _ragged_args(x, lengths)
-    rows, n_max = x2.shape
     s = sos_sections(sos)
     padlen = ragged.sos_padlen(s)
-    ragged.refuse_short(lens, n_max, padlen + 1, ragged.PADLEN_TEXT.format(padlen))
-    lib = _lib.load()
-    d_lens = ragged.counts_on_device(lens, x.device)
-    out = torch.empty((rows, n_max), dtype=torch.float64, device=x.device)
-    ws = torch.empty(int(lib.mm_sosfiltfilt_ragged_workspace_bytes(rows, n_max)), dtype=torch.uint8, device=x.device)
-    fn, name = (lib.mm_sosfiltfilt_ragged_f64, "mm_sosfiltfilt_ragged_f64") if x2.dtype == torch.float64 else \
-        (lib.mm_sosfiltfilt_ragged_f32_f64, "mm_sosfiltfilt_ragged_f32_f64")
-    with torch.cuda.device(x.device):
-        _lib.check(fn(x2.data_ptr(), rows, n_max, ragged.row_pitch(x2), d_lens.data_ptr(), s.ctypes.data,
-                      s.shape[0], out.data_ptr(), ws.data_ptr(), ws.numel(),
-                      C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), name)
-    return out
+    ragged.refuse_short(lens, x2.shape[1], padlen + 1, ragged.PADLEN_TEXT.format(padlen))
+    return _sosfiltfilt(x2, ragged.row_pitch(x2), s, ragged.counts_on_device(lens, x.device))
 
 
 def fir_filtfilt_ragged_batch(x, lengths, taps):
@@ -439,26 +417,13 @@ def fir_filtfilt_ragged_batch(x, lengths, taps):
     float64 or float32 [rows, n_max] on the device, ``lengths`` as for sosfiltfilt_ragged_batch -> float64 [rows, n_max].
     The odd extension is staged about the row's own ends (a float32 row's in float32).  Host lengths <= 3 L raise scipy's
     ValueError with the row named; such a row comes out NaN with device lengths."""
-    import ctypes as C
-    import torch
-    from . import _lib
     x2, lens = _ragged_args(x, lengths)
-    rows, n_max = x2.shape
     b = np.asarray(taps, dtype=np.float64).ravel()
     L = len(b)
     if L < 2:
         raise ValueError("fir_filtfilt_ragged_batch needs at least two taps")
-    ragged.refuse_short(lens, n_max, 3 * L + 1, ragged.PADLEN_TEXT.format(3 * L))
-    d_lens = ragged.counts_on_device(lens, x.device)
-    out = torch.empty((rows, n_max), dtype=torch.float64, device=x.device)
-    (h,) = _device_tables(("fir", b.tobytes()), x.device, lambda: (fir_filtfilt_taps(b),))
-    lib = _lib.load()
-    fn, name = (lib.mm_fir_filtfilt_ragged_f64, "mm_fir_filtfilt_ragged_f64") if x2.dtype == torch.float64 else \
-        (lib.mm_fir_filtfilt_ragged_f32_f64, "mm_fir_filtfilt_ragged_f32_f64")
-    with torch.cuda.device(x.device):
-        _lib.check(fn(x2.data_ptr(), rows, n_max, ragged.row_pitch(x2), d_lens.data_ptr(), h.data_ptr(), L,
-                      out.data_ptr(), n_max, C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), name)
-    return out
+    ragged.refuse_short(lens, x2.shape[1], 3 * L + 1, ragged.PADLEN_TEXT.format(3 * L))
+    return _fir_filtfilt(x2, b, ragged.counts_on_device(lens, x.device))
 
 
 def savgol_ragged_batch(x, lengths, window_length, polyorder, deriv=0, delta=1.0):
@@ -466,26 +431,15 @@ def savgol_ragged_batch(x, lengths, window_length, polyorder, deriv=0, delta=1.0
     the device, ``lengths`` as for sosfiltfilt_ragged_batch -> [rows, n_max], float64, or float32 for a float32 x (filtered
     in float64, rounded once).  The edge polynomials are fitted to the row's own first and last window.  Host lengths below
     the window raise scipy's ValueError with the row named; such a row comes out NaN with device lengths."""
-    import ctypes as C
     import torch
-    from . import _lib
     x2, lens = _ragged_args(x, lengths)
     W, p, deriv, delta = int(window_length), int(polyorder), int(deriv), float(delta)
-    rows, n_max = x2.shape
-    ragged.refuse_short(lens, n_max, W, ragged.SG_WINDOW_TEXT)
-    c, q, pe = _device_tables(("sg", W, p, deriv, delta), x.device, lambda: savgol_tables(W, p, deriv, delta))
+    ragged.refuse_short(lens, x2.shape[1], W, ragged.SG_WINDOW_TEXT)
+    tables = _device_tables(("sg", W, p, deriv, delta), x.device, lambda: savgol_tables(W, p, deriv, delta))
     was_f32 = x2.dtype == torch.float32
     if was_f32:
         x2 = x2.double()        # (the padding converts with the rows; it is never read)
-    d_lens = ragged.counts_on_device(lens, x.device)
-    out = torch.empty((rows, n_max), dtype=torch.float64, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().mm_savgol_ragged_f64(x2.data_ptr(), rows, n_max, ragged.row_pitch(x2),
-                                                    d_lens.data_ptr(), c.data_ptr(), q.data_ptr(), pe.data_ptr(), W, p + 1,
-                                                    out.data_ptr(), n_max,
-                                                    C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)),
-                   "mm_savgol_ragged_f64")
-    return out.float() if was_f32 else out
+    return _savgol(x2, tables, W, p, was_f32, ragged.counts_on_device(lens, x.device))
 
 
 def _apply_filter_per_length(x, lens, sr, kw):

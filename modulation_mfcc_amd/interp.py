@@ -15,7 +15,6 @@ body, ``_fill``.
 from __future__ import annotations
 
 import collections
-import ctypes as C
 
 import numpy as np
 from scipy import interpolate
@@ -121,10 +120,9 @@ def _fill(xd, pitch, counts, m):
         lib = _lib.load()
         args = [xd.data_ptr(), rows, n, pitch] + ([] if cd is None else [cd.data_ptr()]) + [y.data_ptr(), n]
         if m.workspace is not None:
-            ws = torch.empty(int(getattr(lib, m.workspace)(kind, rows, n)), dtype=torch.uint8, device=dev)
+            ws = _lib.workspace(getattr(lib, m.workspace)(kind, rows, n), dev)
             args = [kind] + args + [ws.data_ptr(), ws.numel()]
-        name = m.entry if cd is None else m.ragged_entry
-        _lib.check(getattr(lib, name)(*args, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), name)
+        _lib.call(m.entry if cd is None else m.ragged_entry, dev, *args)
     return y
 
 

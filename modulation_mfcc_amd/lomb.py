@@ -13,7 +13,6 @@ the samples it has.  There is no host fallback.
 """
 from __future__ import annotations
 
-import ctypes as C
 
 import numpy as np
 
@@ -119,12 +118,10 @@ def _run(xd, cd, t, fs, f, precenter, normalize, floating_mean):
         need = int(lib.mm_lombscargle_workspace_bytes(rows, n_max, nf))
         if need == 0:
             raise ValueError(f"modulation_lombscargle: [{rows}, {n_max}] rows x {nf} frequencies is beyond the kernel's limits")
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        _lib.check(lib.mm_lombscargle_f64(xd.data_ptr(), rows, n_max, ragged.row_pitch(xd),
-                                          None if cd is None else cd.data_ptr(), td.data_ptr(), od.data_ptr(), nf, flags,
-                                          out[0].data_ptr(), nf, out[1].data_ptr() if amplitude else None, ws.data_ptr(),
-                                          ws.numel(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                   "mm_lombscargle_f64")
+        ws = _lib.workspace(need, dev)
+        _lib.call("mm_lombscargle_f64", dev, xd.data_ptr(), rows, n_max, ragged.row_pitch(xd),
+                  None if cd is None else cd.data_ptr(), td.data_ptr(), od.data_ptr(), nf, flags, out[0].data_ptr(), nf,
+                  out[1].data_ptr() if amplitude else None, ws.data_ptr(), ws.numel())
         return torch.complex(out[0], out[1]) if amplitude else out[0]
 
 

@@ -70,7 +70,6 @@ def _rows(t, n):
 def _run(spec, x2, y2, group, lens_dev, want):
     """mm_modcsd_f32 on x2 [rows, n], y2 [rows / group, n] on the current stream -> [Pxx, Pyy, Pxy, Cxy], None for an
     output ``want`` does not ask for (its pointer is NULL: not computed, not stored)."""
-    import ctypes as C
     import torch
     from . import _lib
     lib = _lib.load()
@@ -81,13 +80,10 @@ def _run(spec, x2, y2, group, lens_dev, want):
     if rows:
         plan = modpsd._modpsd_plan(spec, dev)
         need = int(lib.mm_modcsd_workspace_bytes(plan.h, rows, n))
-        ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(lib.mm_modcsd_f32(plan.h, x2.data_ptr(), rows, n, ragged.row_pitch(x2), y2.data_ptr(),
-                                         ragged.row_pitch(y2), group, None if lens_dev is None else lens_dev.data_ptr(),
-                                         *[None if o is None else o.data_ptr() for o in outs], spec.bins,
-                                         None if ws is None else ws.data_ptr(), need, stream), "mm_modcsd_f32")
+        ws = _lib.workspace(need, dev) if need else None
+        _lib.call("mm_modcsd_f32", dev, plan.h, x2.data_ptr(), rows, n, ragged.row_pitch(x2), y2.data_ptr(),
+                  ragged.row_pitch(y2), group, None if lens_dev is None else lens_dev.data_ptr(),
+                  *[None if o is None else o.data_ptr() for o in outs], spec.bins, None if ws is None else ws.data_ptr(), need)
     if outs[2] is not None:
         outs[2] = torch.view_as_complex(outs[2])
     return outs

@@ -141,7 +141,6 @@ def _modpsd_plan(spec, device):
 
 def _run(spec, x2, lens_dev):
     """mm_modpsd_f32 on x2 [rows, n_max] (unit inner stride) on the current stream -> Pxx [rows, bins] float32."""
-    import ctypes as C
     import torch
     from . import _lib
     lib = _lib.load()
@@ -152,12 +151,10 @@ def _run(spec, x2, lens_dev):
         return out
     plan = _modpsd_plan(spec, dev)
     need = int(lib.mm_modpsd_workspace_bytes(plan.h, rows, n))
-    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.mm_modpsd_f32(plan.h, x2.data_ptr(), rows, n, ragged.row_pitch(x2),
-                                     None if lens_dev is None else lens_dev.data_ptr(), out.data_ptr(), spec.bins,
-                                     None if ws is None else ws.data_ptr(), need, stream), "mm_modpsd_f32")
+    ws = _lib.workspace(need, dev) if need else None
+    _lib.call("mm_modpsd_f32", dev, plan.h, x2.data_ptr(), rows, n, ragged.row_pitch(x2),
+              None if lens_dev is None else lens_dev.data_ptr(), out.data_ptr(), spec.bins,
+              None if ws is None else ws.data_ptr(), need)
     return out
 
 

@@ -244,8 +244,6 @@ def pyin_batch(audio, sr, *, fmin, fmax, frame_length=2048, win_length=None, hop
     """librosa.pyin on every row of a device batch -> (f0 float64, voiced_flag bool, voiced_prob float64), each
     [B, n_frames] (or [n_frames] for a [n] input), on the input's device.  ``return_states`` adds the decoded Viterbi
     states (int32; state < n_bins is voiced).  Batches are cut so that one call's scratch stays within PYIN_WS_BYTES."""
-    import torch
-    from . import _lib
     x, squeeze = _as_signal(audio)
     if center and pad_mode != "constant":
         x = _pad_center(x, frame_length, pad_mode)
@@ -255,33 +253,45 @@ def pyin_batch(audio, sr, *, fmin, fmax, frame_length=2048, win_length=None, hop
                        hop_length=hop_length, n_thresholds=n_thresholds, resolution=resolution,
                        max_transition_rate=max_transition_rate, switch_prob=switch_prob, no_trough_prob=no_trough_prob,
                        fill_na=fill_na, center=center)
-    T = z["n_frames"]
-    if T < 1:
+    if z["n_frames"] < 1:
         raise ValueError(f"pyin: a signal of {n} samples is shorter than frame_length={frame_length}")
-    lib = _lib.load()
-    tabs = _tables(p, z, switch_prob, beta_parameters, boltzmann_parameter, x.device)
-    p.band_h = tabs.H
-    dev = x.device
-    f0 = torch.empty((B, T), dtype=torch.float64, device=dev)
-    voiced = torch.empty((B, T), dtype=torch.uint8, device=dev)
-    vprob = torch.empty((B, T), dtype=torch.float64, device=dev)
-    states = torch.empty((B, T), dtype=torch.int32, device=dev)
-    rows = B
-    while rows > 1 and lib.mm_pyin_workspace_bytes(C.byref(p), rows, n) > PYIN_WS_BYTES:
-        rows = max(1, min(rows - 1, rows * PYIN_WS_BYTES // lib.mm_pyin_workspace_bytes(C.byref(p), rows, n)))
-    ws = torch.empty(int(lib.mm_pyin_workspace_bytes(C.byref(p), rows, n)), dtype=torch.uint8, device=dev)
-    fn, name = (lib.mm_pyin_f32, "mm_pyin_f32") if x.dtype == torch.float32 else (lib.mm_pyin_f64, "mm_pyin_f64")
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        for r0 in range(0, B, rows):
-            r = min(rows, B - r0)
-            _lib.check(fn(C.byref(p), C.byref(tabs.c), x[r0].data_ptr(), r, n, ragged.row_pitch(x), f0[r0].data_ptr(),
-                          voiced[r0].data_ptr(), vprob[r0].data_ptr(), states[r0].data_ptr(), ws.data_ptr(), ws.numel(),
-                          stream), name)
+    tabs, f0, voiced, vprob, states, _ = _pyin(x, p, z, switch_prob, beta_parameters, boltzmann_parameter)
     if fill_na is None:                 # librosa keeps the decoded bin's frequency on unvoiced frames
         f0 = tabs.dev["freqs"][(states % z["n_bins"]).long()]
     out = (f0, voiced.bool(), vprob) + ((states,) if return_states else ())
     return tuple(o[0] for o in out) if squeeze else out
+
+
+def _pyin(x, p, z, switch_prob, beta_parameters, boltzmann_parameter, d_lens=None):
+    """mm_pyin_f32 / _f64 (``d_lens`` None) or their _ragged twins on checked rows [B, n] with validated parameters, in
+    calls whose scratch stays within PYIN_WS_BYTES -> (the device tables, f0, voiced uint8, voiced_prob, states, each
+    [B, n_frames], and the ragged entries' frames [B], else None)."""
+    import torch
+    from . import _lib
+    lib = _lib.load()
+    B, n = x.shape
+    T, dev = z["n_frames"], x.device
+    tabs = _tables(p, z, switch_prob, beta_parameters, boltzmann_parameter, dev)
+    p.band_h = tabs.H
+    f0 = torch.empty((B, T), dtype=torch.float64, device=dev)
+    voiced = torch.empty((B, T), dtype=torch.uint8, device=dev)
+    vprob = torch.empty((B, T), dtype=torch.float64, device=dev)
+    states = torch.empty((B, T), dtype=torch.int32, device=dev)
+    frames = None if d_lens is None else torch.empty(B, dtype=torch.int64, device=dev)
+    form = "" if d_lens is None else "_ragged"
+    need = getattr(lib, f"mm_pyin{form}_workspace_bytes")
+    rows = B
+    while rows > 1 and need(C.byref(p), rows, n) > PYIN_WS_BYTES:
+        rows = max(1, min(rows - 1, rows * PYIN_WS_BYTES // need(C.byref(p), rows, n)))
+    pitch = ragged.row_pitch(x)
+
+    def args(r0, r):
+        lens, counted = ((), ()) if d_lens is None else ((d_lens[r0:].data_ptr(),), (frames[r0:].data_ptr(),))
+        return (C.byref(p), C.byref(tabs.c), x[r0].data_ptr(), r, n, pitch, *lens, f0[r0].data_ptr(), voiced[r0].data_ptr(),
+                vprob[r0].data_ptr(), states[r0].data_ptr(), *counted)
+    _lib.call_chunked(f"mm_pyin{form}_f32" if x.dtype == torch.float32 else f"mm_pyin{form}_f64", dev, B, rows, args,
+                      lambda r: need(C.byref(p), r, n))
+    return tabs, f0, voiced, vprob, states, frames
 
 
 pyin_ragged_frames = ragged.centered_frames     # frames of clips of ``lengths`` samples: mm_pyin_num_frames per clip
@@ -305,7 +315,6 @@ def pyin_ragged_batch(audio, lengths, sr, *, fmin, fmax, frame_length=2048, win_
     lengths: every clip is padded alone and the batch is packed again.  The scratch follows T_max, not the sum of the
     clips' frames; batches are cut to PYIN_WS_BYTES as in pyin_batch."""
     import torch
-    from . import _lib
     x, _ = _as_signal(audio)
     if audio.dim() != 2:
         raise ValueError("audio must be [B, n_max]")
@@ -324,37 +333,13 @@ def pyin_ragged_batch(audio, lengths, sr, *, fmin, fmax, frame_length=2048, win_
                        hop_length=hop_length, n_thresholds=n_thresholds, resolution=resolution,
                        max_transition_rate=max_transition_rate, switch_prob=switch_prob, no_trough_prob=no_trough_prob,
                        fill_na=fill_na, center=center)
-    T = z["n_frames"]
-    if T < 1:
+    if z["n_frames"] < 1:
         raise ValueError(_MSG_SHORT.format(n, frame_length))
     ragged.refuse_short(lens, n, 1 if center else frame_length, lambda short: _MSG_SHORT.format(short, frame_length), "clip", None)
-    lib = _lib.load()
-    dev = x.device
-    tabs = _tables(p, z, switch_prob, beta_parameters, boltzmann_parameter, dev)
-    p.band_h = tabs.H
-    f0 = torch.empty((B, T), dtype=torch.float64, device=dev)
-    voiced = torch.empty((B, T), dtype=torch.uint8, device=dev)
-    vprob = torch.empty((B, T), dtype=torch.float64, device=dev)
-    states = torch.empty((B, T), dtype=torch.int32, device=dev)
-    frames = torch.empty(B, dtype=torch.int64, device=dev)
-    need = lib.mm_pyin_ragged_workspace_bytes
-    rows = B
-    while rows > 1 and need(C.byref(p), rows, n) > PYIN_WS_BYTES:
-        rows = max(1, min(rows - 1, rows * PYIN_WS_BYTES // need(C.byref(p), rows, n)))
-    ws = torch.empty(int(need(C.byref(p), rows, n)), dtype=torch.uint8, device=dev)
-    f32 = x.dtype == torch.float32
-    name = "mm_pyin_ragged_f32" if f32 else "mm_pyin_ragged_f64"
-    with torch.cuda.device(dev):
-        lens_dev = ragged.counts_on_device(lens, dev)       # (on the current stream)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        for r0 in range(0, B, rows):
-            r = min(rows, B - r0)
-            fn = lib.mm_pyin_ragged_f32 if f32 else lib.mm_pyin_ragged_f64
-            _lib.check(fn(C.byref(p), C.byref(tabs.c), x[r0].data_ptr(), r, n, ragged.row_pitch(x), lens_dev[r0:].data_ptr(),
-                          f0[r0].data_ptr(), voiced[r0].data_ptr(), vprob[r0].data_ptr(), states[r0].data_ptr(),
-                          frames[r0:].data_ptr(), ws.data_ptr(), ws.numel(), stream), name)
+    tabs, f0, voiced, vprob, states, frames = _pyin(x, p, z, switch_prob, beta_parameters, boltzmann_parameter,
+                                                    ragged.counts_on_device(lens, x.device))
     if fill_na is None:                 # librosa keeps the decoded bin's frequency on unvoiced frames: of real frames only
-        live = torch.arange(T, device=dev)[None, :] < frames[:, None]
+        live = torch.arange(z["n_frames"], device=x.device)[None, :] < frames[:, None]
         f0 = tabs.dev["freqs"][(states % z["n_bins"]).long()] * live
     return (f0, voiced.bool(), vprob, frames) + ((states,) if return_states else ())
 
@@ -369,10 +354,8 @@ def pyin_cmnd(audio, sr, *, fmin, fmax, frame_length=2048, win_length=None, hop_
     p, z = pyin_params(n, sr, fmin=fmin, fmax=fmax, frame_length=frame_length, win_length=win_length,
                        hop_length=hop_length, center=center)
     out = torch.empty((B, z["n_frames"], z["max_period"] - z["min_period"] + 1), dtype=torch.float64, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().mm_pyin_cmnd(C.byref(p), x.data_ptr(), 0 if x.dtype == torch.float32 else 1, B, n,
-                                            ragged.row_pitch(x), out.data_ptr(),
-                                            C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), "mm_pyin_cmnd")
+    _lib.call("mm_pyin_cmnd", x.device, C.byref(p), x.data_ptr(), 0 if x.dtype == torch.float32 else 1, B, n,
+              ragged.row_pitch(x), out.data_ptr())
     return out[0] if squeeze else out
 
 
@@ -396,11 +379,8 @@ def pyin_records(cmnd, sr, *, fmin, fmax, frame_length=2048, win_length=None, ho
     bins = torch.zeros((T, R), dtype=torch.int32, device=dev)
     probs = torch.zeros((T, R), dtype=torch.float64, device=dev)
     vp = torch.empty(T, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().mm_pyin_candidates(C.byref(p), C.byref(tabs.c), c.data_ptr(), T, count.data_ptr(),
-                                                  bins.data_ptr(), probs.data_ptr(), vp.data_ptr(),
-                                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                   "mm_pyin_candidates")
+    _lib.call("mm_pyin_candidates", dev, C.byref(p), C.byref(tabs.c), c.data_ptr(), T, count.data_ptr(), bins.data_ptr(),
+              probs.data_ptr(), vp.data_ptr())
     return count, bins, probs, vp
 
 

@@ -186,7 +186,12 @@ class MfccPlan:
 
     # ---- helpers ----------------------------------------------------------------------
     def _stream(self):
-        return C.c_void_p(_torch().cuda.current_stream(self.device).cuda_stream)
+        """The stream _lib.call passes, for callers that go to the C ABI themselves."""
+        return C.c_void_p(_lib.torch_stream(self.device).cuda_stream)
+
+    def _call(self, name, *args, ok=()):
+        """The plan's entry ``name`` (handle first, stream last) on the plan's device."""
+        return _lib.call(name, self.device, self._h, *args, ok=ok)
 
     def _check_audio(self, audio):
         torch = _torch()
@@ -216,6 +221,26 @@ class MfccPlan:
             raise ValueError(f"{what}: out must be a contiguous {dtype} tensor of shape {tuple(shape)}, "
                              f"got {out.dtype} {tuple(out.shape)} (contiguous: {out.is_contiguous()})")
         return out
+
+    def _out(self, out, shape, dtype, what):
+        """The output of a call: a new tensor, or the caller's, checked."""
+        if out is None:
+            return _torch().empty(shape, dtype=dtype, device=self.device)
+        return self._check_out(out, shape, dtype, what)
+
+    def _outputs(self, B, T, out, out_mod, nm):
+        """(MFCC [B, n_mfcc, T] float32, modulation spectrum [B, n_mfcc, nm / 2 + 1] complex64 -- None when nm is 0)."""
+        torch = _torch()
+        out = self._out(out, (B, self.cfg.n_mfcc, T), torch.float32, "mfcc")
+        if nm:
+            out_mod = self._out(out_mod, (B, self.cfg.n_mfcc, nm // 2 + 1), torch.complex64, "modspec")
+        return out, out_mod
+
+    def _check_mfcc(self, mfcc):
+        torch = _torch()
+        if not (ragged.is_device_tensor(mfcc) and mfcc.dtype == torch.float32
+                and mfcc.dim() == 3 and mfcc.shape[1] == self.cfg.n_mfcc):
+            raise TypeError("mfcc must be a float32 CUDA(HIP) tensor [B, n_mfcc, T]")
 
     def workspace(self, batch, n_samples):
         torch = _torch()
@@ -277,46 +302,28 @@ class MfccPlan:
     # ---- compute ------------------------------------------------------------------------
     def mfcc(self, audio, out=None):
         """[B, n] float32 device tensor -> [B, n_mfcc, T] float32 (librosa layout per clip)."""
-        torch = _torch()
         audio = self._check_audio(audio)
         B, n = audio.shape
-        T = self.cfg.num_frames(n)
-        if out is None:
-            out = torch.empty((B, self.cfg.n_mfcc, T), dtype=torch.float32, device=self.device)
-        else:
-            self._check_out(out, (B, self.cfg.n_mfcc, T), torch.float32, "mfcc")
+        out, _ = self._outputs(B, self.cfg.num_frames(n), out, None, 0)
         ws = self.workspace(B, n)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.mm_mfcc_f32(self._h, audio.data_ptr(), B, n, audio.stride(0),
-                                             out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
-                       "mm_mfcc_f32")
+        self._call("mm_mfcc_f32", audio.data_ptr(), B, n, audio.stride(0), out.data_ptr(), ws.data_ptr(), ws.numel())
         return out
 
     def mfcc_modspec(self, audio, out=None, out_mod=None):
         """[B, n] float32 device tensor -> (MFCC [B, n_mfcc, T] float32, modulation spectrum complex64
         [B, n_mfcc, n_mod/2+1]): mfcc() followed by modspec() (MFCC bit for bit, spectrum to float32 round-off), in
         one launch where the plan can (fused_tail())."""
-        torch = _torch()
         audio = self._check_audio(audio)
         B, n = audio.shape
         T = self.cfg.num_frames(n)
         nm = self.cfg.mod_fft_len(T)
-        if out is None:
-            out = torch.empty((B, self.cfg.n_mfcc, T), dtype=torch.float32, device=self.device)
-        else:
-            self._check_out(out, (B, self.cfg.n_mfcc, T), torch.float32, "mfcc")
-        if out_mod is None:
-            out_mod = torch.empty((B, self.cfg.n_mfcc, nm // 2 + 1), dtype=torch.complex64, device=self.device)
-        else:
-            self._check_out(out_mod, (B, self.cfg.n_mfcc, nm // 2 + 1), torch.complex64, "modspec")
+        out, out_mod = self._outputs(B, T, out, out_mod, nm)
         if nm > 8192:
             self.mfcc(audio, out=out)
             return out, self.modspec(out, out=out_mod)
         ws = self.workspace(B, n)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.mm_mfcc_modspec_f32(self._h, audio.data_ptr(), B, n, audio.stride(0), out.data_ptr(),
-                                                     out_mod.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
-                       "mm_mfcc_modspec_f32")
+        self._call("mm_mfcc_modspec_f32", audio.data_ptr(), B, n, audio.stride(0), out.data_ptr(), out_mod.data_ptr(),
+                   ws.data_ptr(), ws.numel())
         return out, out_mod
 
     # ---- ragged batches: a padded batch and a length per clip -----------------------------------
@@ -341,28 +348,16 @@ class MfccPlan:
         return lens, ragged.stft_frames(lens.clamp(1, n), n_fft, hop)
 
     def _ragged(self, audio, lengths, out, out_mod, want_mod):
-        torch = _torch()
         audio = self._check_audio(audio)
         B, n = audio.shape
         T = self.cfg.num_frames(n)
         lens, frames = self._ragged_lengths(lengths, B, n)
-        if out is None:
-            out = torch.empty((B, self.cfg.n_mfcc, T), dtype=torch.float32, device=self.device)
-        else:
-            self._check_out(out, (B, self.cfg.n_mfcc, T), torch.float32, "mfcc")
         nm = self.cfg.mod_fft_len(T) if want_mod else 0
-        if want_mod:
-            if out_mod is None:
-                out_mod = torch.empty((B, self.cfg.n_mfcc, nm // 2 + 1), dtype=torch.complex64, device=self.device)
-            else:
-                self._check_out(out_mod, (B, self.cfg.n_mfcc, nm // 2 + 1), torch.complex64, "modspec")
+        out, out_mod = self._outputs(B, T, out, out_mod, nm)
         fused_mod = want_mod and nm <= 8192
         ws = self.ragged_workspace(B, n)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.mm_mfcc_ragged_f32(self._h, audio.data_ptr(), B, n, audio.stride(0), lens.data_ptr(),
-                                                    out.data_ptr(), out_mod.data_ptr() if fused_mod else None,
-                                                    ws.data_ptr(), ws.numel(), self._stream()),
-                       "mm_mfcc_ragged_f32")
+        self._call("mm_mfcc_ragged_f32", audio.data_ptr(), B, n, audio.stride(0), lens.data_ptr(), out.data_ptr(),
+                   out_mod.data_ptr() if fused_mod else None, ws.data_ptr(), ws.numel())
         if want_mod and not fused_mod:
             self.modspec(out, out=out_mod)      # more than 8192 frames per clip: the transform in global memory
         return out, out_mod, frames
@@ -445,9 +440,7 @@ class MfccPlan:
         T = self.cfg.num_frames(n)
         lm = torch.empty((B, self.cfg.n_mels, T), dtype=torch.float32, device=self.device)
         mx = torch.empty((B,), dtype=torch.float32, device=self.device)
-        _lib.check(self._lib.mm_logmel_f32(self._h, audio.data_ptr(), B, n, audio.stride(0),
-                                           lm.data_ptr(), mx.data_ptr(), self._stream()),
-                   "mm_logmel_f32")
+        self._call("mm_logmel_f32", audio.data_ptr(), B, n, audio.stride(0), lm.data_ptr(), mx.data_ptr())
         return lm, mx
 
     def stft_power(self, audio):
@@ -457,8 +450,7 @@ class MfccPlan:
         B, n = audio.shape
         T = self.cfg.num_frames(n)
         out = torch.empty((B, T, self.cfg.n_bins), dtype=torch.float32, device=self.device)
-        _lib.check(self._lib.mm_stft_power_f32(self._h, audio.data_ptr(), B, n, audio.stride(0),
-                                               out.data_ptr(), self._stream()), "mm_stft_power_f32")
+        self._call("mm_stft_power_f32", audio.data_ptr(), B, n, audio.stride(0), out.data_ptr())
         return out
 
     def rfft(self, rows, n, out=None):
@@ -472,20 +464,14 @@ class MfccPlan:
         R, L = rows.shape
         if rows.device != self.device:
             raise ValueError(f"rows is on {rows.device}, the plan on {self.device}")
-        if out is None:
-            out = torch.empty((R, n // 2 + 1), dtype=torch.complex64, device=self.device)
-        else:
-            self._check_out(out, (R, n // 2 + 1), torch.complex64, "rfft")
-        _lib.check(self._lib.mm_rfft_f32(self._h, rows.data_ptr(), R, L, rows.stride(0), int(n),
-                                         out.data_ptr(), self._stream()), "mm_rfft_f32")
+        out = self._out(out, (R, n // 2 + 1), torch.complex64, "rfft")
+        self._call("mm_rfft_f32", rows.data_ptr(), R, L, rows.stride(0), int(n), out.data_ptr())
         return out
 
     def modspec(self, mfcc, out=None):
         """[B, n_mfcc, T] -> complex64 [B, n_mfcc, n_mod/2+1] (row A8)."""
         torch = _torch()
-        if not (ragged.is_device_tensor(mfcc) and mfcc.dtype == torch.float32
-                and mfcc.dim() == 3 and mfcc.shape[1] == self.cfg.n_mfcc):
-            raise TypeError("mfcc must be a float32 CUDA(HIP) tensor [B, n_mfcc, T]")
+        self._check_mfcc(mfcc)
         mfcc = mfcc.contiguous()
         B, _, T = mfcc.shape
         n = self.cfg.mod_fft_len(T)
@@ -499,13 +485,8 @@ class MfccPlan:
             res = rfft_rows_long(mfcc.reshape(B * self.cfg.n_mfcc, T), n,
                                  None if out is None else out.reshape(B * self.cfg.n_mfcc, n // 2 + 1))
             return res.reshape(B, self.cfg.n_mfcc, n // 2 + 1) if out is None else out
-        if out is None:
-            out = torch.empty((B, self.cfg.n_mfcc, n // 2 + 1), dtype=torch.complex64,
-                              device=self.device)
-        else:
-            self._check_out(out, (B, self.cfg.n_mfcc, n // 2 + 1), torch.complex64, "modspec")
-        _lib.check(self._lib.mm_modspec_f32(self._h, mfcc.data_ptr(), B, T, out.data_ptr(),
-                                            self._stream()), "mm_modspec_f32")
+        out = self._out(out, (B, self.cfg.n_mfcc, n // 2 + 1), torch.complex64, "modspec")
+        self._call("mm_modspec_f32", mfcc.data_ptr(), B, T, out.data_ptr())
         return out
 
     def mfcc_change(self, mfcc, sos1, sos2=None, remove_first=True, diff_method="grad", out_filter=True):
@@ -514,33 +495,42 @@ class MfccPlan:
         outFilter=None branch); out_filter=False stops after the norm (the caller applies a 'fir' / 'sg'
         output filter to the result).  diff_method 'grad' = np.gradient, anything else = the reference's
         Savitzky-Golay differentiator savgol_filter(x, 3, 2, deriv=1, mode='interp')."""
-        torch = _torch()
-        if not (ragged.is_device_tensor(mfcc) and mfcc.dtype == torch.float32
-                and mfcc.dim() == 3 and mfcc.shape[1] == self.cfg.n_mfcc):
-            raise TypeError("mfcc must be a float32 CUDA(HIP) tensor [B, n_mfcc, T]")
+        self._check_mfcc(mfcc)
         mfcc = mfcc.contiguous()
-        B, _, T = mfcc.shape
-        from .filters import sos_sections      # scipy's own checks and messages (2-D, six columns, a0 == 1)
-        s1 = sos_sections(sos1)
-        s2 = s1 if sos2 is None else sos_sections(sos2)
-        for s in ((s1, s2) if out_filter else (s1,)):
+        T = mfcc.shape[2]
+        s1, s2, filters = self._change_sections(sos1, sos2, out_filter)
+        for s in filters:
             if T <= ragged.sos_padlen(s):   # scipy.signal.sosfiltfilt's own check and message
                 raise ValueError(ragged.PADLEN_TEXT.format(ragged.sos_padlen(s)))
         sg = 0 if diff_method == "grad" else 1
         if sg and T < 3:    # scipy.signal.savgol_filter's own check and message
             raise ValueError(ragged.SG_WINDOW_TEXT)
-        out = torch.empty((B, T), dtype=torch.float64, device=self.device)
-        # sized by the form this call takes (a few KB for the clip-resident one), not by the bound over all forms
-        need = int(self._lib.mm_change_workspace_bytes_for(self._h, B, T, 1 if remove_first else 0, s1.ctypes.data, s1.shape[0],
-                                                           s2.ctypes.data, s2.shape[0] if out_filter else 0))
+        return self._change(mfcc, s1, s2, remove_first, sg, out_filter)[1]
+
+    @staticmethod
+    def _change_sections(sos1, sos2, out_filter):
+        """(sections of the first filter, of the output filter -- sos2 None: the first again --, the filters the call runs)."""
+        from .filters import sos_sections      # scipy's own checks and messages (2-D, six columns, a0 == 1)
+        s1 = sos_sections(sos1)
+        s2 = s1 if sos2 is None else sos_sections(sos2)
+        return s1, s2, ((s1, s2) if out_filter else (s1,))
+
+    def _change(self, mfcc, s1, s2, remove_first, sg, out_filter, d_frames=None, ok=()):
+        """mm_mfcc_change_f64 (``d_frames`` None) or mm_mfcc_change_ragged_f64 on a checked contiguous [B, n_mfcc, T] ->
+        (status, [B, T] float64); the workspace is sized by the form this call takes (a few KB for the clip-resident one),
+        not by the bound over all forms."""
+        B, _, T = mfcc.shape
+        form = "" if d_frames is None else "_ragged"
+        filt = (1 if remove_first else 0, s1.ctypes.data, s1.shape[0], s2.ctypes.data, s2.shape[0] if out_filter else 0)
+        out = _torch().empty((B, T), dtype=_torch().float64, device=self.device)
+        sizer = f"mm_change{form}_workspace_bytes_for"
+        need = int(getattr(self._lib, sizer)(self._h, B, T, *filt))
         if need == 0:
-            raise ValueError("mm_change_workspace_bytes_for: invalid arguments")
-        ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        _lib.check(self._lib.mm_mfcc_change_f64(self._h, mfcc.data_ptr(), B, T, 1 if remove_first else 0, sg,
-                                                s1.ctypes.data, s1.shape[0], s2.ctypes.data, s2.shape[0] if out_filter else 0,
-                                                out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
-                   "mm_mfcc_change_f64")
-        return out
+            raise ValueError(f"{sizer}: invalid arguments")
+        ws = _lib.workspace(need, self.device)
+        rc = self._call(f"mm_mfcc_change{form}_f64", mfcc.data_ptr(), B, T, *ragged.lens_arg(d_frames), filt[0], sg, *filt[1:],
+                        out.data_ptr(), ws.data_ptr(), ws.numel(), ok=ok)
+        return rc, out
 
     def mfcc_change_ragged(self, mfcc, frames, sos1, sos2=None, remove_first=True, diff_method="grad", out_filter=True):
         """mfcc_change() for a ragged batch: [B, n_mfcc, T_max] float32 (what mfcc_ragged() returns) + `frames` [B] ->
@@ -557,36 +547,21 @@ class MfccPlan:
         entry) fall back to one mfcc_change() per distinct frame count, scattered into the zeroed output: correct,
         slower, and the one place this method synchronises (it reads `frames` back when they live on the device)."""
         torch = _torch()
-        if not (ragged.is_device_tensor(mfcc) and mfcc.dtype == torch.float32
-                and mfcc.dim() == 3 and mfcc.shape[1] == self.cfg.n_mfcc):
-            raise TypeError("mfcc must be a float32 CUDA(HIP) tensor [B, n_mfcc, T]")
+        self._check_mfcc(mfcc)
         if mfcc.device != self.device:
             raise ValueError(f"mfcc is on {mfcc.device}, the plan on {self.device}")
         mfcc = mfcc.contiguous()
         B, _, Tm = mfcc.shape
-        from .filters import sos_sections
-        s1 = sos_sections(sos1)
-        s2 = s1 if sos2 is None else sos_sections(sos2)
-        padlen = max(ragged.sos_padlen(s) for s in ((s1, s2) if out_filter else (s1,)))
+        s1, s2, filters = self._change_sections(sos1, sos2, out_filter)
+        padlen = max(ragged.sos_padlen(s) for s in filters)
         if Tm <= padlen:
             raise ValueError(ragged.PADLEN_TEXT.format(padlen))
         sg = 0 if diff_method == "grad" else 1
         fr = ragged.check_frames(frames, B, Tm, padlen, self.device)
         on_host = isinstance(fr, np.ndarray)
         fr_dev = ragged.counts_on_device(fr, self.device)
-        rf, n2 = 1 if remove_first else 0, s2.shape[0] if out_filter else 0
-        out = torch.empty((B, Tm), dtype=torch.float64, device=self.device)
-        need = int(self._lib.mm_change_ragged_workspace_bytes_for(self._h, B, Tm, rf, s1.ctypes.data, s1.shape[0],
-                                                                  s2.ctypes.data, n2))
-        if need == 0:
-            raise ValueError("mm_change_ragged_workspace_bytes_for: invalid arguments")
-        ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self._lib.mm_mfcc_change_ragged_f64(self._h, mfcc.data_ptr(), B, Tm, fr_dev.data_ptr(), rf, sg,
-                                                     s1.ctypes.data, s1.shape[0], s2.ctypes.data, n2, out.data_ptr(),
-                                                     ws.data_ptr(), ws.numel(), self._stream())
-        if rc != _lib.MM_ERR_UNSUPPORTED:
-            _lib.check(rc, "mm_mfcc_change_ragged_f64")
+        rc, out = self._change(mfcc, s1, s2, remove_first, sg, out_filter, fr_dev, ok=(_lib.MM_ERR_UNSUPPORTED,))
+        if rc == _lib.MM_OK:
             return out
         # no ragged kernel for this call: one single-length call per distinct frame count (reads device lengths back)
         fr_host = fr if on_host else fr_dev.clamp(1, Tm).cpu().numpy()

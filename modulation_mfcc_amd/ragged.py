@@ -130,6 +130,27 @@ def device_rows(x, dtypes, type_text, shape_text, *, widen=None, one_dim=False, 
     return x
 
 
+def batch_rows(x, shape_text, *, pitched=False):
+    """The [n] or [rows, n] argument of a single-length call -> ([rows, n] with unit inner stride, whether x was [n]);
+    ValueError(shape_text) for any other number of dimensions.  A strided inner axis is copied; with ``pitched`` (the
+    entries that take their row pitch from row_pitch) only where n > 1, and rows closer than n (expand()ed, overlapping)
+    are copied as well, as device_rows copies them."""
+    squeeze = x.dim() == 1
+    x2 = x.unsqueeze(0) if squeeze else x
+    if x2.dim() != 2:
+        raise ValueError(shape_text)
+    rows, n = x2.shape
+    if ((n > 1 and x2.stride(1) != 1) or (rows > 1 and x2.stride(0) < n)) if pitched else x2.stride(1) != 1:
+        x2 = x2.contiguous()
+    return x2, squeeze
+
+
+def lens_arg(d_lens):
+    """The lengths argument of an entry that serves both forms: nothing for the single-length entry (``d_lens`` None), the
+    device pointer for its ``_ragged`` twin, which takes it right behind the row pitch."""
+    return () if d_lens is None else (d_lens.data_ptr(),)
+
+
 def row_pitch(x):
     """Elements between the rows of [rows, n] as the kernels want it (>= n; the stride of a single row says nothing:
     numpy's x[None, :] gives 0)."""

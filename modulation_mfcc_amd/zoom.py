@@ -18,7 +18,6 @@ rest.  There is no host fallback.
 """
 from __future__ import annotations
 
-import ctypes as C
 import operator
 
 import numpy as np
@@ -104,28 +103,19 @@ def _run(x3, widths, zoom_x, order, mode, cval, flags, h_out, w_out):
     from . import _lib
     b, h, w = x3.shape
     dev = x3.device
-    with torch.cuda.device(dev):
-        out = torch.empty((b, h_out, w_out), dtype=x3.dtype, device=dev)
-        if b == 0 or h_out == 0 or w_out == 0:
-            return out
-        lib = _lib.load()
-        need = int(lib.mm_zoom2d_workspace_bytes(order, b, h, w, h_out, w_out))
-        if need == 0:
-            raise ValueError(f"zoom: {b} images of {h} x {w} to {h_out} x {w_out} are beyond the kernel's limits")
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        f32 = x3.dtype == torch.float32
-        si, sr = _strides(x3)
-        tail = (h_out, w_out, out.data_ptr(), h_out * w_out, w_out, ws.data_ptr(), ws.numel(),
-                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        head = (order, mode, float(cval), flags, x3.data_ptr(), b, h, w, si, sr)
-        if widths is None:
-            name = "mm_zoom2d_f32" if f32 else "mm_zoom2d_f64"
-            rc = getattr(lib, name)(*head, *tail)
-        else:
-            name = "mm_zoom2d_ragged_f32" if f32 else "mm_zoom2d_ragged_f64"
-            rc = getattr(lib, name)(*head, widths.data_ptr(), float(zoom_x), *tail)
-        _lib.check(rc, name)
+    out = torch.empty((b, h_out, w_out), dtype=x3.dtype, device=dev)
+    if b == 0 or h_out == 0 or w_out == 0:
         return out
+    need = int(_lib.load().mm_zoom2d_workspace_bytes(order, b, h, w, h_out, w_out))
+    if need == 0:
+        raise ValueError(f"zoom: {b} images of {h} x {w} to {h_out} x {w_out} are beyond the kernel's limits")
+    ws = _lib.workspace(need, dev)
+    si, sr = _strides(x3)
+    form, per_image = ("", ()) if widths is None else ("_ragged", (widths.data_ptr(), float(zoom_x)))
+    _lib.call(f"mm_zoom2d{form}_f32" if x3.dtype == torch.float32 else f"mm_zoom2d{form}_f64", dev,
+              order, mode, float(cval), flags, x3.data_ptr(), b, h, w, si, sr, *per_image,
+              h_out, w_out, out.data_ptr(), h_out * w_out, w_out, ws.data_ptr(), ws.numel())
+    return out
 
 
 def zoom_batch(x, zoom, order=3, mode="constant", cval=0.0, prefilter=True, *, grid_mode=False, db=False):
