@@ -42,6 +42,18 @@
 // chirp spectrum, both written per call (hb_chirp_ragged_kernel + one batched FFT in the clips' precision).  The passes
 // are the RG = true instantiations of the same kernels: hb_row_setup loads the row's n, w, bhat and scale once per
 // workgroup.  One clip per transform -- two clips could share one only if they shared a chirp.
+//
+// SHARED PIECES.  Device, as MACROS (below: MM_HB_...): FUSED_ITEM (the XCD-ordered (row, c) of the two fused kernels),
+// TWIDDLE_DFT (twiddle + DFT of all four pass kernels), COLUMN_POWERS / EXCHANGE / STAGE_B (the rest of the radix-R^2
+// butterfly: hb_pass2_kernel once, hb_mid2_kernel twice), STORE_RUN2 / STORE_RUN (the staged stores of the fused / the
+// single-radix kernels); as a function hb_chirp_phase (both chirp kernels).  Host: hb_with_radix (every launch of the four
+// pass kernels, dense and ragged), hb_fused_grid, hb_chirp_envelope (the four chirp transforms of mm_hilbert_envelope and
+// mm_hilbert_envelope_ragged).  Macros, because an inlined function around these pieces is optimised on its own first: with
+// a complex product inside, the operands of the sum of two products in hb_mul come out in the other order and the backend
+// contracts the other product into the FMA (the last bit of the results changes); without one, the integer code and the
+// register allocation of the kernel still move (docs/experiments.md, "Hilbert FFT: shared pieces").
+
+#include <type_traits>
 
 #include "mm_hb_math.h"
 
@@ -232,25 +244,98 @@ __device__ __forceinline__ void hb_twiddle_powers(const hb_c<double>* __restrict
 template <typename T, int R> struct HbFuse {
   static constexpr int C = (R == 16 ? MM_HB_C16 : 10) / (sizeof(T) == 8 ? 2 : 1);
   static constexpr int THREADS = C * R;
+  static constexpr int PITCH = R * (R + 1) + 1;       // LDS points per butterfly: R columns of R + 1, one more between butterflies
 };
+
+// The shared pieces of the two fused kernels are MACROS, not functions, on purpose: an inlined function is optimised on its
+// own first, and that changes which product of a complex multiplication the compiler contracts into an FMA (the last bit
+// of the results) and the register allocation (docs/experiments.md, "Hilbert FFT: shared pieces").  The text below compiles
+// exactly as if it stood in the kernel.  They use the kernels' own names: T, R, C, RC, PITCH, tile, cl, x, nbC, n_rows, live,
+// lo, hi, io, dst, row, c.
+//
+// MM_HB_FUSED_ITEM: declares the thread's `row` and `c`; returns from the kernel in the workgroups that pad the grid
+// (hb_fused_grid rounds up to 8).  XCD-aware block order: workgroups go round-robin to the 8 XCDs, and blocks with
+// neighbouring c share cache lines (C = 10: 80-byte segments) -- so XCD x takes a contiguous eighth of the (row, c-block)
+// list, and neighbours meet in one L2 instead of fetching the shared lines into two.
+#define MM_HB_FUSED_ITEM                                                      \
+  const int64_t nblk = (nbC + C - 1) / C;                                     \
+  const int64_t per = (int64_t)gridDim.x / 8;                                 \
+  const int64_t L = (int64_t)(blockIdx.x % 8) * per + blockIdx.x / 8;         \
+  if (L >= nblk * n_rows) return;                                             \
+  const int64_t row = L / nblk;                                               \
+  const int64_t c = (L - row * nblk) * C + cl;
+
+// MM_HB_TWIDDLE_DFT(V, TW, E), inside `if (live)`, all four pass kernels: V[t] *= W_M^(E t) if TW (the passes in front left
+// Ns > 1; E is evaluated only then), then the DFT of V (output u at V[hb_perm<R>(u)]).
+// W_(Ns R)^(k t) = W_M^(E t), t < R: two exact values from the float64 tables -- W^E and W^(B E) -- rounded to T, their
+// first powers by squaring / one more product, and w[t] = (W^(B E))^(t / B) * (W^E)^(t % B): at most four roundings per
+// twiddle, four table reads per butterfly instead of two per point.  (The whole chain in float64 cost the float32 passes
+// 10 % of their time; one long float32 chain 4x the error.)  E t < M for t < R.
+#define MM_HB_TWIDDLE_DFT(V, TW, E)                                           \
+  if (TW) {                                                                   \
+    hb_c<T> w[R];                                                             \
+    hb_twiddle_powers<T, R>(lo, hi, (E), w);                                  \
+    _Pragma("unroll") for (int t = 1; t < R; ++t) V[t] = hb_mul(V[t], w[t]);  \
+  }                                                                           \
+  hb_dft<T, R>(V);
+
+// MM_HB_COLUMN_POWERS, inside `if (live)`: declares wu[u] = W_M^(tB nbC u) = W_(R^2)^(tB u), tB = x, for MM_HB_EXCHANGE.
+// Computed by every butterfly: kept live across the two of hb_mid2_kernel the powers cost 2 R registers.
+#define MM_HB_COLUMN_POWERS                                                   \
+  hb_c<T> wu[R];                                                              \
+  if (x > 0) hb_twiddle_powers<T, R>(lo, hi, (int64_t)x * nbC, wu);
+
+// MM_HB_EXCHANGE(V, TW, E_OUT), behind the two above: stage A's outputs * W_(R^2)^(tB u), and if TW * W_M^(E_OUT) =
+// W_(Ns R^2)^(k tB) (one table value), into the thread's row of the butterfly's LDS tile.
+#define MM_HB_EXCHANGE(V, TW, E_OUT)                                          \
+  hb_c<T> outer;                                                              \
+  outer.x = (T)1; outer.y = (T)0;                                             \
+  if ((TW) && x > 0) {                                                        \
+    const hb_c<double> a = hb_twiddle(lo, hi, (E_OUT));                       \
+    outer.x = (T)a.x; outer.y = (T)a.y;                                       \
+  }                                                                           \
+  hb_c<T>* wr = tile + cl * PITCH + x;                                        \
+  _Pragma("unroll") for (int u = 0; u < R; ++u) {                             \
+    hb_c<T> a = V[hb_perm<R>(u)];                                             \
+    if (x > 0) {                                                              \
+      if (u > 0) a = hb_mul(a, wu[u]);                                        \
+      if (TW) a = hb_mul(a, outer);                                           \
+    }                                                                         \
+    wr[u * (R + 1)] = a;                                                      \
+  }
+
+// MM_HB_STAGE_B(B), inside `if (live)` behind the barrier: declares B, the thread's column of the exchange, and transforms it
+// (output vv at B[hb_perm<R>(vv)]).
+#define MM_HB_STAGE_B(B)                                                      \
+  hb_c<T> B[R];                                                               \
+  const hb_c<T>* rd = tile + cl * PITCH + x * (R + 1);                        \
+  _Pragma("unroll") for (int tB = 0; tB < R; ++tB) B[tB] = rd[tB];            \
+  hb_dft<T, R>(B);
+
+// MM_HB_STORE_RUN2(RG, B): butterfly c fills out[c R^2 .. (c + 1) R^2), i.e. the workgroup one contiguous run (Ns = 1) -- B
+// (natural order) back through LDS (slot x + vv R of butterfly cl), then unit-stride stores.  Two barriers, the first one for
+// the threads that still read their column of the tile; every thread of the workgroup comes here.
+#define MM_HB_STORE_RUN2(RG, B)                                               \
+  __syncthreads();                                                            \
+  if (live) {                                                                 \
+    _Pragma("unroll") for (int vv = 0; vv < R; ++vv) tile[cl * PITCH + x + vv * R] = B[vv]; \
+  }                                                                           \
+  __syncthreads();                                                            \
+  const int64_t c0 = c - cl;                                                  \
+  const int n_live = (int)(nbC - c0 < C ? nbC - c0 : C);                      \
+  for (int e = threadIdx.x; e < n_live * RC; e += C * R)                      \
+    hb_store<T, RG>(io, dst, row, c0 * RC + e, tile[(e / RC) * PITCH + (e % RC)]);
+
 template <typename T, int R, bool RG = false>
 __global__ __launch_bounds__((HbFuse<T, R>::THREADS)) void hb_pass2_kernel(const hb_c<T>* __restrict__ in, hb_c<T>* __restrict__ out,
                                                                         int64_t M, int64_t Ns, int64_t n_rows,
                                                                         const hb_c<double>* __restrict__ lo,
                                                                         const hb_c<double>* __restrict__ hi, HbIo<T> io) {
-  constexpr int C = HbFuse<T, R>::C, RC = R * R, PITCH = R * (R + 1) + 1;
+  constexpr int C = HbFuse<T, R>::C, RC = R * R, PITCH = HbFuse<T, R>::PITCH;
   __shared__ hb_c<T> tile[C * PITCH];
   const int64_t nbC = M / RC;
   const int cl = threadIdx.x % C, x = threadIdx.x / C;          // x: tB in stage A, u in stage B
-  // XCD-aware block order: workgroups go round-robin to the 8 XCDs, and blocks with neighbouring c share cache lines
-  // (C = 10: 80-byte segments) -- so XCD x takes a contiguous eighth of the (row, c-block) list, and neighbours meet
-  // in one L2 instead of fetching the shared lines into two.
-  const int64_t nblk = (nbC + C - 1) / C;
-  const int64_t per = (int64_t)gridDim.x / 8;
-  const int64_t L = (int64_t)(blockIdx.x % 8) * per + blockIdx.x / 8;
-  if (L >= nblk * n_rows) return;
-  const int64_t row = L / nblk;
-  const int64_t c = (L - row * nblk) * C + cl;
+  MM_HB_FUSED_ITEM
   const hb_c<T>* src = in + row * M;
   hb_c<T>* dst = out + row * M;
   hb_row_setup<T, RG>(io, row, M);
@@ -260,41 +345,14 @@ __global__ __launch_bounds__((HbFuse<T, R>::THREADS)) void hb_pass2_kernel(const
     hb_c<T> v[R];
 #pragma unroll
     for (int tA = 0; tA < R; ++tA) v[tA] = hb_load(io, src, row, c + (x + (int64_t)R * tA) * nbC);
-    if (Ns > 1) {
-      hb_c<T> w[R];
-      hb_twiddle_powers<T, R>(lo, hi, k * (M / (Ns * R)), w);
-#pragma unroll
-      for (int tA = 1; tA < R; ++tA) v[tA] = hb_mul(v[tA], w[tA]);
-    }
-    hb_dft<T, R>(v);
-    // * W_(Ns R^2)^(k tB) * W_(R^2)^(tB u): the first factor is one table value, the second the powers of W_M^(tB nbC)
-    hb_c<T> wu[R];
-    if (x > 0) hb_twiddle_powers<T, R>(lo, hi, (int64_t)x * nbC, wu);
-    hb_c<T> outer;
-    outer.x = (T)1; outer.y = (T)0;
-    if (Ns > 1 && x > 0) {
-      const hb_c<double> a = hb_twiddle(lo, hi, k * x * (nbC / Ns));
-      outer.x = (T)a.x; outer.y = (T)a.y;
-    }
-    hb_c<T>* wr = tile + cl * PITCH + x;
-#pragma unroll
-    for (int u = 0; u < R; ++u) {
-      hb_c<T> a = v[hb_perm<R>(u)];
-      if (x > 0) {
-        if (u > 0) a = hb_mul(a, wu[u]);
-        if (Ns > 1) a = hb_mul(a, outer);
-      }
-      wr[u * (R + 1)] = a;
-    }
+    MM_HB_TWIDDLE_DFT(v, Ns > 1, k * (M / (Ns * R)))
+    MM_HB_COLUMN_POWERS
+    MM_HB_EXCHANGE(v, Ns > 1, k * x * (nbC / Ns))
   }
   __syncthreads();
   hb_c<T> b_keep[R];                      // natural order, for the first pass's staged stores
   if (live) {
-    hb_c<T> b[R];
-    const hb_c<T>* rd = tile + cl * PITCH + x * (R + 1);
-#pragma unroll
-    for (int tB = 0; tB < R; ++tB) b[tB] = rd[tB];
-    hb_dft<T, R>(b);
+    MM_HB_STAGE_B(b)
 #pragma unroll
     for (int vv = 0; vv < R; ++vv) b_keep[vv] = b[hb_perm<R>(vv)];
     if (Ns > 1) {
@@ -303,19 +361,8 @@ __global__ __launch_bounds__((HbFuse<T, R>::THREADS)) void hb_pass2_kernel(const
       for (int vv = 0; vv < R; ++vv) hb_store<T, RG>(io, dst, row, m0 + (int64_t)vv * R * Ns, b[hb_perm<R>(vv)]);
     }
   }
-  if (Ns == 1) {
-    // first pass: butterfly c fills out[c R^2 .. (c + 1) R^2), i.e. the workgroup one contiguous run -- back through
-    // LDS (slot u + v R of butterfly cl), then unit-stride stores
-    __syncthreads();
-    if (live) {
-#pragma unroll
-      for (int vv = 0; vv < R; ++vv) tile[cl * PITCH + x + vv * R] = b_keep[vv];
-    }
-    __syncthreads();
-    const int64_t c0 = c - cl;
-    const int n_live = (int)(nbC - c0 < C ? nbC - c0 : C);
-    for (int e = threadIdx.x; e < n_live * RC; e += C * R)
-      hb_store<T, RG>(io, dst, row, c0 * RC + e, tile[(e / RC) * PITCH + (e % RC)]);
+  if (Ns == 1) {                          // the first pass
+    MM_HB_STORE_RUN2(RG, b_keep)
   }
 }
 
@@ -335,59 +382,28 @@ __global__ __launch_bounds__((HbFuse<T, R>::THREADS)) void hb_mid2_kernel(const 
                                                                        int64_t M, int64_t n_rows,
                                                                        const hb_c<double>* __restrict__ lo,
                                                                        const hb_c<double>* __restrict__ hi, HbIo<T> io) {
-  constexpr int C = HbFuse<T, R>::C, RC = R * R, PITCH = R * (R + 1) + 1;
+  constexpr int C = HbFuse<T, R>::C, RC = R * R, PITCH = HbFuse<T, R>::PITCH;
   __shared__ hb_c<T> tile[C * PITCH];
   const int64_t nbC = M / RC;                                   // = Ns of the forward's last pass
   const int cl = threadIdx.x % C, x = threadIdx.x / C;
-  const int64_t nblk = (nbC + C - 1) / C;
-  const int64_t per = (int64_t)gridDim.x / 8;
-  const int64_t L = (int64_t)(blockIdx.x % 8) * per + blockIdx.x / 8;      // XCD-aware order, as hb_pass2_kernel
-  if (L >= nblk * n_rows) return;
-  const int64_t row = L / nblk;
-  const int64_t c = (L - row * nblk) * C + cl;
+  MM_HB_FUSED_ITEM
   const hb_c<T>* src = in + row * M;
   hb_c<T>* dst = out + row * M;
   hb_row_setup<T>(io, row, M);
   const bool live = c < nbC;
-  // ---- forward, last pass (Ns = nbC, so k = c) ----
+  // ---- forward, last pass (Ns = nbC, so k = c): W_(Ns R)^(k tA) = W_M^(k R tA), W_(Ns R^2)^(k tB) = W_M^(k tB) ----
   if (live) {
-    hb_c<T> wu[R];                                              // W_(R^2)^(x u) (computed again for the second butterfly:
-    if (x > 0) hb_twiddle_powers<T, R>(lo, hi, (int64_t)x * nbC, wu);   // kept live it costs 2 R registers across both)
+    MM_HB_COLUMN_POWERS
     hb_c<T> v[R];
 #pragma unroll
     for (int tA = 0; tA < R; ++tA) v[tA] = hb_load(io, src, row, c + (x + (int64_t)R * tA) * nbC);
-    if (nbC > 1) {
-      hb_c<T> w[R];
-      hb_twiddle_powers<T, R>(lo, hi, c * R, w);                // W_(Ns R)^(k tA) = W_M^(k R tA)
-#pragma unroll
-      for (int tA = 1; tA < R; ++tA) v[tA] = hb_mul(v[tA], w[tA]);
-    }
-    hb_dft<T, R>(v);
-    hb_c<T> outer;
-    outer.x = (T)1; outer.y = (T)0;
-    if (nbC > 1 && x > 0) {
-      const hb_c<double> a = hb_twiddle(lo, hi, c * x);         // W_(Ns R^2)^(k tB) = W_M^(k tB)
-      outer.x = (T)a.x; outer.y = (T)a.y;
-    }
-    hb_c<T>* wr = tile + cl * PITCH + x;
-#pragma unroll
-    for (int u = 0; u < R; ++u) {
-      hb_c<T> a = v[hb_perm<R>(u)];
-      if (x > 0) {
-        if (u > 0) a = hb_mul(a, wu[u]);
-        if (nbC > 1) a = hb_mul(a, outer);
-      }
-      wr[u * (R + 1)] = a;
-    }
+    MM_HB_TWIDDLE_DFT(v, nbC > 1, c * R)
+    MM_HB_EXCHANGE(v, nbC > 1, c * x)
   }
   __syncthreads();
   hb_c<T> v2[R];                                                // thread u: X[c + nbC (u + R v)], masked and conjugated
   if (live) {
-    hb_c<T> b[R];
-    const hb_c<T>* rd = tile + cl * PITCH + x * (R + 1);
-#pragma unroll
-    for (int tB = 0; tB < R; ++tB) b[tB] = rd[tB];
-    hb_dft<T, R>(b);
+    MM_HB_STAGE_B(b)
 #pragma unroll
     for (int vv = 0; vv < R; ++vv) {
       hb_c<T> V = b[hb_perm<R>(vv)];
@@ -399,41 +415,39 @@ __global__ __launch_bounds__((HbFuse<T, R>::THREADS)) void hb_mid2_kernel(const 
   __syncthreads();                                              // every thread has read its column of the tile
   // ---- inverse, first pass (Ns = 1: no twiddles in front, W_(R^2)^(tB u) behind stage A) ----
   if (live) {
-    hb_c<T> wu[R];
-    if (x > 0) hb_twiddle_powers<T, R>(lo, hi, (int64_t)x * nbC, wu);
-    hb_dft<T, R>(v2);
-    hb_c<T>* wr = tile + cl * PITCH + x;
-#pragma unroll
-    for (int u = 0; u < R; ++u) {
-      hb_c<T> a = v2[hb_perm<R>(u)];
-      if (x > 0 && u > 0) a = hb_mul(a, wu[u]);
-      wr[u * (R + 1)] = a;
-    }
+    MM_HB_COLUMN_POWERS
+    MM_HB_TWIDDLE_DFT(v2, false, 0)
+    MM_HB_EXCHANGE(v2, false, 0)
   }
   __syncthreads();
   hb_c<T> b_keep[R];
   if (live) {
-    hb_c<T> b[R];
-    const hb_c<T>* rd = tile + cl * PITCH + x * (R + 1);
-#pragma unroll
-    for (int tB = 0; tB < R; ++tB) b[tB] = rd[tB];
-    hb_dft<T, R>(b);
+    MM_HB_STAGE_B(b)
 #pragma unroll
     for (int vv = 0; vv < R; ++vv) b_keep[vv] = b[hb_perm<R>(vv)];
   }
-  // butterfly c fills out[c R^2 .. (c + 1) R^2): the workgroup one contiguous run -- back through LDS, unit-stride stores
-  __syncthreads();
-  if (live) {
-#pragma unroll
-    for (int vv = 0; vv < R; ++vv) tile[cl * PITCH + x + vv * R] = b_keep[vv];
-  }
-  __syncthreads();
-  const int64_t c0 = c - cl;
-  const int n_live = (int)(nbC - c0 < C ? nbC - c0 : C);
-  HbIo<T> q = io;
-  for (int e = threadIdx.x; e < n_live * RC; e += C * R)
-    hb_store(q, dst, row, c0 * RC + e, tile[(e / RC) * PITCH + (e % RC)]);
+  MM_HB_STORE_RUN2(false, b_keep)
 }
+
+// MM_HB_STORE_RUN(RG, V, NS): a single-radix kernel's staged store (radix <= 16) where the workgroup's 128 butterflies cover
+// ONE contiguous run -- runs of NS consecutive butterflies fill one contiguous block of NS R outputs each (NS divides the
+// workgroup; NS = 1: every butterfly its own R outputs).  Through LDS (slot p of the run at p + p / R: conflict-free for
+// NS = 1 as for NS >= 16), then unit-stride stores.  One barrier; every thread of the workgroup comes here.  A macro for the
+// reason given at MM_HB_FUSED_ITEM; uses the kernels' T, R, tile, live, nb, io, dst, row.
+#define MM_HB_STORE_RUN(RG, V, NS)                                            \
+  if (live) {                                                                 \
+    const int jl = threadIdx.x, ns = (int)(NS);                               \
+    const int p0 = (jl / ns) * ns * R + jl % ns;                              \
+    _Pragma("unroll") for (int u = 0; u < R; ++u) {                           \
+      const int pp = p0 + u * ns;                                             \
+      tile[pp + pp / R] = V[hb_perm<R>(u)];                                   \
+    }                                                                         \
+  }                                                                           \
+  __syncthreads();                                                            \
+  const int64_t j0 = (int64_t)blockIdx.x * MM_HB_THREADS;                     \
+  const int64_t cnt = (nb - j0 < MM_HB_THREADS ? nb - j0 : MM_HB_THREADS) * R; \
+  for (int64_t e = threadIdx.x; e < cnt; e += MM_HB_THREADS)                  \
+    hb_store<T, RG>(io, dst, row, j0 * R + e, tile[e + e / R]);
 
 // The same for a single radix (one thread per butterfly: the forward's outputs ARE the inverse's inputs, in registers).
 template <typename T, int R>
@@ -453,13 +467,7 @@ __global__ __launch_bounds__(MM_HB_THREADS) void hb_mid_kernel(const hb_c<T>* __
   if (live) {
 #pragma unroll
     for (int t = 0; t < R; ++t) v[t] = hb_load(io, src, row, j + t * nb);
-    if (nb > 1) {
-      hb_c<T> w[R];
-      hb_twiddle_powers<T, R>(lo, hi, j, w);                // k = j, W_(Ns R)^(k t) = W_M^(j t)
-#pragma unroll
-      for (int t = 1; t < R; ++t) v[t] = hb_mul(v[t], w[t]);
-    }
-    hb_dft<T, R>(v);
+    MM_HB_TWIDDLE_DFT(v, nb > 1, j)                         // k = j, W_(Ns R)^(k t) = W_M^(j t)
 #pragma unroll
     for (int u = 0; u < R; ++u) {                           // X[j + nb u] -> the inverse's input t = u
       hb_c<T> V = v[hb_perm<R>(u)];
@@ -470,16 +478,7 @@ __global__ __launch_bounds__(MM_HB_THREADS) void hb_mid_kernel(const hb_c<T>* __
     hb_dft<T, R>(v2);
   }
   if (kTile) {
-    if (live) {
-      const int p0 = threadIdx.x * R;
-#pragma unroll
-      for (int u = 0; u < R; ++u) tile[p0 + u + (p0 + u) / R] = v2[hb_perm<R>(u)];
-    }
-    __syncthreads();
-    const int64_t j0 = (int64_t)blockIdx.x * MM_HB_THREADS;
-    const int64_t cnt = (nb - j0 < MM_HB_THREADS ? nb - j0 : MM_HB_THREADS) * R;
-    for (int64_t e = threadIdx.x; e < cnt; e += MM_HB_THREADS)
-      hb_store(io, dst, row, j0 * R + e, tile[e + e / R]);
+    MM_HB_STORE_RUN(false, v2, 1)
   } else if (live) {
 #pragma unroll
     for (int u = 0; u < R; ++u) hb_store(io, dst, row, j * R + u, v2[hb_perm<R>(u)]);
@@ -504,37 +503,10 @@ __global__ __launch_bounds__(MM_HB_THREADS) void hb_pass_kernel(const hb_c<T>* _
   if (live) {
 #pragma unroll
     for (int t = 0; t < R; ++t) v[t] = hb_load(io, src, row, j + t * nb);
-    if (Ns > 1) {
-      const int64_t k = (int64_t)((uint32_t)j % (uint32_t)Ns);     // M <= 2^25
-      // W_(Ns R)^(k t) = W_M^(e1 t), t < R: two exact values from the float64 tables -- W^e1 and W^(B e1) -- rounded
-      // to T, their first powers by squaring / one more product, and w[t] = (W^(B e1))^(t / B) * (W^e1)^(t % B):
-      // at most four roundings per twiddle, four table reads per butterfly instead of two per point.  (The whole
-      // chain in float64 cost the float32 passes 10 % of their time; one long float32 chain 4x the error.)
-      hb_c<T> w[R];
-      hb_twiddle_powers<T, R>(lo, hi, k * (M / (Ns * R)), w);       // e t < M for t < R
-#pragma unroll
-      for (int t = 1; t < R; ++t) v[t] = hb_mul(v[t], w[t]);
-    }
-    hb_dft<T, R>(v);
+    MM_HB_TWIDDLE_DFT(v, Ns > 1, (int64_t)((uint32_t)j % (uint32_t)Ns) * (M / (Ns * R)))      // k = j mod Ns; M <= 2^25
   }
   if (kTile && Ns <= MM_HB_THREADS && MM_HB_THREADS % Ns == 0) {
-    // Ns consecutive butterflies fill one contiguous block of Ns R outputs, so the workgroup's 128 butterflies
-    // cover ONE contiguous run: through LDS (slot p of the run at p + p / R: conflict-free for Ns = 1 as for
-    // Ns >= 16), unit-stride stores
-    if (live) {
-      const int jl = threadIdx.x, ns = (int)Ns;
-      const int p0 = (jl / ns) * ns * R + jl % ns;
-#pragma unroll
-      for (int u = 0; u < R; ++u) {
-        const int pp = p0 + u * ns;
-        tile[pp + pp / R] = v[hb_perm<R>(u)];
-      }
-    }
-    __syncthreads();
-    const int64_t j0 = (int64_t)blockIdx.x * MM_HB_THREADS;
-    const int64_t cnt = (nb - j0 < MM_HB_THREADS ? nb - j0 : MM_HB_THREADS) * R;
-    for (int64_t e = threadIdx.x; e < cnt; e += MM_HB_THREADS)
-      hb_store<T, RG>(io, dst, row, j0 * R + e, tile[e + e / R]);
+    MM_HB_STORE_RUN(RG, v, Ns)
   } else if (live) {
     const int64_t k = (int64_t)((uint32_t)j % (uint32_t)Ns);
     const int64_t m0 = (j - k) * R + k;
@@ -542,6 +514,15 @@ __global__ __launch_bounds__(MM_HB_THREADS) void hb_pass_kernel(const hb_c<T>* _
     for (int u = 0; u < R; ++u) hb_store<T, RG>(io, dst, row, m0 + u * Ns, v[hb_perm<R>(u)]);
   }
 }
+
+// the textual pieces belong to the four kernels above and to nothing else
+#undef MM_HB_FUSED_ITEM
+#undef MM_HB_TWIDDLE_DFT
+#undef MM_HB_COLUMN_POWERS
+#undef MM_HB_EXCHANGE
+#undef MM_HB_STAGE_B
+#undef MM_HB_STORE_RUN2
+#undef MM_HB_STORE_RUN
 
 // W_M^e tables in float64: lo[e] = W_M^e (e < min(M, 1024)), hi[a] = W_M^(1024 a) (a < ceil(M / 1024))
 __global__ __launch_bounds__(256) void hb_tables_kernel(hb_c<double>* __restrict__ lo, hb_c<double>* __restrict__ hi,
@@ -562,9 +543,7 @@ __global__ __launch_bounds__(256) void hb_tables_kernel(hb_c<double>* __restrict
 
 // b[k] = exp(+i pi k^2 / n) for |k| < n (wrapped into [0, M)), 0 elsewhere: the chirp whose spectrum multiplies
 // every Bluestein product.  k^2 is reduced mod 2n in integers, so the phase is exact to float64 rounding.
-__global__ __launch_bounds__(256) void hb_chirp_kernel(hb_c<double>* __restrict__ b, int64_t n, int64_t M) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= M) return;
+__device__ __forceinline__ hb_c<double> hb_chirp_phase(int64_t i, int64_t n, int64_t M) {
   const int64_t k = i < n ? i : (M - i < n ? M - i : -1);
   hb_c<double> r;
   r.x = 0.0; r.y = 0.0;
@@ -572,7 +551,13 @@ __global__ __launch_bounds__(256) void hb_chirp_kernel(hb_c<double>* __restrict_
     const unsigned long long q = ((unsigned long long)k * (unsigned long long)k) % (unsigned long long)(2 * n);
     sincospi((double)q / (double)n, &r.y, &r.x);
   }
-  b[i] = r;
+  return r;
+}
+
+__global__ __launch_bounds__(256) void hb_chirp_kernel(hb_c<double>* __restrict__ b, int64_t n, int64_t M) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= M) return;
+  b[i] = hb_chirp_phase(i, n, M);
 }
 
 // The same chirp for every row of a ragged batch, each at its own length n = lens[row] (clamped into [1, n_max]), rounded
@@ -591,14 +576,9 @@ __global__ __launch_bounds__(256) void hb_chirp_ragged_kernel(const T* __restric
   if (i >= M) return;
   const int64_t len = lens[row];
   const int64_t n = len < 1 ? 1 : (len > n_max ? n_max : len);
-  const int64_t k = i < n ? i : (M - i < n ? M - i : -1);
-  double c = 0.0, s = 0.0;
-  if (k >= 0) {
-    const unsigned long long q = ((unsigned long long)k * (unsigned long long)k) % (unsigned long long)(2 * n);
-    sincospi((double)q / (double)n, &s, &c);
-  }
+  const hb_c<double> ph = hb_chirp_phase(i, n, M);
   hb_c<T> r;
-  r.x = (T)c; r.y = (T)s;
+  r.x = (T)ph.x; r.y = (T)ph.y;
   b[row * M + i] = r;
   if (i < n) {
     r.y = -r.y;
@@ -694,76 +674,67 @@ struct mm_hilbert {
   void* hi;
 };
 
+// The one radix -> instantiation table: f(the kernel's radix as a std::integral_constant, whether it is a fused pair) for
+// the pass radix R of a plan (256 / 625: two passes of radix 16 / 25 fused).  RG, a ragged batch: M is a power of two, so
+// radix 256, 16, 8, 4 or 2 only -- no ragged kernel of another radix is instantiated.
+template <bool RG, typename F>
+static void hb_with_radix(int R, F&& f) {
+#define MM_HB_CASE(RR, KR, FUSED) \
+  case RR: f(std::integral_constant<int, KR>{}, std::integral_constant<bool, FUSED>{}); return;
+  if constexpr (!RG) {
+    switch (R) {
+      MM_HB_CASE(625, 25, true)
+      MM_HB_CASE(49, 49, false) MM_HB_CASE(25, 25, false) MM_HB_CASE(9, 9, false) MM_HB_CASE(7, 7, false)
+      MM_HB_CASE(5, 5, false) MM_HB_CASE(3, 3, false)
+    }
+  }
+  switch (R) {
+    MM_HB_CASE(256, 16, true) MM_HB_CASE(16, 16, false) MM_HB_CASE(8, 8, false) MM_HB_CASE(4, 4, false)
+    default: f(std::integral_constant<int, 2>{}, std::false_type{});
+  }
+#undef MM_HB_CASE
+}
+
+// the XCD-ordered grid of a fused kernel: C butterflies of R^2 points per workgroup, rounded up to the 8 XCDs (MM_HB_FUSED_ITEM)
+template <typename T, int R>
+static dim3 hb_fused_grid(int64_t M, int64_t rows) {
+  constexpr int C = HbFuse<T, R>::C;
+  const int64_t total = ((M / (R * R) + C - 1) / C) * rows;
+  return dim3((unsigned)((total + 7) / 8 * 8));
+}
+
+static dim3 hb_single_grid(int64_t M, int R, int64_t rows) {
+  return dim3((unsigned)((M / R + MM_HB_THREADS - 1) / MM_HB_THREADS), (unsigned)rows);
+}
+
 template <typename T, bool RG = false>
 static void hb_launch_pass(int R, const hb_c<T>* in, hb_c<T>* out, int64_t M, int64_t Ns, int64_t rows,
                            const hb_c<double>* lo, const hb_c<double>* hi, const HbIo<T>& io, hipStream_t st) {
-  if constexpr (RG) {                   // a ragged batch: M is a power of two, so radix 256 (fused), 16, 8, 4 or 2
-    if (R == 256) {
-      constexpr int C = HbFuse<T, 16>::C;
-      const int64_t total = ((M / 256 + C - 1) / C) * rows;
-      hipLaunchKernelGGL((hb_pass2_kernel<T, 16, true>), dim3((unsigned)((total + 7) / 8 * 8)), dim3(C * 16), 0, st, in, out, M,
-                         Ns, rows, lo, hi, io);
-      return;
-    }
-    const dim3 grid((unsigned)((M / R + MM_HB_THREADS - 1) / MM_HB_THREADS), (unsigned)rows), block(MM_HB_THREADS);
-    switch (R) {
-      case 16: hipLaunchKernelGGL((hb_pass_kernel<T, 16, true>), grid, block, 0, st, in, out, M, Ns, lo, hi, io); break;
-      case 8: hipLaunchKernelGGL((hb_pass_kernel<T, 8, true>), grid, block, 0, st, in, out, M, Ns, lo, hi, io); break;
-      case 4: hipLaunchKernelGGL((hb_pass_kernel<T, 4, true>), grid, block, 0, st, in, out, M, Ns, lo, hi, io); break;
-      default: hipLaunchKernelGGL((hb_pass_kernel<T, 2, true>), grid, block, 0, st, in, out, M, Ns, lo, hi, io); break;
-    }
-    return;
-  }
-  if (R == 256 || R == 625) {           // two passes of radix 16 / 25 fused
-    if (R == 256) {
-      constexpr int C = HbFuse<T, 16>::C;
-      const int64_t total = ((M / 256 + C - 1) / C) * rows;
-      hipLaunchKernelGGL((hb_pass2_kernel<T, 16>), dim3((unsigned)((total + 7) / 8 * 8)), dim3(C * 16), 0, st, in, out, M, Ns,
-                         rows, lo, hi, io);
+  hb_with_radix<RG>(R, [&](auto radix, auto fused) {
+    constexpr int KR = decltype(radix)::value;
+    if constexpr (decltype(fused)::value) {
+      const dim3 grid = hb_fused_grid<T, KR>(M, rows), block(HbFuse<T, KR>::THREADS);
+      hipLaunchKernelGGL((hb_pass2_kernel<T, KR, RG>), grid, block, 0, st, in, out, M, Ns, rows, lo, hi, io);
     } else {
-      constexpr int C = HbFuse<T, 25>::C;
-      const int64_t total = ((M / 625 + C - 1) / C) * rows;
-      hipLaunchKernelGGL((hb_pass2_kernel<T, 25>), dim3((unsigned)((total + 7) / 8 * 8)), dim3(C * 25), 0, st, in, out, M, Ns,
-                         rows, lo, hi, io);
+      hipLaunchKernelGGL((hb_pass_kernel<T, KR, RG>), hb_single_grid(M, KR, rows), dim3(MM_HB_THREADS), 0, st, in, out, M, Ns, lo,
+                         hi, io);
     }
-    return;
-  }
-  const dim3 grid((unsigned)((M / R + MM_HB_THREADS - 1) / MM_HB_THREADS), (unsigned)rows);
-#define MM_HB_CASE(RR) \
-  case RR: hipLaunchKernelGGL((hb_pass_kernel<T, RR>), grid, dim3(MM_HB_THREADS), 0, st, in, out, M, Ns, lo, hi, io); break;
-  switch (R) {
-    MM_HB_CASE(49) MM_HB_CASE(25) MM_HB_CASE(9) MM_HB_CASE(7) MM_HB_CASE(5) MM_HB_CASE(3)
-    MM_HB_CASE(16) MM_HB_CASE(8) MM_HB_CASE(4)
-    default: hipLaunchKernelGGL((hb_pass_kernel<T, 2>), grid, dim3(MM_HB_THREADS), 0, st, in, out, M, Ns, lo, hi, io); break;
-  }
-#undef MM_HB_CASE
+  });
 }
 
 // the fused middle of a directly transformed envelope (hb_mid2_kernel / hb_mid_kernel) for the pass radix R
 template <typename T>
 static void hb_launch_mid(int R, const hb_c<T>* in, hb_c<T>* out, int64_t M, int64_t rows, const hb_c<double>* lo,
                           const hb_c<double>* hi, const HbIo<T>& io, hipStream_t st) {
-  if (R == 256) {
-    constexpr int C = HbFuse<T, 16>::C;
-    const int64_t total = ((M / 256 + C - 1) / C) * rows;
-    hipLaunchKernelGGL((hb_mid2_kernel<T, 16>), dim3((unsigned)((total + 7) / 8 * 8)), dim3(C * 16), 0, st, in, out, M, rows, lo, hi, io);
-    return;
-  }
-  if (R == 625) {
-    constexpr int C = HbFuse<T, 25>::C;
-    const int64_t total = ((M / 625 + C - 1) / C) * rows;
-    hipLaunchKernelGGL((hb_mid2_kernel<T, 25>), dim3((unsigned)((total + 7) / 8 * 8)), dim3(C * 25), 0, st, in, out, M, rows, lo, hi, io);
-    return;
-  }
-  const dim3 grid((unsigned)((M / R + MM_HB_THREADS - 1) / MM_HB_THREADS), (unsigned)rows);
-#define MM_HB_MID(RR) \
-  case RR: hipLaunchKernelGGL((hb_mid_kernel<T, RR>), grid, dim3(MM_HB_THREADS), 0, st, in, out, M, lo, hi, io); break;
-  switch (R) {
-    MM_HB_MID(49) MM_HB_MID(25) MM_HB_MID(9) MM_HB_MID(7) MM_HB_MID(5) MM_HB_MID(3)
-    MM_HB_MID(16) MM_HB_MID(8) MM_HB_MID(4)
-    default: hipLaunchKernelGGL((hb_mid_kernel<T, 2>), grid, dim3(MM_HB_THREADS), 0, st, in, out, M, lo, hi, io); break;
-  }
-#undef MM_HB_MID
+  hb_with_radix<false>(R, [&](auto radix, auto fused) {
+    constexpr int KR = decltype(radix)::value;
+    if constexpr (decltype(fused)::value) {
+      const dim3 grid = hb_fused_grid<T, KR>(M, rows), block(HbFuse<T, KR>::THREADS);
+      hipLaunchKernelGGL((hb_mid2_kernel<T, KR>), grid, block, 0, st, in, out, M, rows, lo, hi, io);
+    } else {
+      hipLaunchKernelGGL((hb_mid_kernel<T, KR>), hb_single_grid(M, KR, rows), dim3(MM_HB_THREADS), 0, st, in, out, M, lo, hi, io);
+    }
+  });
 }
 
 // forward FFT of `rows` rows of M points: *cur holds the input and, on return, the output; *other is scratch.
@@ -784,6 +755,23 @@ static void hb_fft(const mm_hilbert* h, hb_c<T>** cur, hb_c<T>** other, int64_t 
     Ns *= R;
     std::swap(*cur, *other);
   }
+}
+
+// The envelope through chirps, four transforms: chirp transform 1: (x w) -> FFT -> * Bhat -> inverse FFT (as a forward one
+// of the conjugate) -> * w / M; mask; chirp transform 2 of conj(Y) the same way; magnitude.  io: the clips, the chirp, its
+// spectrum, the envelope and n (RG: n_max, every row's own n, w, bhat and scale 1 / (M n_b) by hb_row_setup).
+template <typename T, bool RG>
+static void hb_chirp_envelope(const mm_hilbert* h, hb_c<T>** cur, hb_c<T>** other, int64_t rows, const hb_c<double>* lo,
+                              const hb_c<double>* hi, HbIo<T> io, hipStream_t st) {
+  io.in_mode = HB_IN_REAL_CHIRP; io.out_mode = HB_OUT_MUL_CONJ;
+  hb_fft<T, RG>(h, cur, other, rows, lo, hi, io, st);
+  io.in_mode = HB_IN_COMPLEX; io.out_mode = HB_OUT_BLUESTEIN_MID; io.scale = (T)(1.0 / (double)h->M);
+  hb_fft<T, RG>(h, cur, other, rows, lo, hi, io, st);
+  io.out_mode = HB_OUT_MUL_CONJ;
+  hb_fft<T, RG>(h, cur, other, rows, lo, hi, io, st);
+  // (RG: io.n is n_max and this scale a placeholder -- hb_row_setup<T, true> writes the row's 1 / (M n_b) over it)
+  io.out_mode = HB_OUT_ENVELOPE; io.scale = (T)(1.0 / ((double)h->M * (double)io.n));
+  hb_fft<T, RG>(h, cur, other, rows, lo, hi, io, st);
 }
 
 static void hb_free(mm_hilbert* h) {
@@ -953,16 +941,7 @@ static int hb_envelope(const mm_hilbert* h, const T* d_x, int64_t rows, int64_t 
     hipLaunchKernelGGL(hb_abs_kernel<T>, dim3((unsigned)((x_rows + 255) / 256)), dim3(256), 0, st, d_x, x_stride, x_rows, d_env,
                        env_stride);
   } else if (h->bluestein) {
-    // chirp transform 1: (x w) -> FFT -> * Bhat -> inverse FFT (as a forward one of the conjugate) -> * w / M;
-    // mask; chirp transform 2 of conj(Y) the same way; magnitude
-    io.in_mode = HB_IN_REAL_CHIRP; io.out_mode = HB_OUT_MUL_CONJ;
-    hb_fft<T>(h, &cur, &other, rows, lo, hi, io, st);
-    io.in_mode = HB_IN_COMPLEX; io.out_mode = HB_OUT_BLUESTEIN_MID; io.scale = (T)(1.0 / (double)M);
-    hb_fft<T>(h, &cur, &other, rows, lo, hi, io, st);
-    io.out_mode = HB_OUT_MUL_CONJ;
-    hb_fft<T>(h, &cur, &other, rows, lo, hi, io, st);
-    io.out_mode = HB_OUT_ENVELOPE; io.scale = (T)(1.0 / ((double)M * (double)n));
-    hb_fft<T>(h, &cur, &other, rows, lo, hi, io, st);
+    hb_chirp_envelope<T, false>(h, &cur, &other, rows, lo, hi, io, st);
   } else {
     // forward passes 0 .. P-2 | the fused middle: forward pass P-1, mask, inverse pass P-1 (hb_mid*_kernel) | inverse passes
     // P-2 .. 0 (the inverse in the opposite radix order: any order is a valid Stockham factorisation); the clips ride in
@@ -1044,14 +1023,7 @@ static int hb_envelope_ragged(const mm_hilbert* h, const T* d_x, int64_t rows, i
   HbIo<T> io = {};
   io.x = d_x; io.x_stride = x_stride; io.w = w; io.bhat = bhat; io.env = d_env; io.env_stride = env_stride;
   io.n = n_max; io.n_max = n_max; io.x_rows = rows; io.lens = d_lens; io.bad = bad;
-  io.in_mode = HB_IN_REAL_CHIRP; io.out_mode = HB_OUT_MUL_CONJ;
-  hb_fft<T, true>(h, &cur, &other, rows, lo, hi, io, st);
-  io.in_mode = HB_IN_COMPLEX; io.out_mode = HB_OUT_BLUESTEIN_MID; io.scale = (T)(1.0 / (double)M);
-  hb_fft<T, true>(h, &cur, &other, rows, lo, hi, io, st);
-  io.out_mode = HB_OUT_MUL_CONJ;
-  hb_fft<T, true>(h, &cur, &other, rows, lo, hi, io, st);
-  io.out_mode = HB_OUT_ENVELOPE;               // (the scale 1 / (M n_b): hb_row_setup)
-  hb_fft<T, true>(h, &cur, &other, rows, lo, hi, io, st);
+  hb_chirp_envelope<T, true>(h, &cur, &other, rows, lo, hi, io, st);
   HIP_TRY(hipGetLastError());
   return MM_OK;
 }

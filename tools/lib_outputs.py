@@ -13,7 +13,13 @@ Case set `ragged`: every public *_ragged_batch function with host and with devic
 Case set `welch`: every instantiation and path of the Welch power and cross spectrum kernels (welch_cases).
 Case set `gapfill`: every interp_NAN kind through the five gap-filling calls -- shapes, types, layouts, rows with too few valid
 samples, counts, host inputs, get_f0 / get_f0_batch -- with every refusal's type and text (gapfill_cases); for a change of
-the host code, run on two checkouts with the same library as well."""
+the host code, run on two checkouts with the same library as well.
+Case set `hilbert`: the three call paths of mm_hilbert.hip.inc (hilbert_cases), float32 and float64, contiguous rows, on the
+oracle's case rows (tests/hilbert_oracle.py rows_for / take: the zero row is in).  Envelope: ENVELOPE_LENGTHS +
+BLUESTEIN_LENGTHS with 1 / 2 / 5 / 37 rows, LONG_CASES with 5 float32 rows, test_many_rows' 256 x 1000, 625 x 1001 and
+35 x 1000, nine rows of 625 / 9600 / 511 under a two-pair workspace bound, a NaN row and an infinity row at 9600 (direct) and
+511 (chirps).  Forward transform: FORWARD_LENGTHS through calc.rfft_rows_long with 1 / 5 / 37 rows.  Ragged: RAGGED_M with
+test_ragged's lengths.  Beyond 20 000 samples 5 rows only.  614 arrays, 211 MB: compare where they were written."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -496,7 +502,82 @@ def gapfill_cases():
     return out
 
 
-CASESETS = {"s16": s16_cases, "tail": tail_cases, "ragged": ragged_cases, "welch": welch_cases, "gapfill": gapfill_cases}
+def hilbert_cases():
+    """Case set `hilbert`: the three call paths of csrc/mm_hilbert.hip.inc on the length lists of tests/hilbert_oracle.py (which
+    tests/test_hilbert_host.py proves to reach every kernel instantiation), on the oracle's case rows, contiguous."""
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import hilbert_oracle as H
+    import modspec_oracle as MO
+    from test_gpu_hilbert import BIG, _ragged_lengths
+    from modulation_mfcc_amd import _lib, calc
+    dev = torch.device("cuda", 0)
+    out = {}
+    DTYPES = ("float32", "float64")
+
+    def put(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+    def envelope(name, x):
+        out[name] = calc.hilbert_envelope_batch(put(x)).cpu().numpy()
+
+    def row_counts(n, counts):
+        return (5,) if n > BIG else counts
+
+    # mm_hilbert_envelope: every direct and chirp plan, 1 row (unpaired), 2, 5 (the last clip without a partner) and 37
+    for n in H.ENVELOPE_LENGTHS + H.BLUESTEIN_LENGTHS:
+        for dt in DTYPES:
+            rows = H.rows_for(n, dt)
+            for R in row_counts(n, H.ENVELOPE_ROWS):
+                envelope("env.n%d.%s.r%d" % (n, dt, R), H.take(rows, R)[0])
+    for n in H.LONG_CASES:
+        envelope("env.long.n%d" % n, H.take(H.rows_for(n, "float32"), 5)[0])
+    # the XCD-ordered block lists with a block count that is no multiple of eight, and a plain plan beside them
+    for n, R in ((256, 1000), (625, 1001), (35, 1000)):
+        for dt in DTYPES:
+            envelope("env.many.n%d.%s.r%d" % (n, dt, R), H.take(H.rows_for(n, dt), R)[0])
+    # nine rows under a workspace bound that takes two pairs: library calls of 4, 4 and 1 rows
+    for n in (625, 9600, 511):
+        for code, dt in enumerate(DTYPES):
+            per_pair = int(_lib.load().mm_hilbert_workspace_bytes(calc._hilbert_plan(n, code, dev).h, 2))
+            old = calc.HILBERT_WS_BYTES
+            try:
+                calc.HILBERT_WS_BYTES = 2 * per_pair
+                envelope("env.chunked.n%d.%s" % (n, dt), H.take(H.rows_for(n, dt), 9)[0])
+            finally:
+                calc.HILBERT_WS_BYTES = old
+    # a row with a NaN and a row with an infinity beside four finite ones: a direct length and a chirp length
+    for n in (9600, 511):
+        for dt in DTYPES:
+            for value in (np.nan, np.inf):
+                x = H.take(H.rows_for(n, dt), 5)[0].copy()
+                x[0, n // 3] = value
+                envelope("env.%s.n%d.%s" % (value, n, dt), x)
+    print("envelope: %d arrays" % len(out), flush=True)
+    # mm_hilbert_rfft_f32: the forward passes alone, all samples valid and zeros behind the last three
+    for n in H.FORWARD_LENGTHS:
+        rows = H.rows_for(n, "float32")
+        for R in row_counts(n, (1, 5, 37)):
+            x = H.take(rows, R)[0]
+            for T in sorted({n, max(1, n - 3)}):
+                out["rfft.n%d.T%d.r%d" % (n, T, R)] = calc.rfft_rows_long(put(x[:, :T]), n).cpu().numpy()
+    print("envelope + forward transform: %d arrays" % len(out), flush=True)
+    # mm_hilbert_envelope_ragged with device lengths: test_ragged's clips, NaN behind every one of them
+    for M_fft in H.RAGGED_M:
+        n_max = M_fft // 2
+        lengths = _ragged_lengths(n_max)
+        for dt in DTYPES:
+            x = np.full((len(lengths), n_max), np.nan, dtype=dt)
+            for b, L in enumerate(lengths):
+                x[b, :L] = H.rows_for(L, dt)[(H.ROW_LOUD + 3 * b) % MO.N_CASES]
+            lens = torch.tensor(lengths, dtype=torch.int64, device=dev)
+            out["ragged.M%d.%s" % (M_fft, dt)] = calc.hilbert_envelope_ragged_batch(put(x), lens).cpu().numpy()
+    torch.cuda.synchronize()
+    return out
+
+
+CASESETS = {"s16": s16_cases, "tail": tail_cases, "ragged": ragged_cases, "welch": welch_cases, "gapfill": gapfill_cases,
+            "hilbert": hilbert_cases}
 
 if __name__ == "__main__":
     if len(sys.argv) == 4 and sys.argv[1] == "--compare":
