@@ -32,6 +32,8 @@ from .interp import interp_nan_spline_batch, interp_nan_spline_ragged_batch  # n
 from .lomb import modulation_lombscargle_batch, modulation_lombscargle_ragged_batch, modulation_lombscargle_list  # noqa: F401
 from .zoom import (zoom_batch, zoom_ragged_batch, spline_filter_batch, spectrogram_image,  # noqa: F401
                    spectrogram_image_batch)
+from .pspec import (praat_spectrogram_params, praat_spectrogram_batch, praat_spectrogram_ragged_batch,  # noqa: F401
+                    praat_spectrogram_list, Parselmouth, Sound, Spectrogram, spectrogram_view)
 from .ema import read_AG50x, read_AG50x_arrays, read_pos_header  # noqa: F401
 
 __version__ = "0.2.0"

@@ -1,7 +1,7 @@
 """ctypes binding of libmodmfcc.so (include/modmfcc.h and, for the Welch modulation power spectrum, include/modmfcc_modpsd.h;
 for the Welch cross spectrum and coherence, include/modmfcc_modcsd.h; for the quadratic and cubic spline gap filling,
 include/modmfcc_spline.h; for the Lomb-Scargle periodogram of rows with holes, include/modmfcc_lomb.h; for the B-spline zoom
-of 2-D feature images, include/modmfcc_zoom.h).
+of 2-D feature images, include/modmfcc_zoom.h; for the Praat-style spectrogram, include/modmfcc_pspec.h).
 
 There is NO CPU fallback: when the shared library cannot be loaded, or a plan cannot be created
 because no MI355X is visible, the calls raise.  Build the library with
@@ -291,6 +291,28 @@ PROTOTYPES_ZOOM = {
     "mm_zoom2d_ragged_f64": (C.c_int, _zoom_args + [_vp, C.c_double] + _zoom_out),
 }
 
+
+
+class mm_pspec_params(C.Structure):
+    _fields_ = [
+        ("scale", C.c_double),
+        ("nw", C.c_int32), ("nfft", C.c_int32), ("bw", C.c_int32), ("n_freqs", C.c_int32), ("channels", C.c_int32),
+        ("span", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+# every symbol include/modmfcc_pspec.h declares (the seventh header: the Praat-style spectrogram; no entry takes a workspace)
+MM_PSPEC_MAX_NFFT, MM_PSPEC_MAX_CHANNELS, MM_PSPEC_DB = 4096, 8, 1
+_psp = C.POINTER(mm_pspec_params)
+_pspec_args = [_psp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp]
+PROTOTYPES_PSPEC = {
+    "mm_pspec_version": (C.c_int, []),
+    "mm_pspec_check": (C.c_int, [_psp]),
+    "mm_pspec_tile_frames": (C.c_int32, [_psp]),
+    "mm_pspec_f32": (C.c_int, _pspec_args),
+    "mm_pspec_f64": (C.c_int, _pspec_args),
+}
+
 _lib = None
 _torch = None       # the torch module, bound by load(): call() and workspace() look nothing up per call
 
@@ -314,7 +336,8 @@ def load():
             "`make -C modulation_mfcc_amd/csrc` (needs hipcc, --offload-arch=gfx950). "
             "modulation_mfcc_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for table in (PROTOTYPES, PROTOTYPES_MODPSD, PROTOTYPES_MODCSD, PROTOTYPES_SPLINE, PROTOTYPES_LOMB, PROTOTYPES_ZOOM):
+    for table in (PROTOTYPES, PROTOTYPES_MODPSD, PROTOTYPES_MODCSD, PROTOTYPES_SPLINE, PROTOTYPES_LOMB, PROTOTYPES_ZOOM,
+                  PROTOTYPES_PSPEC):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError when the .so is stale
             fn.restype = res

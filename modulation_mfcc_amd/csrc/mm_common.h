@@ -91,6 +91,12 @@ __device__ __forceinline__ void wg_barrier_lds() {
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
   return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
+__device__ __forceinline__ double2 cmul(double2 a, double2 b) {
+  return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
+}
+// a complex value of either precision from its parts (the transforms below are written once for float2 and double2)
+__device__ __forceinline__ float2 mm_cplx(float re, float im) { return make_float2(re, im); }
+__device__ __forceinline__ double2 mm_cplx(double re, double im) { return make_double2(re, im); }
 
 // order-preserving float -> int key for atomicMax
 __device__ __forceinline__ int float_key(float f) {
@@ -115,22 +121,23 @@ __device__ __forceinline__ float wave_min(float v) {
 
 typedef float mm_f32x4 __attribute__((ext_vector_type(4)));   // accumulator of v_mfma_f32_16x16x4_f32
 
-// In-place radix-2 DIT over a wave-private LDS buffer; input already bit-reversed.
-__device__ __forceinline__ void wave_cfft_lds(float2* z, int log2nc, const float2* __restrict__ tw,
-                                              int lane) {
+// In-place radix-2 DIT over a wave-private LDS buffer; input already bit-reversed.  C2: float2 or double2.  tw holds
+// exp(-2 pi i k / tw_n): the master table of MM_TW_N entries, or a table of the transform's own (tw_n / 2 entries suffice).
+template <class C2>
+__device__ __forceinline__ void wave_cfft_lds(C2* z, int log2nc, const C2* __restrict__ tw, int lane, int tw_n = MM_TW_N) {
   const int nc = 1 << log2nc;
   for (int s = 1; s <= log2nc; ++s) {
     const int half = 1 << (s - 1);
-    const int tw_stride = MM_TW_N >> s;
+    const int tw_stride = tw_n >> s;
     for (int j = lane; j < (nc >> 1); j += 64) {
       const int pos = j & (half - 1);
       const int i0 = ((j >> (s - 1)) << s) + pos;
       const int i1 = i0 + half;
-      const float2 w = tw[pos * tw_stride];
-      const float2 a = z[i0];
-      const float2 t = cmul(w, z[i1]);
-      z[i0] = make_float2(a.x + t.x, a.y + t.y);
-      z[i1] = make_float2(a.x - t.x, a.y - t.y);
+      const C2 w = tw[pos * tw_stride];
+      const C2 a = z[i0];
+      const C2 t = cmul(w, z[i1]);
+      z[i0] = mm_cplx(a.x + t.x, a.y + t.y);
+      z[i1] = mm_cplx(a.x - t.x, a.y - t.y);
     }
     wave_lds_sync();
   }
@@ -138,16 +145,19 @@ __device__ __forceinline__ void wave_cfft_lds(float2* z, int log2nc, const float
 
 // Split the half-length complex FFT Z (nc points, in LDS) of a packed real row into the real
 // FFT bins k and nc-k.  Returns X[k] in xa and X[nc-k] in xb.
-__device__ __forceinline__ void real_split(const float2* z, int k, int nc, const float2* __restrict__ tw,
-                                           int tw_stride, float2& xa, float2& xb) {
-  const float2 a = z[k];
-  const float2 b = z[(nc - k) & (nc - 1)];
-  const float2 E = make_float2(0.5f * (a.x + b.x), 0.5f * (a.y - b.y));
-  const float2 D = make_float2(0.5f * (a.x - b.x), 0.5f * (a.y + b.y));
-  const float2 O = make_float2(D.y, -D.x);  // -i * D
-  const float2 t = cmul(tw[k * tw_stride], O);
-  xa = make_float2(E.x + t.x, E.y + t.y);
-  xb = make_float2(E.x - t.x, -(E.y - t.y));
+template <class C2>
+__device__ __forceinline__ void real_split(const C2* z, int k, int nc, const C2* __restrict__ tw, int tw_stride, C2& xa,
+                                           C2& xb) {
+  using R = decltype(xa.x);
+  const R h = (R)0.5;
+  const C2 a = z[k];
+  const C2 b = z[(nc - k) & (nc - 1)];
+  const C2 E = mm_cplx(h * (a.x + b.x), h * (a.y - b.y));
+  const C2 D = mm_cplx(h * (a.x - b.x), h * (a.y + b.y));
+  const C2 O = mm_cplx(D.y, -D.x);  // -i * D
+  const C2 t = cmul(tw[k * tw_stride], O);
+  xa = mm_cplx(E.x + t.x, E.y + t.y);
+  xb = mm_cplx(E.x - t.x, -(E.y - t.y));
 }
 
 // native vector types and explicit address spaces (1 = global, 3 = LDS) for code that must not fall back to flat accesses

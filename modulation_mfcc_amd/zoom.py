@@ -189,7 +189,8 @@ def spectrogram_image(spect_data, zoom_blur=True):
 
 
 def spectrogram_image_batch(power, zoom=6, order=4, db=True):
-    """The viewer's image from a POWER spectrogram [F, T] or [B, F, T] (what MfccPlan.stft_power returns, or any strictly
-    positive image): ``scipy.ndimage.zoom(10 * numpy.log10(power), zoom, order=order)`` with the dB step taken on load, in
-    float64, without a pass of its own."""
+    """The viewer's image from a POWER spectrogram [F, T] or [B, F, T] (what pspec.praat_spectrogram_batch returns -- the
+    reference's Sound.to_spectrogram; pspec.spectrogram_view is the whole chain -- or any strictly positive image):
+    ``scipy.ndimage.zoom(10 * numpy.log10(power), zoom, order=order)`` with the dB step taken on load, in float64, without
+    a pass of its own."""
     return zoom_batch(power, zoom, order=order, db=db)
