@@ -34,6 +34,8 @@ from .zoom import (zoom_batch, zoom_ragged_batch, spline_filter_batch, spectrogr
                    spectrogram_image_batch)
 from .pspec import (praat_spectrogram_params, praat_spectrogram_batch, praat_spectrogram_ragged_batch,  # noqa: F401
                     praat_spectrogram_list, Parselmouth, Sound, Spectrogram, spectrogram_view)
+from .pint import (praat_intensity_params, praat_intensity_batch, praat_intensity_ragged_batch,  # noqa: F401
+                   praat_intensity_list, Intensity, to_intensity, praat_rms_envelope)
 from .ema import read_AG50x, read_AG50x_arrays, read_pos_header  # noqa: F401
 
 __version__ = "0.2.0"

@@ -1,7 +1,8 @@
 """ctypes binding of libmodmfcc.so (include/modmfcc.h and, for the Welch modulation power spectrum, include/modmfcc_modpsd.h;
 for the Welch cross spectrum and coherence, include/modmfcc_modcsd.h; for the quadratic and cubic spline gap filling,
 include/modmfcc_spline.h; for the Lomb-Scargle periodogram of rows with holes, include/modmfcc_lomb.h; for the B-spline zoom
-of 2-D feature images, include/modmfcc_zoom.h; for the Praat-style spectrogram, include/modmfcc_pspec.h).
+of 2-D feature images, include/modmfcc_zoom.h; for the Praat-style spectrogram, include/modmfcc_pspec.h; for Praat's
+intensity contour, include/modmfcc_pint.h).
 
 There is NO CPU fallback: when the shared library cannot be loaded, or a plan cannot be created
 because no MI355X is visible, the calls raise.  Build the library with
@@ -313,6 +314,27 @@ PROTOTYPES_PSPEC = {
     "mm_pspec_f64": (C.c_int, _pspec_args),
 }
 
+
+
+class mm_pint_params(C.Structure):
+    _fields_ = [("hw", C.c_int32), ("channels", C.c_int32), ("span", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+# every symbol include/modmfcc_pint.h declares (the eighth header: Praat's intensity contour; no entry takes a workspace)
+MM_PINT_MAX_HALF, MM_PINT_MAX_CHANNELS = 16384, 8
+MM_PINT_LINEAR, MM_PINT_KEEP_MEAN = 1, 2
+MM_PINT_NEAREST, MM_PINT_LINEAR_INTERP, MM_PINT_CUBIC = 0, 1, 2
+_pip = C.POINTER(mm_pint_params)
+_pint_args = [_pip, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]
+PROTOTYPES_PINT = {
+    "mm_pint_version": (C.c_int, []),
+    "mm_pint_check": (C.c_int, [_pip]),
+    "mm_pint_tile_frames": (C.c_int32, [_pip]),
+    "mm_pint_f32": (C.c_int, _pint_args),
+    "mm_pint_f64": (C.c_int, _pint_args),
+    "mm_pint_value_f64": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, C.c_double, _vp, _i64, _i64, C.c_int32, _vp, _i64, _vp]),
+}
+
 _lib = None
 _torch = None       # the torch module, bound by load(): call() and workspace() look nothing up per call
 
@@ -337,7 +359,7 @@ def load():
             "modulation_mfcc_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for table in (PROTOTYPES, PROTOTYPES_MODPSD, PROTOTYPES_MODCSD, PROTOTYPES_SPLINE, PROTOTYPES_LOMB, PROTOTYPES_ZOOM,
-                  PROTOTYPES_PSPEC):
+                  PROTOTYPES_PSPEC, PROTOTYPES_PINT):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError when the .so is stale
             fn.restype = res
